@@ -7,7 +7,9 @@ ONE per-GPU workload for every --gpus N, so that the driver's N = 1, 2, 4, 8 val
   R->L + novel-view blend through pf_novel_view_dev; weak scaling, no collective on the data path.  With N > 1 (or
   PANOFLOW_FORCE_DIST=1 on one GPU) the blended strips are additionally gathered to rank 0 over RCCL inside libpanoflow.so
   (pf_dist_*), overlapped with the next pair.  `value` = N x 36 Mpix x steps / max-over-ranks time.
-At N = 1 the same JSON line carries, as extra keys timed in-process (never `value`):
+A plain run sets up, warms up, times --steps steps and prints the headline keys; --dump-outputs DIR also writes a fixed sample of what
+the last timed step computed.  Everything else needs --full: the timed pairs checked against their oracle fixtures (`fixture_ok`),
+the per-kernel-family breakdown, `config5_strong`, the roofline figures and, at N = 1, these extra keys timed in-process (never `value`):
   `strip_2000x4000`  BASELINE configs[1] (one 2000x4000 strip, what rounds 1-2 quoted `value` on),
   `config4_chain`    BASELINE configs[3] (5+top stitch chain at 9000x4000, pixflow_search_20, host images -> host composite),
   `throughput_mode`  several independent strips side by side on the GPU (pf_novel_view_batch_dev),
@@ -220,6 +222,37 @@ def config5_strong(torch, np, pf, synth, shard, dist, pfd, local_rank, dev, rank
             "workload": "BASELINE configs[4] as strong scaling: the %d oracle-fixture pairs (seeds 1234..%d), pair i on rank i mod N, each rank's share as one batch in flight" % (P, 1233 + P)}
 
 
+def dump_outputs(d, torch, np, f0, f1, strip):
+    """--dump-outputs: what the last timed step handed back -- flow L->R and R->L (float32 dx, dy) and the blended strip (its BGRA bytes
+    as float32) -- at the same pixels on every run of a size (a seeded sample of 1 Mpix when the pair is larger: 32 MB in all), so that
+    two builds can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    rows, cols = f0.shape[:2]
+    n = rows * cols
+    k = min(n, 1 << 20)
+    idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False)) if k < n else np.arange(n)
+    idx = torch.from_numpy(idx).to(f0.device)
+    for name, t in (("flow_l2r", f0), ("flow_r2l", f1), ("novel_view", strip)):
+        np.save(os.path.join(d, name + ".npy"), t.reshape(n, -1)[idx].float().cpu().numpy())
+
+
+def finish(rank, res, pfd, dist):
+    """Closes the library's communicator and torch.distributed (`dist` None: never initialised) and prints the result line on rank 0."""
+    if pfd:
+        pfd.close()
+    if dist is not None:
+        dist.destroy_process_group()
+    if rank == 0:
+        # RCCL prints a version banner through C stdio, which a pipe only delivers at exit: flush it first so that the
+        # JSON line is the last thing on stdout
+        try:
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -228,6 +261,10 @@ def main():
     ap.add_argument("--cols", type=int, default=9000, help="default 9000 (BASELINE configs[4] / north_star: one 9000x4000 pair per GPU, for EVERY --gpus N)")
     ap.add_argument("--rows", type=int, default=4000)
     ap.add_argument("--alg", default="pixflow_low")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also check the timed pairs against their oracle fixtures and measure "
+                    "everything beyond the headline figure (per-kernel breakdown, roofline, config5_strong, copies, strip, chain, throughput mode, "
+                    "large displacements, CPU baseline); the --no-* and --pairs-total options below select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's flows and blended strip to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the 2000x4000 strip / config-4 chain / throughput / lone-band step-time legs")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
@@ -235,6 +272,8 @@ def main():
                     "(seeds 1234...) in total, sharded round-robin over the ranks, each rank's share as ONE batch in flight, all strips gathered to rank 0; 0 = skip")
     ap.add_argument("--concurrent", type=int, default=1, help="independent pairs in flight per GPU (one context + host thread each); 1 = the BASELINE config")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # a context drives 4 HIP streams (front end, two flow directions, blend ramp) next to torch's and RCCL's: with the
     # runtime's default of 4 hardware queues two of them could share a queue and serialise
@@ -346,17 +385,39 @@ def main():
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
     dt = pfd.max(dt) if pfd else (shard.max_over_ranks(dt, dev) if og else dt)
+    med_ms = statistics.median(step_ms)
+    swept = ctx.last_swept_steps()
+    last_out = og.bufs[(og.k - 1) % 2] if og else out
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, np, f0, f1, last_out)
+    res = None
+    if rank == 0:
+        mpix = cols * rows / 1e6
+        npairs = world * max(1, args.concurrent)
+        value = npairs * mpix * args.steps / dt
+        P, nlev, sweep_steps = pf.level_pixels(cols, rows)
+        which = "BASELINE configs[4] / north_star" if (cols, rows) == (9000, 4000) else ("BASELINE configs[1]" if (cols, rows) == (2000, 4000) else "custom size")
+        res = {
+            "metric": "Mpix/s bidirectional optical flow (overlap strip) at 1/2/4/8 GPU", "value": round(value, 3), "unit": "Mpix/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s: one dense %dx%d overlap pair per GPU (the same for every --gpus N), %s, flow L->R + R->L + novel-view blend, %d pair(s) in flight per GPU"
+                                   % (which, cols, rows, args.alg, max(1, args.concurrent)),
+                       "levels": nlev, "level_pixels": P, "sweep_steps_per_direction": sweep_steps, "swept_steps_per_direction_in_gated_window": swept,
+                       "final_gather": (gather_note or "rccl send/recv to rank 0 inside libpanoflow.so (pf_dist_*), overlapped with the next pair") if og else "none (single rank)"},
+            "ms_per_step_median": round(med_ms, 3), "value_at_median": round(npairs * mpix / (med_ms * 1e-3), 3),
+        }
+    if not args.full:
+        finish(rank, res, pfd, dist if (world > 1 or force_dist) else None)
+        return
     gathered_ok = None
     if og and rank == 0:
         # the strip this rank produced last must be what arrived in its own slot of the receive area
         gathered_ok = bool(torch.equal(og.last()[0], og.bufs[(og.k - 1) % 2]))
-    med_ms = statistics.median(step_ms)
-    swept = ctx.last_swept_steps()
 
     # ---- self-validation, off the clock: EVERY rank holds the outputs of its own timed pair (seed 1234 + rank) against the oracle
     # fixture of that seed; the verdicts are all-reduced, and rank 0 additionally checks every gathered slot against the SHA-256 of
     # the strip its producer should have made -- an N-GPU run needs nothing else to be trusted ----
-    last_out = og.bufs[(og.k - 1) % 2] if og else out
     fx_ok, fx_detail = fixture_verdict(np, cols, rows, args.alg, 1234 + rank, L, R, blend, f0, f1, last_out)
     fx_all = fx_ok
     if world > 1 or force_dist:
@@ -384,23 +445,10 @@ def main():
     if args.pairs_total > 0 and (cols, rows, args.alg) == (9000, 4000, "pixflow_low") and args.concurrent <= 1 and args.pairs_total <= 8:
         strong = config5_strong(torch, np, pf, synth, shard, dist if (world > 1 or force_dist) else None, pfd, local_rank, dev, rank, world, cols, rows, args, (L, R, blend))
     if rank == 0:
-        mpix = cols * rows / 1e6
-        npairs = world * max(1, args.concurrent)
-        value = npairs * mpix * args.steps / dt
-        P, nlev, sweep_steps = pf.level_pixels(cols, rows)
         b_alg = pf.algorithmic_bytes(cols, rows)
-        which = "BASELINE configs[4] / north_star" if (cols, rows) == (9000, 4000) else ("BASELINE configs[1]" if (cols, rows) == (2000, 4000) else "custom size")
-        res = {
-            "metric": "Mpix/s bidirectional optical flow (overlap strip) at 1/2/4/8 GPU", "value": round(value, 3), "unit": "Mpix/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: one dense %dx%d overlap pair per GPU (the same for every --gpus N), %s, flow L->R + R->L + novel-view blend, %d pair(s) in flight per GPU"
-                                   % (which, cols, rows, args.alg, max(1, args.concurrent)),
-                       "levels": nlev, "level_pixels": P, "sweep_steps_per_direction": sweep_steps, "swept_steps_per_direction_in_gated_window": swept,
-                       "final_gather": ((gather_note or "rccl send/recv to rank 0 inside libpanoflow.so (pf_dist_*), overlapped with the next pair") + "; rank-0 slot verified: %s; every rank's slot equals its oracle fixture's strip: %s" % (gathered_ok, slots_ok)) if og else "none (single rank)"},
-            "fixture_ok": fx_all,
-            "ms_per_step_median": round(med_ms, 3), "value_at_median": round(npairs * mpix / (med_ms * 1e-3), 3),
-        }
+        if og:
+            res["config"]["final_gather"] += "; rank-0 slot verified: %s; every rank's slot equals its oracle fixture's strip: %s" % (gathered_ok, slots_ok)
+        res["fixture_ok"] = fx_all
         # roofline of the dominant kernel (the exact wavefront sweep): algorithmic bytes per launch =
         # 48 B per level-pixel (alpha/grad0 16 + blurred 8 + flow r/w 16 + grad1 gather 8)
         # x the level's pixels; 2 sweeps x 2 directions x all levels = 4*48*P bytes per step.
@@ -625,20 +673,7 @@ def main():
             res["large_displacement"] = ld
             ct.close()
             torch.cuda.empty_cache()
-        line = json.dumps(res)
-    if pfd:
-        pfd.close()
-    if world > 1 or force_dist:
-        dist.destroy_process_group()
-    if rank == 0:
-        # RCCL prints a version banner through C stdio, which a pipe only delivers at exit: flush it first so that the
-        # JSON line is the last thing on stdout
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(line, flush=True)
+    finish(rank, res, pfd, dist if (world > 1 or force_dist) else None)
 
 
 if __name__ == "__main__":

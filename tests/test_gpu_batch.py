@@ -78,7 +78,7 @@ def test_bench_forced_dist_path_validates_itself():
     lines = {}
     for force in ("0", "1"):
         e = dict(env, PANOFLOW_FORCE_DIST=force)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=e)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=e)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
         lines[force] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
     a, b = lines["0"], lines["1"]
@@ -92,3 +92,26 @@ def test_bench_forced_dist_path_validates_itself():
         st = ln["config5_strong"]
         assert st["scaling"] == "strong" and st["pairs_total"] == 8 and st["in_flight_per_rank"] == 8 and st["fixture_ok"] is True and st["value"] > 0
     assert a["config5_strong"]["gathered_strips_equal_fixtures"] is None and b["config5_strong"]["gathered_strips_equal_fixtures"] is True
+
+
+def test_bench_plain_run_dumps_the_timed_outputs(orc, synth, pf, tmp_path):
+    """A plain bench run times exactly --steps steps and prints the headline keys only; --dump-outputs writes what its last timed step
+    computed (every pixel at this size) as float32, equal to the oracle's flows and blended strip for the same seeded pair."""
+    import sys
+    from conftest import ROOT
+    cols, rows = 320, 256
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cols", str(cols), "--rows", str(rows),
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0 and res["dtype"] == "f32"
+    assert not {"fixture_ok", "roofline", "kernels_ms_per_step", "config5_strong", "cpu_baseline"} & set(res)
+    got = {n: np.load(d / (n + ".npy")) for n in ("flow_l2r", "flow_r2l", "novel_view")}
+    assert sorted(os.listdir(d)) == ["flow_l2r.npy", "flow_r2l.npy", "novel_view.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    L, R, blend = synth.make_pair_np(cols, rows, 1234)
+    r0, r1 = orc.flow_bidir(L, R, pf.max_percentage_by_name("pixflow_low"))
+    rout = orc.combine_novel_views(L, R, r0, r1, blend)
+    assert np.array_equal(got["flow_l2r"], r0.reshape(-1, 2)) and np.array_equal(got["flow_r2l"], r1.reshape(-1, 2))
+    assert np.array_equal(got["novel_view"], rout.reshape(-1, 4).astype(np.float32))
