@@ -265,6 +265,31 @@ int pf_stage_level(pf_ctx* ctx, const float* i0, const float* i1, const float* a
                    const float* flow_in /* nullable */, int hint, int max_percentage, float* flow_out); /* PixFlow.hpp:272-340 */
 int pf_stage_blend_smooth(pf_ctx* ctx, float* blend_inout, const float* merged_dis, int cols, int rows); /* StitchTool.cpp:130-143 */
 
+/* ---- flow visualisation ---------------------------------------------------------------------
+ * The reference's debugging views of a flow (CPU/OpticalFlow.cpp:147-204, declared in CPU/OpticalFlow.hpp:72-76), byte for byte,
+ * on the device.  The reference computes them with OpenCV 3.2 on the host; here they are restated kernels:
+ *   grey disparity  visualizeFlowAsGreyDisparity (:147-158): flow.x through normalize(0, 255, NORM_MINMAX) and convertTo(CV_8U);
+ *   colour wheel    visualizeFlowColorWheel (:185-204): hue = flow direction, value = magnitude / (max(cols, rows) / 20), HSV2BGR;
+ *   vector field    visualizeFlowAsVectorField (:160-183): a copy of the image with an anti-aliased black arrow line (LineAA) from
+ *                   every grid point 12 <= x < cols - 12, 12 <= y < rows - 12, x, y multiples of 12, drawn in row-major order;
+ *   panel           the strip buildvisualizations (CPU/main.cpp:20-45) writes per direction: [GRAY2BGRA(grey) | BGR2BGRA(wheel) |
+ *                   vector field], BGRA, 3 * cols x rows.
+ * A flow with a non-finite component is PF_ERR_ARG (the reference's result there depends on OpenCV's SIMD internals and on undefined
+ * float -> uchar conversions); a zero vector is finite (hue byte 0, the reference's x86-64 result for its 0 / 0 direction). */
+int pf_vis_grey_disparity(pf_ctx* ctx, const float* flow, size_t flow_step, int cols, int rows, uint8_t* out, size_t out_step);        /* CV_8UC1 */
+int pf_vis_color_wheel(pf_ctx* ctx, const float* flow, size_t flow_step, int cols, int rows, uint8_t* out_bgr, size_t out_step);       /* CV_8UC3 */
+int pf_vis_vector_field(pf_ctx* ctx, const float* flow, size_t flow_step, const uint8_t* image_bgra, size_t image_step,
+                        int cols, int rows, uint8_t* out_bgra, size_t out_step);                                                  /* CV_8UC4 */
+int pf_vis_panel(pf_ctx* ctx, const float* flow, size_t flow_step, const uint8_t* image_bgra, size_t image_step,
+                 int cols, int rows, uint8_t* out_bgra /* 3*cols x rows */, size_t out_step);
+/* the same on device pointers of this context's device, all packed (d_out: 3 * cols * 4 bytes per row) */
+int pf_vis_panel_dev(pf_ctx* ctx, const float* d_flow, const uint8_t* d_image, int cols, int rows, uint8_t* d_out);
+/* The two panels (L->R over the step's L input, R->L over its R input: the arguments of the reference's commented-out
+ * buildvisualizations call, CPU/main.cpp:85) of the LAST pf_stitch_step on this context, from the flows and inputs still in HBM;
+ * either output may be NULL.  pf_stitch_step itself does no extra work for this.  PF_ERR_ARG if no step has run or a later call
+ * has reused those buffers (any solve: pf_flow*, pf_novel_view*, the throughput mode, a failed step). */
+int pf_stitch_visualize(pf_ctx* ctx, uint8_t* l2r_panel, uint8_t* r2l_panel, size_t step);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

@@ -13,6 +13,10 @@
 //     `__exp_fma` ifunc variant executes on every x86-64 with FMA3 (all current EPYC / Xeon): the contractions below
 //     are the ones in that function's machine code (z + Shift, both reduction steps, the polynomial, scale + scale*tmp).
 //
+//   * atanf / atan2f (the flow colour wheel, CPU/OpticalFlow.cpp:196; debug output, not the blend path): fdlibm's float
+//     algorithms (s_atanf.c, e_atan2f.c), plain fp32 in source order -- tests/cpp/flow_vis_ref.cpp holds them against the host
+//     atan2f (all 2^32 y at x = +-1, 2^30 random pairs, a grid of special cases; the x86-64 build has no FMA variant of them).
+//
 // tests/cpp/libm_exact_test.cpp holds both against the host libm: every one of the 2^32 float bit patterns for
 // tanhf, 2^31 doubles spread over the whole argument range (incl. the subnormal / overflow paths) for exp.
 // No libm function is called here; hipcc's fp32/fp64 +, *, /, fma are IEEE-754 correctly rounded, so the same source
@@ -122,6 +126,91 @@ PF_HD float tanhf_exact(float x) {
     }
   } else z = one - tiny;                   // |x| >= 22: 1 (inexact)
   return (int32_t)jx >= 0 ? z : -z;
+}
+
+// ---- atanf / atan2f (glibc 2.35 s_atanf.c, e_atan2f.c; fdlibm) ----
+// The colour wheel of visualizeFlowColorWheel (CPU/OpticalFlow.cpp:196).  The tables are selected with ternaries, not
+// indexed: a dynamically indexed local array would live in scratch memory on the device.
+PF_HD float atanf_exact(float x) {
+  const float one = 1.0f, huge = 1.0e30f;
+  const float aT0 = 3.3333334327e-01f, aT1 = -2.0000000298e-01f, aT2 = 1.4285714924e-01f, aT3 = -1.1111110449e-01f,
+              aT4 = 9.0908870101e-02f, aT5 = -7.6918758452e-02f, aT6 = 6.6610731184e-02f, aT7 = -5.8335702866e-02f,
+              aT8 = 4.9768779427e-02f, aT9 = -3.6531571299e-02f, aT10 = 1.6285819933e-02f;
+  float w, s1, s2, z;
+  int id;
+  const uint32_t hx = f2u(x);
+  const uint32_t ix = hx & 0x7fffffffu;
+  if (ix >= 0x4c000000u) {                 // |x| >= 2^25
+    if (ix > 0x7f800000u) return x + x;    // NaN
+    const float hi = 1.5707962513e+00f, lo = 7.5497894159e-08f;
+    return (int32_t)hx > 0 ? hi + lo : -hi - lo;
+  }
+  if (ix < 0x3ee00000u) {                  // |x| < 0.4375
+    if (ix < 0x31000000u) {                // |x| < 2^-29: x (inexact)
+      if (huge + x > one) return x;
+    }
+    id = -1;
+  } else {
+    x = u2f(ix);
+    if (ix < 0x3f980000u) {                // |x| < 1.1875
+      if (ix < 0x3f300000u) { id = 0; x = (2.0f * x - one) / (2.0f + x); }   // 7/16 <= |x| < 11/16
+      else { id = 1; x = (x - one) / (x + one); }                            // 11/16 <= |x| < 19/16
+    } else {
+      if (ix < 0x401c0000u) { id = 2; x = (x - 1.5f) / (one + 1.5f * x); }   // |x| < 2.4375
+      else { id = 3; x = -1.0f / x; }                                        // 2.4375 <= |x| < 2^25
+    }
+  }
+  z = x * x;
+  w = z * z;
+  s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+  s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+  if (id < 0) return x - x * (s1 + s2);
+  const float ahi = id == 0 ? 4.6364760399e-01f : id == 1 ? 7.8539812565e-01f : id == 2 ? 9.8279368877e-01f : 1.5707962513e+00f;
+  const float alo = id == 0 ? 5.0121582440e-09f : id == 1 ? 3.7748947079e-08f : id == 2 ? 3.4473217170e-08f : 7.5497894159e-08f;
+  z = ahi - ((x * (s1 + s2) - alo) - x);
+  return (int32_t)hx < 0 ? -z : z;
+}
+
+PF_HD float atan2f_exact(float y, float x) {
+  const float tiny = 1.0e-30f, pi_o_4 = 7.8539818525e-01f, pi_o_2 = 1.5707963705e+00f, pi = 3.1415927410e+00f, pi_lo = -8.7422776573e-08f;
+  float z;
+  const int32_t hx = (int32_t)f2u(x), hy = (int32_t)f2u(y);
+  const int32_t ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+  if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;   // NaN
+  if (hx == 0x3f800000) return atanf_exact(y);            // x = 1.0
+  const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);      // 2 * sign(x) + sign(y)
+  if (iy == 0) {                                          // y = 0
+    if (m <= 1) return y;
+    return m == 2 ? pi + tiny : -pi - tiny;
+  }
+  if (ix == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;   // x = 0
+  if (ix == 0x7f800000) {                                 // x = +-inf
+    if (iy == 0x7f800000) {
+      switch (m) {
+        case 0: return pi_o_4 + tiny;
+        case 1: return -pi_o_4 - tiny;
+        case 2: return 3.0f * pi_o_4 + tiny;
+        default: return -3.0f * pi_o_4 - tiny;
+      }
+    }
+    switch (m) {
+      case 0: return 0.0f;
+      case 1: return -0.0f;
+      case 2: return pi + tiny;
+      default: return -pi - tiny;
+    }
+  }
+  if (iy == 0x7f800000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;   // y = +-inf
+  const int32_t k = (iy - ix) >> 23;
+  if (k > 60) z = pi_o_2 + 0.5f * pi_lo;                  // |y/x| > 2^60
+  else if (hx < 0 && k < -60) z = 0.0f;                   // |y|/x < -2^60
+  else z = atanf_exact(fabsf(y / x));
+  switch (m) {
+    case 0: return z;
+    case 1: return u2f(f2u(z) ^ 0x80000000u);
+    case 2: return pi - (z - pi_lo);
+    default: return (z - pi_lo) - pi;
+  }
 }
 
 // ---- exp, fp64 (glibc 2.35 e_exp.c, N = 128, as executed by the x86-64 FMA variant) ----

@@ -36,6 +36,9 @@ struct pf_ctx {
   int lanes_running = 1;  // throughput mode: lanes (this one included) solving batches side by side on the device right now
   long fuse_ups_px = 0;   // levels up to this many pixels get their incoming flow upsampled inside their first Gaussian (0 = never)
   int chain_cols = 0, chain_rows = 0;   // size of the stitch-chain result resident in "ch_final"
+  // pf_stitch_visualize: the last pf_stitch_step's inputs ("ch_l", "ch_r") and flows ("nv_flow_l2r", "nv_flow_r2l") are still in HBM.
+  // Set by a successful pf_stitch_step, cleared by every call that may reuse those buffers (any solve, the throughput mode, a step).
+  bool vis_step_valid = false;
   long long last_swept_steps = 0;       // wavefront steps of one direction of the last solve (both sweeps, all levels, gated windows)
   // pf_stitch_prefetch: `hint` = the image announced for the NEXT step (one-shot: the next pf_stitch_step latches and clears it, uploads
   // it into "ch_l_next" while its own kernels run, and records it as `ready`); `ready` = what sits in "ch_l_next" for the step after

@@ -88,6 +88,7 @@ int novel_view_group(pf_ctx* lane, int first, int count, const uint8_t* const* d
 int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
                             const float* const* d_blend, uint8_t* const* d_out, float* const* d_l2r, float* const* d_r2l, int in_flight) {
   if (int e = use(c)) return e;
+  c->vis_step_valid = false;   // lane 0 solves in this context's arena
   if (n_pairs < 0 || !d_l || !d_r || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
   if (in_flight < 1) in_flight = 1;
   if (in_flight > 2 * kMaxBatch) in_flight = 2 * kMaxBatch;

@@ -209,6 +209,7 @@ int wait_gate_boxes(pf_ctx* c, hipStream_t st, int epoch, int nlevels, std::vect
 // gated and keep their flow).
 int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* const* d_img1, int cols, int rows, int pad, int max_pct, int ndirs, const int* hints,
             float* const* d_out, float** used_out = nullptr /* [nb * 2]: where each flow went (a NULL d_out entry of a batch = a plane inside the pair's slab) */) {
+  c->vis_step_valid = false;   // the solve may reuse (or regrow) the flow buffers pf_stitch_visualize reads
   if (int e = check_dims(c, cols, rows, pad)) return e;
   if (max_pct < 0 || max_pct > 100) return fail(c, PF_ERR_ARG, "max_percentage %d out of range", max_pct);
   if (nb < 1 || nb > kMaxBatch) return fail(c, PF_ERR_ARG, "batch of %d pairs (1..%d)", nb, kMaxBatch);

@@ -162,6 +162,7 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
   if (step < size_t(cols) * 4 || (out && ostep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
   check_hw_queues(c, 5, "pf_stitch_step");   // front end, two flow directions, blend ramp, prefetch copy
+  c->vis_step_valid = false;
   const size_t n = size_t(cols) * rows;
   uint8_t* dl = (uint8_t*)ensure(c, "ch_l", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "ch_r", n * 4); uint8_t* dfin = (uint8_t*)ensure(c, "ch_final", n * 4);
   uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
@@ -219,7 +220,9 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
   c->chain_cols = cols; c->chain_rows = rows;
-  return check_sweeps(c);
+  if (int e = check_sweeps(c)) return e;
+  c->vis_step_valid = true;
+  return 0;
 }
 
 // Announce the left image of the pf_stitch_step call AFTER the coming one: the coming step uploads it while its own kernels run

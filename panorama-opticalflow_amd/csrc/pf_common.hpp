@@ -194,4 +194,21 @@ void launch_checksum64(hipStream_t st, const void* p, size_t bytes, unsigned lon
 void launch_count_diff_u32(hipStream_t st, const uint32_t* a, const uint32_t* b, size_t n, int* count /* zeroed by the caller */);
 void launch_collect_status(hipStream_t st, const int* ctrl, int nwords, int* status_mapped, int bit, Batch bt = Batch());
 
+// ---- flow visualisers (kernels_vis.hip; CPU/OpticalFlow.cpp:147-204, CPU/main.cpp:20-45).  Flows / images packed. ----
+struct VisParams {   // written on the device: the grey disparity's float scale / shift, and the non-finite flow components seen
+  float scale, shift;
+  int nonfinite;     // zeroed by the caller
+  int pad_;
+};
+void vis_grid(int cols, int rows, int* nax, int* nay);   // arrows per axis of the 12-px grid
+size_t vis_part_bytes();
+size_t vis_arrow_bytes(int cols, int rows);
+void launch_vis_reduce(hipStream_t st, const float* flow, int cols, int rows, float* part, VisParams* par);   // min / max -> scale, shift, count
+void launch_vis_arrows(hipStream_t st, const float* flow, int cols, int rows, void* arrows);                   // LineAA set-up per arrow
+void launch_vis_grey(hipStream_t st, const float* flow, int cols, int rows, const VisParams* par, uint8_t* out);   // 16-byte aligned buffers
+void launch_vis_wheel(hipStream_t st, const float* flow, int cols, int rows, VisParams* par, uint8_t* out);       // counts non-finite too
+void launch_vis_field(hipStream_t st, const uint8_t* img, int cols, int rows, const void* arrows, uint8_t* out);
+void launch_vis_panel(hipStream_t st, const float* flow, const uint8_t* img, int cols, int rows, const VisParams* par, const void* arrows,
+                      uint8_t* out /* 3 cols x rows BGRA */);
+
 }  // namespace pf

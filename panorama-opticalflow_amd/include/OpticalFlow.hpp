@@ -82,6 +82,30 @@ class NovelViewGeneratorAsymmetricFlow : public NovelViewGenerator {
   void setBlend(const Mat& blend) override { Blend = blend.clone(); }
 };
 
+// CPU/OpticalFlow.hpp:72-76 (CPU/OpticalFlow.cpp:147-204): the flow visualisers, on the device (pf_vis_*).  A flow with non-finite
+// components throws, as every other error of the library does.
+inline Mat visualizeFlowAsGreyDisparity(const Mat& flow) {
+  if (flow.type() != CV_32FC2) throw VrCamException("visualizeFlowAsGreyDisparity: flow must be CV_32FC2");
+  Mat out(flow.rows, flow.cols, CV_8UC1);
+  pano::check(pf_vis_grey_disparity(pano::context(), flow.ptr<float>(), flow.step, flow.cols, flow.rows, out.data, out.step));
+  return out;
+}
+
+inline Mat visualizeFlowAsVectorField(const Mat& flow, const Mat& image) {
+  if (flow.type() != CV_32FC2 || image.type() != CV_8UC4) throw VrCamException("visualizeFlowAsVectorField: expects a CV_32FC2 flow and a CV_8UC4 image");
+  if (flow.rows != image.rows || flow.cols != image.cols) throw VrCamException("visualizeFlowAsVectorField: flow and image differ in size");
+  Mat out(image.rows, image.cols, CV_8UC4);
+  pano::check(pf_vis_vector_field(pano::context(), flow.ptr<float>(), flow.step, image.data, image.step, image.cols, image.rows, out.data, out.step));
+  return out;
+}
+
+inline Mat visualizeFlowColorWheel(const Mat& flow) {
+  if (flow.type() != CV_32FC2) throw VrCamException("visualizeFlowColorWheel: flow must be CV_32FC2");
+  Mat out(flow.rows, flow.cols, CV_8UC3);
+  pano::check(pf_vis_color_wheel(pano::context(), flow.ptr<float>(), flow.step, flow.cols, flow.rows, out.data, out.step));
+  return out;
+}
+
 }  // namespace optical_flow
 
 #endif /* OpticalFlow_hpp */

@@ -52,6 +52,14 @@ struct Vec4b {
   const unsigned char& operator[](int i) const { return val[i]; }
 };
 
+struct Vec3b {
+  unsigned char val[3] = {0, 0, 0};
+  Vec3b() {}
+  Vec3b(unsigned char a, unsigned char b, unsigned char c) { val[0] = a; val[1] = b; val[2] = c; }
+  unsigned char& operator[](int i) { return val[i]; }
+  const unsigned char& operator[](int i) const { return val[i]; }
+};
+
 class Mat {
  public:
   int rows = 0, cols = 0;
@@ -95,6 +103,34 @@ class Mat {
 };
 
 }  // namespace panocv
+
+namespace util {
+
+// CPU/util.cpp:36-46 (hconcat of every image onto the first): images of one row count and one of the 8-bit types the reference
+// stacks (CV_8UC1, CV_8UC3, CV_8UC4), side by side
+static inline panocv::Mat stackHorizontal(const std::vector<panocv::Mat>& images) {
+  if (images.empty()) throw VrCamException("stackHorizontal: no images");
+  if (images.size() == 1) return images[0];
+  const int type = images[0].type(), rows = images[0].rows;
+  if (type != panocv::CV_8UC1 && type != panocv::CV_8UC3 && type != panocv::CV_8UC4) throw VrCamException("stackHorizontal: unsupported Mat type");
+  int cols = 0;
+  for (const panocv::Mat& m : images) {
+    if (m.type() != type || m.rows != rows) throw VrCamException("stackHorizontal: images differ in type or row count");
+    cols += m.cols;
+  }
+  panocv::Mat out(rows, cols, type);
+  const size_t es = out.elemSize();
+  for (int y = 0; y < rows; ++y) {
+    size_t o = 0;
+    for (const panocv::Mat& m : images) {
+      std::memcpy(out.data + size_t(y) * out.step + o, m.data + size_t(y) * m.step, size_t(m.cols) * es);
+      o += size_t(m.cols) * es;
+    }
+  }
+  return out;
+}
+
+}  // namespace util
 
 namespace pano {
 

@@ -98,6 +98,7 @@ EXPORTS = [
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
     "pf_stage_diffusion", "pf_stage_upsample_cubic", "pf_stage_final", "pf_stage_adjust_initial_flow", "pf_stage_level",
     "pf_stage_blend_smooth",
+    "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -301,7 +302,49 @@ class Context:
             out = np.empty((rows, cols, 4), np.uint8)
         self._chk(self.l.pf_stitch_step(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
                                         None if out is None else _p(out), C.c_size_t(cols * 4)))
+        self._step_shape = (rows, cols)
         return out
+
+    # ---- flow visualisation (CPU/OpticalFlow.cpp:147-204, the panel of CPU/main.cpp:20-45) ----
+    def vis_grey_disparity(self, flow):
+        """visualizeFlowAsGreyDisparity: (rows, cols) uint8"""
+        f = _f32(flow); rows, cols, _ = f.shape
+        out = np.empty((rows, cols), np.uint8)
+        self._chk(self.l.pf_vis_grey_disparity(self.h, _p(f), C.c_size_t(cols * 8), cols, rows, _p(out), C.c_size_t(cols)))
+        return out
+
+    def vis_color_wheel(self, flow):
+        """visualizeFlowColorWheel: (rows, cols, 3) uint8 BGR"""
+        f = _f32(flow); rows, cols, _ = f.shape
+        out = np.empty((rows, cols, 3), np.uint8)
+        self._chk(self.l.pf_vis_color_wheel(self.h, _p(f), C.c_size_t(cols * 8), cols, rows, _p(out), C.c_size_t(cols * 3)))
+        return out
+
+    def vis_vector_field(self, flow, image):
+        """visualizeFlowAsVectorField: (rows, cols, 4) uint8 BGRA, the image with the flow's arrows"""
+        f = _f32(flow); im = _u8(image); rows, cols, _ = f.shape
+        out = np.empty((rows, cols, 4), np.uint8)
+        self._chk(self.l.pf_vis_vector_field(self.h, _p(f), C.c_size_t(cols * 8), _p(im), C.c_size_t(cols * 4), cols, rows, _p(out),
+                                             C.c_size_t(cols * 4)))
+        return out
+
+    def vis_panel(self, flow, image):
+        """buildvisualizations' strip of one direction: (rows, 3 * cols, 4) uint8 BGRA"""
+        f = _f32(flow); im = _u8(image); rows, cols, _ = f.shape
+        out = np.empty((rows, 3 * cols, 4), np.uint8)
+        self._chk(self.l.pf_vis_panel(self.h, _p(f), C.c_size_t(cols * 8), _p(im), C.c_size_t(cols * 4), cols, rows, _p(out), C.c_size_t(cols * 12)))
+        return out
+
+    def vis_panel_dev(self, d_flow, d_image, cols, rows, d_out):
+        self._chk(self.l.pf_vis_panel_dev(self.h, C.c_void_p(d_flow), C.c_void_p(d_image), cols, rows, C.c_void_p(d_out)))
+
+    def stitch_visualize(self, shape=None):
+        """the (L->R, R->L) panels of the last stitch_step from what it left in HBM; shape = (rows, cols) of that step (default: the last
+        stitch_step made through this object)"""
+        rows, cols = shape if shape is not None else self._step_shape
+        a = np.empty((rows, 3 * cols, 4), np.uint8); b = np.empty_like(a)
+        self._chk(self.l.pf_stitch_visualize(self.h, _p(a), _p(b), C.c_size_t(cols * 12)))
+        return a, b
 
     # ---- device-resident entry points (raw device pointers as ints) ----
     def dev_alloc(self, nbytes):

@@ -2,8 +2,14 @@
 // 5-step chain (R_i = FinalResult_{i-1}, main.cpp:64-65), same timing lines; all pixel work on the MI355X.
 //   pano_stitch -test_dir <dir> -top_img top.tif -flow_alg pixflow_low|pixflow_search_20 [-steps 5] [-fused 0|1]
 //   pano_stitch -inputs 4 -test_dir <dir> -flow_alg ...      the one-pass 4-photo variant (CPU_4Input/main.cpp:45-120)
+//   -visualize 1: also writes <dir>/disparity/LtoR_<alg>_step<i>.png and RtoL_<alg>_step<i>.png for every step i, the panels of the
+//   reference's buildvisualizations (main.cpp:20-45, its call site :85 is commented out there).  Deviation: the reference names them
+//   LtoR_<alg>.png / RtoL_<alg>.png, so each step would overwrite the previous one; the step number keeps them all.
 // reads <dir>/<top_img> and <dir>/1.tif .. 5.tif (8-bit RGB/RGBA TIFF or PNG), writes ProcessResult{i}.png and
 // FinalResult.png (main.cpp:97-100).
+#include <sys/stat.h>
+
+#include <cerrno>
 #include <cstdlib>
 #include <iostream>
 #include <map>
@@ -32,6 +38,40 @@ static std::map<std::string, std::string> parseFlags(int argc, char** argv) {   
   return f;
 }
 
+
+// cvtColor(GRAY2BGRA / BGR2BGRA) of the 8-bit images buildvisualizations converts (alpha 255)
+static Mat toBGRA(const Mat& m) {
+  Mat out(m.rows, m.cols, CV_8UC4);
+  for (int y = 0; y < m.rows; ++y)
+    for (int x = 0; x < m.cols; ++x) {
+      const unsigned char* p = m.ptr<unsigned char>(y) + size_t(x) * m.elemSize();
+      out.at<Vec4b>(y, x) = m.type() == CV_8UC1 ? Vec4b(p[0], p[0], p[0], 255) : Vec4b(p[0], p[1], p[2], 255);
+    }
+  return out;
+}
+
+// CPU/main.cpp:20-45, one file per direction and step (see the usage note at the top)
+static void buildvisualizations(const Mat flowLtoR, const Mat flowRtoL, const Mat ImageL, const Mat ImageR, const std::string& dir,
+                                const std::string& alg, int step) {
+  Mat flowVisLtoR = visualizeFlowAsGreyDisparity(flowLtoR);
+  Mat flowVisRtoL = visualizeFlowAsGreyDisparity(flowRtoL);
+  Mat flowVisLtoRColorWheel = visualizeFlowColorWheel(flowLtoR);
+  Mat flowVisRtoLColorWheel = visualizeFlowColorWheel(flowRtoL);
+  Mat flowVisLtoRColorWithLines = visualizeFlowAsVectorField(flowLtoR, ImageL);
+  Mat flowVisRtoLColorWithLines = visualizeFlowAsVectorField(flowRtoL, ImageR);
+  Mat horizontalVisLtoR = stackHorizontal(std::vector<Mat>({toBGRA(flowVisLtoR), toBGRA(flowVisLtoRColorWheel), flowVisLtoRColorWithLines}));
+  Mat horizontalVisRtoL = stackHorizontal(std::vector<Mat>({toBGRA(flowVisRtoL), toBGRA(flowVisRtoLColorWheel), flowVisRtoLColorWithLines}));
+  pano_io::imwriteExceptionOnFail(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisLtoR);
+  pano_io::imwriteExceptionOnFail(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisRtoL);
+}
+
+// the same panels of a fused step, from the flows and inputs pf_stitch_step left in HBM
+static void stitchVisualizations(int cols, int rows, const std::string& dir, const std::string& alg, int step) {
+  Mat l2r(rows, 3 * cols, CV_8UC4), r2l(rows, 3 * cols, CV_8UC4);
+  pano::check(pf_stitch_visualize(pano::context(), l2r.data, r2l.data, l2r.step));
+  pano_io::imwriteExceptionOnFail(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", l2r);
+  pano_io::imwriteExceptionOnFail(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", r2l);
+}
 
 // CPU_4Input/main.cpp:54-113: crop every photo to the columns where its centre row is opaque, L = 1 + 3, R = 2 + 4
 // (saturating), then ONE stitch step.  The crop/sum is the driver's own image preparation (byte copies on the host,
@@ -66,6 +106,7 @@ int main(int argc, char** argv) {
     const std::string FLAGS_test_dir = flags["test_dir"], FLAGS_top_img = flags["top_img"], FLAGS_flow_alg = flags["flow_alg"];
     const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
     const bool fused = !flags.count("fused") || atoi(flags["fused"].c_str()) != 0;   // -fused 0: the reference's object-by-object sequence
+    const bool visualize = flags.count("visualize") && atoi(flags["visualize"].c_str()) != 0;
     if (flags.count("inputs") && atoi(flags["inputs"].c_str()) == 4) {
       requireArg(FLAGS_test_dir, "test_dir");
       requireArg(FLAGS_flow_alg, "flow_alg");
@@ -78,6 +119,8 @@ int main(int argc, char** argv) {
 
     Mat colorImageL, colorImageR, FinalResult;
     Mat colorImageT = pano_io::imreadExceptionOnFail(FLAGS_test_dir + "/" + FLAGS_top_img);
+    if (visualize && mkdir((FLAGS_test_dir + "/disparity").c_str(), 0777) != 0 && errno != EEXIST)
+      throw VrCamException("cannot create " + FLAGS_test_dir + "/disparity");
     for (int i = 1; i <= nsteps; i++) {
       double StepStart = getCurrTimeSec();
       if (i == 1) colorImageR = colorImageT; else colorImageR = FinalResult;
@@ -86,6 +129,7 @@ int main(int argc, char** argv) {
       if (fused) {
         // same kernels, same results; the step's intermediates and the chained R stay in HBM
         FinalResult = stitchStep(colorImageL, i == 1 ? &colorImageR : nullptr, FLAGS_flow_alg);
+        if (visualize) stitchVisualizations(colorImageL.cols, colorImageL.rows, FLAGS_test_dir, FLAGS_flow_alg, i);
       } else {
       Stitchtools Stools;
       Stools.prepare(colorImageL, colorImageR);
@@ -95,6 +139,8 @@ int main(int argc, char** argv) {
 
       NovelViewGenerator* novelViewGen = new NovelViewGeneratorAsymmetricFlow(FLAGS_flow_alg);
       novelViewGen->prepare(overlappedL, overlappedR);
+
+      if (visualize) buildvisualizations(novelViewGen->getFlowLtoR(), novelViewGen->getFlowRtoL(), colorImageL, colorImageR, FLAGS_test_dir, FLAGS_flow_alg, i);
       novelViewGen->setBlend(blend);
       Mat novelViewMerged = Mat();
       novelViewGen->generateNovelView(novelViewMerged);
