@@ -146,10 +146,12 @@ int pf_novel_view(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int
                   int max_percentage, const float* blend, size_t blend_step_bytes, uint8_t* out_bgra, size_t out_step_bytes,
                   float* flow_l2r, float* flow_r2l, size_t flow_step_bytes);
 
-/* Size limit of the three stitch entry points that build the blend ramp (pf_stitch_prepare, pf_stitch_generate_blend, pf_stitch_step):
- * the tile smoothing of GenerateBlend (CPU/StitchTool.cpp:130-143) keeps one tile's window, (step + k - 1)^2 floats + (step + k - 1) x step
- * doubles with step = min(cols, rows) / 200 and k = rows / 130, in the 160 KB of LDS of a CU: canvases up to ~15,000 rows (a 30000x15000
- * equirectangular panorama) -- beyond that they return PF_ERR_ARG.  The solver and blend entry points have no such limit. */
+/* Size limit of the stitch entry points that build the blend ramp (pf_stitch_prepare, pf_stitch_generate_blend, pf_stitch_step,
+ * pf_stitch_step_batch*): the tile smoothing of GenerateBlend (CPU/StitchTool.cpp:130-143) keeps one tile's window, (step + k - 1)^2 floats
+ * + (step + k - 1) x step doubles with step = min(cols, rows) / 200 and k = rows / 130, in the 160 KiB (163,840 B) of LDS of a CU.  For
+ * canvases at least as wide as they are tall that allows up to 12,000 rows (24000x12000 is accepted, 24500x12250 is not; a 30000x15000
+ * equirectangular panorama would need ~250 KiB); narrower canvases can have more rows.  Beyond the limit they return PF_ERR_ARG.  The
+ * solver and blend entry points have no such limit. */
 /* Stitchtools::prepare, CPU/StitchTool.cpp:7-36 (MatchImages :38-50, GenerateBlend :98-146,
  * countblend :148-191).  merged_dis may be NULL.  All planes cols x rows, packed rows of `step`. */
 int pf_stitch_prepare(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int cols, int rows, size_t step_bytes,
@@ -189,6 +191,24 @@ int pf_stitch_step(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, in
  * a partial overwrite that misses those rows is not detected and the stale device copy would be used.  NULL cancels.  With the
  * contract kept it is purely an optimisation: results are identical. */
 int pf_stitch_prefetch(pf_ctx* ctx, const uint8_t* next_l_bgra, int cols, int rows, size_t step_bytes);
+
+/* Batched stitch step: n_frames independent canvases of one size, each one pf_stitch_step of its own chain, `in_flight` (1..32,
+ * clamped like pf_novel_view_batch_dev; pf_config::batch_pairs applies) of them on this GPU at a time.  Groups of frames share every
+ * launch (match, blend ramp with ONE tile-smoothing launch per group, solve, blend, gather) on one or more lanes of streams.  Frame k
+ * gets exactly the bytes pf_stitch_step would give for frame k's own sequence of calls.  n_frames == 0 does nothing; a negative count,
+ * NULL arrays or a NULL l entry are PF_ERR_ARG, as is anything pf_stitch_step refuses (checked before any work).  Synchronous on return.
+ * Host form: r_bgra == NULL, or r_bgra[k] == NULL, chains frame k on its own composite of the previous pf_stitch_step_batch call on this
+ * context (kept in HBM, one slot per frame index; that call must have had the same cols x rows and more than k frames, else
+ * PF_ERR_ARG).  out_bgra == NULL, or out_bgra[k] == NULL, skips frame k's download.  The slots are separate from pf_stitch_step's
+ * chained result and pf_stitch_prefetch's records: interleaving the two APIs changes neither one's results.
+ * HBM: ~33 B/px of StitchTool planes + 16 B/px of flows + one solver slab per frame in flight, and 12 B/px per frame slot of the host
+ * form (left, right, composite).  Needs GPU_MAX_HW_QUEUES >= 3 x lanes + 2, like pf_novel_view_batch_dev. */
+int pf_stitch_step_batch(pf_ctx* ctx, int n_frames, const uint8_t* const* l_bgra, const uint8_t* const* r_bgra, int cols, int rows,
+                         size_t step_bytes, int max_percentage, uint8_t* const* out_bgra, size_t out_step_bytes, int in_flight);
+/* Device form: packed device buffers; no chain state -- every d_r[k] must be non-NULL (the caller chains by ping-ponging its
+ * buffers).  A d_out[k] that overlaps any input of the call or another d_out is PF_ERR_ARG; repeated input pointers are allowed. */
+int pf_stitch_step_batch_dev(pf_ctx* ctx, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows,
+                             int max_percentage, uint8_t* const* d_out, int in_flight);
 
 /* ---- device-resident entry points (packed buffers already in this context's HBM) -----------
  * Same semantics as above; used by bench.py (inputs resident when the clock starts) and by the

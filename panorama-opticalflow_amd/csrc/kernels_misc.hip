@@ -254,8 +254,8 @@ void launch_blend(hipStream_t st, const uint8_t* L, const uint8_t* R, const floa
 // ------------------------------------------------------------------------------------------------
 // K12 MatchImages + overlap masking (StitchTool.cpp:17-33, :38-50)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_match_images(const uchar4* __restrict__ L, const uchar4* __restrict__ R, int n, uint8_t* __restrict__ map,
-                                                      uchar4* __restrict__ ovL, uchar4* __restrict__ ovR) {
+__device__ __forceinline__ void d_match_px(const uchar4* __restrict__ L, const uchar4* __restrict__ R, int n, uint8_t* __restrict__ map,
+                                           uchar4* __restrict__ ovL, uchar4* __restrict__ ovR) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uchar4 l = L[i], r = R[i];
@@ -264,6 +264,10 @@ __global__ __launch_bounds__(256) void k_match_images(const uchar4* __restrict__
   const bool ov = m > 140;
   ovL[i] = ov ? l : make_uchar4(0, 0, 0, 0);
   ovR[i] = ov ? r : make_uchar4(0, 0, 0, 0);
+}
+__global__ __launch_bounds__(256) void k_match_images(const uchar4* __restrict__ L, const uchar4* __restrict__ R, int n, uint8_t* __restrict__ map,
+                                                      uchar4* __restrict__ ovL, uchar4* __restrict__ ovR) {
+  d_match_px(L, R, n, map, ovL, ovR);
 }
 void launch_match_images(hipStream_t st, const uint8_t* L, const uint8_t* R, int cols, int rows, uint8_t* map, uint8_t* ovL, uint8_t* ovR) {
   const int n = cols * rows;
@@ -275,8 +279,8 @@ void launch_match_images(hipStream_t st, const uint8_t* L, const uint8_t* R, int
 // K13 GenerateBlend's per-pixel part + countblend (StitchTool.cpp:98-128, :148-191).  The map extended
 // by cols/5 wrapped columns each side (:102-111) is virtual.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_countblend(const uint8_t* __restrict__ map, int cols, int rows, int length, int step, float* __restrict__ blend,
-                                                    float* __restrict__ mergedDis) {
+__device__ __forceinline__ void d_countblend_px(const uint8_t* __restrict__ map, int cols, int rows, int length, int step, float* __restrict__ blend,
+                                                float* __restrict__ mergedDis) {
   const int x0 = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x0 >= cols) return;
   const int MW = cols + 2 * length, MH = rows;
@@ -311,11 +315,17 @@ __global__ __launch_bounds__(256) void k_countblend(const uint8_t* __restrict__ 
   blend[size_t(y) * cols + x0] = b;
   mergedDis[size_t(y) * cols + x0] = md;
 }
+__global__ __launch_bounds__(256) void k_countblend(const uint8_t* __restrict__ map, int cols, int rows, int length, int step, float* __restrict__ blend,
+                                                    float* __restrict__ mergedDis) {
+  d_countblend_px(map, cols, rows, length, step, blend, mergedDis);
+}
+int countblend_step(int cols, int rows) {
+  const int step = cols <= rows ? cols / 200 : rows / 200;
+  return step < 1 ? 1 : step;   // reference never terminates for step==0 (inputs < 200 px); defined as 1
+}
 void launch_countblend(hipStream_t st, const uint8_t* map, int cols, int rows, float* blend, float* mergedDis) {
-  int step = cols <= rows ? cols / 200 : rows / 200;
-  if (step < 1) step = 1;  // reference never terminates for step==0 (inputs < 200 px); defined as 1
   dim3 grid((cols + 255) / 256, rows);
-  hipLaunchKernelGGL(k_countblend, grid, dim3(256), 0, st, map, cols, rows, cols / 5, step, blend, mergedDis);
+  hipLaunchKernelGGL(k_countblend, grid, dim3(256), 0, st, map, cols, rows, cols / 5, countblend_step(cols, rows), blend, mergedDis);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -325,7 +335,7 @@ void launch_countblend(hipStream_t st, const uint8_t* map, int cols, int rows, f
 // pass) and each column (column pass) -- exactly the O(1)/pixel schedule one wants anyway.
 // ------------------------------------------------------------------------------------------------
 // any kernel width, one lane per row straight from memory (only used beyond kBoxKMax)
-__global__ __launch_bounds__(64) void k_box_rows_wide(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
+__device__ __forceinline__ void d_box_rows_wide(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
   const int y = blockIdx.x * blockDim.x + threadIdx.x;
   if (y >= rows) return;
   const int a = k / 2;
@@ -338,14 +348,16 @@ __global__ __launch_bounds__(64) void k_box_rows_wide(const float* __restrict__ 
     rs[size_t(y) * cols + x] = s;
   }
 }
+__global__ __launch_bounds__(64) void k_box_rows_wide(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
+  d_box_rows_wide(src, rs, cols, rows, k);
+}
 // Row pass.  A block owns 64 rows and walks them in chunks of 64 columns: the chunk (+ the k-1 taps beside it, reflected) is staged
 // in LDS with coalesced loads, lane y then advances ITS row's sliding sum through the chunk in the reference's order -- the
 // dependent chain is one fp64 add per pixel, everything else comes from LDS -- and the 64 x 64 sums leave through LDS as coalesced
 // 512-byte rows.  (Before: every lane read its own row straight from HBM, 64 cache lines per load: ~150 GB/s.)
 constexpr int kBoxR = 64, kBoxC = 64, kBoxKMax = 32;   // 58 KB of LDS (24.8 in + 33.3 out)
-__global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
-  __shared__ float tin[kBoxR][kBoxC + kBoxKMax + 1];   // odd row stride: the 64 lanes (rows) of the walking wave hit different banks
-  __shared__ double tout[kBoxR][kBoxC + 1];
+__device__ __forceinline__ void d_box_rows(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k,
+                                           float (&tin)[kBoxR][kBoxC + kBoxKMax + 1], double (&tout)[kBoxR][kBoxC + 1]) {
   const int y0 = blockIdx.x * kBoxR, tid = threadIdx.x;
   const int a = k / 2;
   const int wIn = kBoxC + k;   // columns c0 - a - 1 .. c0 + 63 - a - 1 + k: the subtracted tap of the chunk's first pixel .. the added tap of its last
@@ -392,9 +404,14 @@ __global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ src,
     // the next chunk's staging writes tin only (read by the walking wave before the barrier above); tout is rewritten after the next barrier
   }
 }
+__global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
+  __shared__ float tin[kBoxR][kBoxC + kBoxKMax + 1];   // odd row stride: the 64 lanes (rows) of the walking wave hit different banks
+  __shared__ double tout[kBoxR][kBoxC + 1];
+  d_box_rows(src, rs, cols, rows, k, tin, tout);
+}
 // Column pass: lanes are adjacent columns (coalesced already); the two taps of the next 8 rows are loaded before the 8 dependent
 // updates, so that a wave has 16 loads in flight instead of one round trip per row.
-__global__ __launch_bounds__(64) void k_box_cols(const double* __restrict__ rs, float* __restrict__ dst, int cols, int rows, int k) {
+__device__ __forceinline__ void d_box_cols(const double* __restrict__ rs, float* __restrict__ dst, int cols, int rows, int k) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= cols) return;
   const int a = k / 2;
@@ -419,6 +436,9 @@ __global__ __launch_bounds__(64) void k_box_cols(const double* __restrict__ rs, 
       }
     }
   }
+}
+__global__ __launch_bounds__(64) void k_box_cols(const double* __restrict__ rs, float* __restrict__ dst, int cols, int rows, int k) {
+  d_box_cols(rs, dst, cols, rows, k);
 }
 void launch_box_blur(hipStream_t st, const float* src, float* dst, double* rowsum_tmp, int cols, int rows, int k) {
   if (k <= kBoxKMax) hipLaunchKernelGGL(k_box_rows, dim3((rows + kBoxR - 1) / kBoxR), dim3(256), 0, st, src, rowsum_tmp, cols, rows, k);
@@ -459,10 +479,47 @@ __device__ __forceinline__ bool d_grid_barrier(int* bar, int* err, int target, l
   __syncthreads();
   return ok != 0;
 }
+// one tile (x0, y0) of one canvas, by the whole block; sm / win = the dynamic LDS (row sums nr x step, window nr x nr)
+__device__ __forceinline__ void d_tile_blur_one(float* __restrict__ img, int cols, int rows, int step, int k, int x0, int y0, double* sm, float* win,
+                                                double scale) {
+  const int a = k / 2, nr = step + k - 1, tid = threadIdx.x;
+  __syncthreads();   // the previous tile's LDS is no longer read
+  for (int base = 0; base < nr * nr; base += 256 * 4) {
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * 256 + tid, j = idx / nr, i = idx - j * nr;
+      v[u] = idx < nr * nr ? img[size_t(d_reflect101(y0 - a + j, rows)) * cols + d_reflect101(x0 - a + i, cols)] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { const int idx = base + u * 256 + tid; if (idx < nr * nr) win[idx] = v[u]; }
+  }
+  __syncthreads();
+  for (int j = tid; j < nr; j += 256) {
+    const float* r = win + j * nr;
+    double s = 0;
+    for (int i = 0; i < k; ++i) s += (double)r[i];
+    sm[j * step] = s;
+    for (int x = 1; x < step; ++x) {
+      s += (double)r[x - 1 + k] - (double)r[x - 1];
+      sm[j * step + x] = s;
+    }
+  }
+  __syncthreads();
+  for (int x = tid; x < step; x += 256) {
+    double sum = 0;
+    for (int j = 0; j < k - 1; ++j) sum += sm[j * step + x];
+    for (int y = 0; y < step; ++y) {
+      const double s0 = sum + sm[(y + k - 1) * step + x];
+      img[size_t(y0 + y) * cols + x0 + x] = (float)(s0 * scale);
+      sum = s0 - sm[y * step + x];
+    }
+  }
+}
 __global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, const float* __restrict__ mergedDis, int cols, int rows, int step, int k,
                                                    int dskew, int ntx, int nty, TileBlurWork* __restrict__ wk, long long budget_ticks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-  const int a = k / 2, nr = step + k - 1;
+  const int nr = step + k - 1;
   double* sm = reinterpret_cast<double*>(smraw);                 // row sums: nr x step
   float* win = reinterpret_cast<float*>(sm + size_t(nr) * step);  // the tile's input window: nr x nr
   const int tid = threadIdx.x, nblk = gridDim.x;
@@ -485,39 +542,7 @@ __global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, cons
     for (int ty = ty_min + blockIdx.x; ty <= ty_max; ty += nblk) {
       const int tx = t - dskew * ty;
       if (tx < 0 || tx >= ntx || !active(tx, ty)) continue;   // block-uniform
-      const int x0 = tx * step, y0 = ty * step;
-      __syncthreads();   // the previous tile's LDS is no longer read
-      for (int base = 0; base < nr * nr; base += 256 * 4) {
-        float v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int idx = base + u * 256 + tid, j = idx / nr, i = idx - j * nr;
-          v[u] = idx < nr * nr ? img[size_t(d_reflect101(y0 - a + j, rows)) * cols + d_reflect101(x0 - a + i, cols)] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const int idx = base + u * 256 + tid; if (idx < nr * nr) win[idx] = v[u]; }
-      }
-      __syncthreads();
-      for (int j = tid; j < nr; j += 256) {
-        const float* r = win + j * nr;
-        double s = 0;
-        for (int i = 0; i < k; ++i) s += (double)r[i];
-        sm[j * step] = s;
-        for (int x = 1; x < step; ++x) {
-          s += (double)r[x - 1 + k] - (double)r[x - 1];
-          sm[j * step + x] = s;
-        }
-      }
-      __syncthreads();
-      for (int x = tid; x < step; x += 256) {
-        double sum = 0;
-        for (int j = 0; j < k - 1; ++j) sum += sm[j * step + x];
-        for (int y = 0; y < step; ++y) {
-          const double s0 = sum + sm[(y + k - 1) * step + x];
-          img[size_t(y0 + y) * cols + x0 + x] = (float)(s0 * scale);
-          sum = s0 - sm[y * step + x];
-        }
-      }
+      d_tile_blur_one(img, cols, rows, step, k, tx * step, ty * step, sm, win, scale);
     }
     ++phase;
     if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
@@ -567,8 +592,8 @@ void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int 
 // ------------------------------------------------------------------------------------------------
 // K15 Gather (StitchTool.cpp:52-96).  Out-of-range probes (latent OOB reads) are defined as "no match".
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gather(const uchar4* __restrict__ L, const uchar4* __restrict__ R, const uchar4* __restrict__ merged,
-                                                const uint8_t* __restrict__ map, int cols, int rows, uchar4* __restrict__ out) {
+__device__ __forceinline__ void d_gather_px(const uchar4* __restrict__ L, const uchar4* __restrict__ R, const uchar4* __restrict__ merged,
+                                            const uint8_t* __restrict__ map, int cols, int rows, uchar4* __restrict__ out) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= cols) return;
   auto M = [&](int yy, int xx) -> int {
@@ -595,10 +620,126 @@ __global__ __launch_bounds__(256) void k_gather(const uchar4* __restrict__ L, co
   }
   out[i] = o;
 }
+__global__ __launch_bounds__(256) void k_gather(const uchar4* __restrict__ L, const uchar4* __restrict__ R, const uchar4* __restrict__ merged,
+                                                const uint8_t* __restrict__ map, int cols, int rows, uchar4* __restrict__ out) {
+  d_gather_px(L, R, merged, map, cols, rows, out);
+}
 void launch_gather(hipStream_t st, const uint8_t* L, const uint8_t* R, const uint8_t* merged, const uint8_t* map, int cols, int rows, uint8_t* out) {
   dim3 grid((cols + 255) / 256, rows);
   hipLaunchKernelGGL(k_gather, grid, dim3(256), 0, st, reinterpret_cast<const uchar4*>(L), reinterpret_cast<const uchar4*>(R),
                      reinterpret_cast<const uchar4*>(merged), map, cols, rows, reinterpret_cast<uchar4*>(out));
+}
+
+// ------------------------------------------------------------------------------------------------
+// K12-K15 batched: n same-size canvases of independent stitch steps in one launch each (pf_stitch_step_batch*).  Every
+// per-frame buffer comes from a pointer table (StitchPtrs); blockIdx.z is the frame, and the arithmetic per pixel is the
+// single-canvas kernels' own (the same device functions).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_match_images_batch(StitchPtrs p, int n) {
+  const int z = blockIdx.z;
+  d_match_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), n, p.map[z], reinterpret_cast<uchar4*>(p.ovL[z]),
+             reinterpret_cast<uchar4*>(p.ovR[z]));
+}
+void launch_match_images_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
+  const int n = cols * rows;
+  hipLaunchKernelGGL(k_match_images_batch, dim3((n + 255) / 256, 1, nf), dim3(256), 0, st, p, n);
+}
+__global__ __launch_bounds__(256) void k_countblend_batch(StitchPtrs p, int cols, int rows, int length, int step) {
+  const int z = blockIdx.z;
+  d_countblend_px(p.map[z], cols, rows, length, step, p.blend[z], p.md[z]);
+}
+void launch_countblend_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
+  hipLaunchKernelGGL(k_countblend_batch, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows, cols / 5, countblend_step(cols, rows));
+}
+__global__ __launch_bounds__(64) void k_box_rows_wide_batch(StitchPtrs p, int cols, int rows, int k) {
+  const int z = blockIdx.z;
+  d_box_rows_wide(p.blend[z], p.rs[z], cols, rows, k);
+}
+__global__ __launch_bounds__(256) void k_box_rows_batch(StitchPtrs p, int cols, int rows, int k) {
+  __shared__ float tin[kBoxR][kBoxC + kBoxKMax + 1];
+  __shared__ double tout[kBoxR][kBoxC + 1];
+  const int z = blockIdx.z;
+  d_box_rows(p.blend[z], p.rs[z], cols, rows, k, tin, tout);
+}
+__global__ __launch_bounds__(64) void k_box_cols_batch(StitchPtrs p, int cols, int rows, int k) {
+  const int z = blockIdx.z;
+  d_box_cols(p.rs[z], p.tmp[z], cols, rows, k);
+}
+// blend -> tmp of every frame (each frame its own fp64 row sums rs)
+void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k) {
+  if (k <= kBoxKMax) hipLaunchKernelGGL(k_box_rows_batch, dim3((rows + kBoxR - 1) / kBoxR, 1, nf), dim3(256), 0, st, p, cols, rows, k);
+  else hipLaunchKernelGGL(k_box_rows_wide_batch, dim3((rows + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);
+  hipLaunchKernelGGL(k_box_cols_batch, dim3((cols + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);
+}
+
+// The tile smoothing of nf canvases as ONE persistent launch.  The work item is (frame, tile); the frames have one tile grid
+// (same size), so diagonal t of every frame is one diagonal of the launch: the per-diagonal active-tile counts are summed over
+// the frames, and the blocks walk the diagonals together exactly as k_tile_blur does for one canvas.  Frames share no pixels,
+// so the tiles of different frames on one diagonal are independent as well: the wavefront stays exact.
+__global__ __launch_bounds__(256) void k_tile_blur_batch(StitchPtrs p, int nf, int cols, int rows, int step, int k, int dskew, int ntx, int nty,
+                                                         TileBlurWork* __restrict__ wk, long long budget_ticks) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
+  const int nr = step + k - 1;
+  double* sm = reinterpret_cast<double*>(smraw);
+  float* win = reinterpret_cast<float*>(sm + size_t(nr) * step);
+  const int tid = threadIdx.x, nblk = gridDim.x;
+  const long long deadline = (long long)wall_clock64() + budget_ticks;
+  const int tmax = (ntx - 1) + dskew * (nty - 1), ntiles = ntx * nty;
+  auto active = [&](int f, int tx, int ty) { return p.md[f][size_t(ty) * step * cols + size_t(tx) * step] > step; };
+  // pass 0: active tiles per diagonal, summed over the frames
+  for (int i = blockIdx.x * 256 + tid; i < nf * ntiles; i += nblk * 256) {
+    const int f = i / ntiles, r = i - f * ntiles, ty = r / ntx, tx = r - ty * ntx;
+    if (active(f, tx, ty)) __hip_atomic_fetch_add(&wk->cnt[tx + dskew * ty], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  int phase = 1;
+  if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
+  const double scale = 1. / ((double)k * k);
+  for (int t = 0; t <= tmax; ++t) {
+    if (__hip_atomic_load(&wk->cnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) continue;   // the same answer in every block
+    const int lo = t - (ntx - 1);
+    const int ty_min = lo > 0 ? (lo + dskew - 1) / dskew : 0;
+    const int ty_max = t / dskew < nty - 1 ? t / dskew : nty - 1;
+    const int span = ty_max - ty_min + 1;
+    for (int item = blockIdx.x; item < nf * span; item += nblk) {   // (frame, tile) items of this diagonal
+      const int f = item / span, ty = ty_min + (item - f * span), tx = t - dskew * ty;
+      if (tx < 0 || tx >= ntx || !active(f, tx, ty)) continue;   // block-uniform
+      d_tile_blur_one(p.blend[f], cols, rows, step, k, tx * step, ty * step, sm, win, scale);
+    }
+    ++phase;
+    if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
+  }
+}
+void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work) {
+  if (step < 1 || k < 1) return;
+  int nty = 0, ntx = 0;
+  for (int y = 0; y + step < rows; y += step) ++nty;
+  for (int x = 0; x + step < cols; x += step) ++ntx;
+  if (nty <= 0 || ntx <= 0) return;
+  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
+  const int dskew = (reach + step - 1) / step + 1;
+  const size_t shmem = tile_blur_lds_bytes(step, k);
+  if (shmem > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_blur_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
+  // the grid-size rule of launch_tile_blur: every block resident (at most half of what fits on the device beside nothing else),
+  // no more blocks than a diagonal has items -- here the items of all frames
+  int dev = 0, ncu = 64, per_cu = 1;
+  if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_tile_blur_batch), 256, shmem) != hipSuccess || per_cu < 1) per_cu = 1;
+  int blocks = nty * nf < 32 ? nty * nf : 32;
+  if (blocks > ncu * per_cu / 2) blocks = ncu * per_cu / 2;
+  if (blocks < 1) blocks = 1;
+  const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks
+  hipLaunchKernelGGL(k_tile_blur_batch, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, dskew, ntx, nty,
+                     static_cast<TileBlurWork*>(work), budget);
+}
+
+__global__ __launch_bounds__(256) void k_gather_batch(StitchPtrs p, int cols, int rows) {
+  const int z = blockIdx.z;
+  d_gather_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), reinterpret_cast<const uchar4*>(p.merged[z]),
+              p.map[z], cols, rows, reinterpret_cast<uchar4*>(p.out[z]));
+}
+void launch_gather_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
+  hipLaunchKernelGGL(k_gather_batch, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows);
 }
 
 }  // namespace pf

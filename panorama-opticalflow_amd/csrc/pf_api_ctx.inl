@@ -36,6 +36,7 @@ struct pf_ctx {
   int lanes_running = 1;  // throughput mode: lanes (this one included) solving batches side by side on the device right now
   long fuse_ups_px = 0;   // levels up to this many pixels get their incoming flow upsampled inside their first Gaussian (0 = never)
   int chain_cols = 0, chain_rows = 0;   // size of the stitch-chain result resident in "ch_final"
+  int sb_cols = 0, sb_rows = 0, sb_frames = 0;   // pf_stitch_step_batch: size and frame count of the composites resident in the slots "sb_fin<k>"
   // pf_stitch_visualize: the last pf_stitch_step's inputs ("ch_l", "ch_r") and flows ("nv_flow_l2r", "nv_flow_r2l") are still in HBM.
   // Set by a successful pf_stitch_step, cleared by every call that may reuse those buffers (any solve, the throughput mode, a step).
   bool vis_step_valid = false;

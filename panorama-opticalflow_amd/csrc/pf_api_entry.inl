@@ -84,18 +84,17 @@ int novel_view_group(pf_ctx* lane, int first, int count, const uint8_t* const* d
   if (int e = finish(lane)) return e;
   return check_sweeps(lane);
 }
-}  // namespace
-int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
-                            const float* const* d_blend, uint8_t* const* d_out, float* const* d_l2r, float* const* d_r2l, int in_flight) {
-  if (int e = use(c)) return e;
-  c->vis_step_valid = false;   // lane 0 solves in this context's arena
-  if (n_pairs < 0 || !d_l || !d_r || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
+// The lanes of the throughput mode: n_items split into groups of per_batch (batch_split), group g on lane g % lanes, each lane
+// driven by its own host thread; group(lane, first, count) enqueues and drains one group.  Shared by pf_novel_view_batch_dev and
+// pf_stitch_step_batch*.  queues_per_lane: the HIP streams a lane drives (check_hw_queues: that many per lane + 2).
+extern "C++" template <class Group>
+int run_lanes(pf_ctx* c, int n_items, int in_flight, int cols, int rows, int queues_per_lane, const char* what, Group group) {
   if (in_flight < 1) in_flight = 1;
   if (in_flight > 2 * kMaxBatch) in_flight = 2 * kMaxBatch;
-  if (in_flight > n_pairs) in_flight = n_pairs > 0 ? n_pairs : 1;
+  if (in_flight > n_items) in_flight = n_items > 0 ? n_items : 1;
   int nlanes = 1, per_batch = 1;
   batch_split(c, in_flight, nlanes, per_batch);
-  check_hw_queues(c, 3 * nlanes + 2, "pf_novel_view_batch_dev");   // three streams per lane + this context's blend-ramp and copy streams
+  check_hw_queues(c, queues_per_lane * nlanes + 2, what);
   while ((int)c->lanes.size() < nlanes - 1) {
     pf_config lc = c->cfg; lc.max_cols = per_batch > 1 ? 0 : cols; lc.max_rows = per_batch > 1 ? 0 : rows;   // a batching lane lives in its slabs: nothing to pre-size
     pf_ctx* l = create_ctx(lc, true);
@@ -103,7 +102,7 @@ int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, c
     c->lanes.push_back(l);
   }
   for (pf_ctx* l : c->lanes) { l->prof = c->prof; l->sp = c->sp; l->cf = c->cf; }   // profiling covers every lane (collected into the lane's own totals); lanes solve with the owner's parameters
-  const int ngroups = (n_pairs + per_batch - 1) / per_batch;
+  const int ngroups = (n_items + per_batch - 1) / per_batch;
   std::vector<int> rc(nlanes, 0);
   std::vector<std::string> msg(nlanes);
   auto run = [&](int k) {
@@ -114,8 +113,8 @@ int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, c
     // A batch pays every launch once for all its pairs, and there the separate (shorter) kernels win again: 8 in one batch 1374 vs 1347 Mpix/s.
     if (in_flight > 1) { lane->fuse_ups_px = per_batch > 1 ? 0 : 262144; lane->is_lane = true; }
     for (int gidx = k; gidx < ngroups; gidx += nlanes) {
-      const int first = gidx * per_batch, count = std::min(per_batch, n_pairs - first);
-      const int e = novel_view_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_blend, d_out, d_l2r, d_r2l);
+      const int first = gidx * per_batch, count = std::min(per_batch, n_items - first);
+      const int e = group(lane, first, count);
       if (e) { rc[k] = e; msg[k] = lane->err; return; }
     }
   };
@@ -132,6 +131,17 @@ int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, c
         l->prof_tot[i] = ProfEntry();
       }
   return 0;
+}
+}  // namespace
+int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
+                            const float* const* d_blend, uint8_t* const* d_out, float* const* d_l2r, float* const* d_r2l, int in_flight) {
+  if (int e = use(c)) return e;
+  c->vis_step_valid = false;   // lane 0 solves in this context's arena
+  if (n_pairs < 0 || !d_l || !d_r || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
+  // three streams per lane + this context's blend-ramp and copy streams
+  return run_lanes(c, n_pairs, in_flight, cols, rows, 3, "pf_novel_view_batch_dev", [&](pf_ctx* lane, int first, int count) {
+    return novel_view_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_blend, d_out, d_l2r, d_r2l);
+  });
 }
 
 // ---- host-buffer entry points ----

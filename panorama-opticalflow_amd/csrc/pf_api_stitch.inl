@@ -1,11 +1,18 @@
 // Part of pf_api.hip (one translation unit, split along its seams in round 5): Stitchtools: prepare / match / blend ramp / gather, the device-resident chain step and its prefetch.
 
+// The tile kernel keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS, step = min(cols, rows)/200, k1 = rows/130:
+// 160 KB per CU.  For canvases at least as wide as they are tall that bounds them at 12,000 rows (24000x12000 fits, 24500x12250
+// does not; 30000x15000 would need 250 KB); narrower canvases can have more rows.
+static bool blend_ramp_fits(int cols, int rows) {
+  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130;
+  return !(step > 0 && k1 > 0) || tile_blur_lds_bytes(step, k1) <= 160 * 1024;
+}
+
 static int blend_smooth_dev(pf_ctx* c, float* d_blend, const float* d_md, int cols, int rows, hipStream_t sm = nullptr) {
   const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130, k2 = rows / 400;
   if (!sm) sm = c->s_main;
   if (step > 0 && k1 > 0) {
-    // the tile kernel keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS: 160 KB per CU bound the canvas at ~15000 rows
-    if (tile_blur_lds_bytes(step, k1) > 160 * 1024) return fail(c, PF_ERR_ARG, "canvas %dx%d too large for the blend-ramp tile smoothing (LDS)", cols, rows);
+    if (!blend_ramp_fits(cols, rows)) return fail(c, PF_ERR_ARG, "canvas %dx%d too large for the blend-ramp tile smoothing (LDS)", cols, rows);
     void* work = ensure(c, "st_tile_work", tile_blur_work_bytes(cols, rows, step, k1) + 256);
     if (!work) return PF_ERR_NOMEM;
     { PROF(c, sm, "tile_blur"); launch_tile_blur(sm, d_blend, d_md, cols, rows, step, k1, work); }
@@ -236,3 +243,152 @@ int pf_stitch_prefetch(pf_ctx* c, const uint8_t* next_l, int cols, int rows, siz
   return 0;
 }
 
+
+// ---- batched stitch step: many canvases in flight ----
+// Frame k of a call is exactly one pf_stitch_step of its own chain; frames share nothing but the launches.  Groups of up to
+// kMaxBatch frames go through one set of launches (blockIdx.z = frame) on a lane of the throughput mode (run_lanes): the batched
+// match on the lane's main stream, the blend ramp (countblend, ONE persistent tile-smoothing launch for all frames, box blur) on
+// its aux stream beside solve_n() of the overlaps on the direction streams, then the batched novel-view blend and gather.
+namespace {
+// everything pf_stitch_step refuses about the canvas, before any work
+int check_stitch_canvas(pf_ctx* c, int cols, int rows, int max_pct) {
+  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  if (!blend_ramp_fits(cols, rows)) return fail(c, PF_ERR_ARG, "canvas %dx%d too large for the blend-ramp tile smoothing (LDS)", cols, rows);
+  if (max_pct < 0 || max_pct > 100) return fail(c, PF_ERR_ARG, "max_percentage %d out of range", max_pct);
+  return 0;
+}
+// per-frame planes of a group, `count` frames back to back in one arena buffer (256-byte aligned frames)
+extern "C++" template <class T> T* frame_planes(pf_ctx* c, const char* name, int count, size_t per_frame, size_t& stride) {
+  stride = (per_frame + 255) & ~size_t(255);
+  return (T*)ensure(c, name, stride * count);
+}
+int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
+                 uint8_t* const* d_out) {
+  if (int e = use(lane)) return e;
+  CallGuard guard_(lane);
+  const size_t n = size_t(cols) * rows;
+  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130, k2 = rows / 400;
+  // 33 B/px of StitchTool planes per frame (map 1, overlaps 8, ramp + MergedDis 8, box blur 12, novel view 4) + 16 B/px of flows
+  size_t s1, s4, s8, s16;
+  uint8_t* map = frame_planes<uint8_t>(lane, "sb_map", count, n, s1);
+  uint8_t* ovl = frame_planes<uint8_t>(lane, "sb_ovl", count, n * 4, s4); uint8_t* ovr = frame_planes<uint8_t>(lane, "sb_ovr", count, n * 4, s4);
+  float* blend = frame_planes<float>(lane, "sb_blend", count, n * 4, s4); float* md = frame_planes<float>(lane, "sb_md", count, n * 4, s4);
+  uint8_t* merged = frame_planes<uint8_t>(lane, "sb_merged", count, n * 4, s4);
+  float* flow = frame_planes<float>(lane, "sb_flow", count, n * 16, s16);
+  if (!map || !ovl || !ovr || !blend || !md || !merged || !flow) return PF_ERR_NOMEM;
+  double* rs = nullptr; float* tmp = nullptr;
+  if (k2 > 0) {
+    rs = frame_planes<double>(lane, "sb_rowsum", count, n * 8, s8); tmp = frame_planes<float>(lane, "sb_blur_tmp", count, n * 4, s4);
+    if (!rs || !tmp) return PF_ERR_NOMEM;
+  }
+  StitchPtrs sp{};
+  BlendPtrs bp{};
+  const uint8_t* i0[kMaxBatch]; const uint8_t* i1[kMaxBatch]; float* outs[2 * kMaxBatch];
+  for (int p = 0; p < count; ++p) {
+    sp.L[p] = d_l[first + p]; sp.R[p] = d_r[first + p]; sp.out[p] = d_out[first + p];
+    sp.map[p] = map + p * s1; sp.ovL[p] = ovl + p * s4; sp.ovR[p] = ovr + p * s4;
+    sp.blend[p] = (float*)((char*)blend + p * s4); sp.md[p] = (float*)((char*)md + p * s4); sp.merged[p] = merged + p * s4;
+    sp.rs[p] = rs ? (double*)((char*)rs + p * s8) : nullptr; sp.tmp[p] = tmp ? (float*)((char*)tmp + p * s4) : nullptr;
+    i0[p] = sp.ovL[p]; i1[p] = sp.ovR[p];
+    outs[2 * p] = (float*)((char*)flow + p * s16); outs[2 * p + 1] = outs[2 * p] + n * 2;
+    bp.L[p] = sp.ovL[p]; bp.R[p] = sp.ovR[p]; bp.fLR[p] = outs[2 * p]; bp.fRL[p] = outs[2 * p + 1];
+    bp.blend[p] = k2 > 0 ? sp.tmp[p] : sp.blend[p]; bp.out[p] = merged + p * s4;
+  }
+  hipStream_t sm = lane->s_main;
+  { PROF(lane, sm, "match_images"); launch_match_images_batch(sm, sp, count, cols, rows); }
+  // the blend ramp depends on the maps only: aux stream, enqueued after the solver's launches (as in pf_stitch_step)
+  if (!lane->s_aux) HIPCHK(lane, hipStreamCreateWithFlags(&lane->s_aux, hipStreamNonBlocking));
+  hipStream_t sa = lane->s_aux;
+  HIPCHK(lane, hipEventRecord(lane->ev_aux_go, sm));
+  const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT};
+  if (int e = solve_n(lane, count, i0, i1, cols, rows, cols / 20, max_pct, 2, hints, outs)) return e;
+  HIPCHK(lane, hipStreamWaitEvent(sa, lane->ev_aux_go, 0));
+  { PROF(lane, sa, "countblend"); launch_countblend_batch(sa, sp, count, cols, rows); }
+  if (step > 0 && k1 > 0) {
+    void* work = ensure(lane, "sb_tile_work", tile_blur_work_bytes(cols, rows, step, k1) + 256);
+    if (!work) return PF_ERR_NOMEM;
+    { PROF(lane, sa, "tile_blur"); launch_tile_blur_batch(sa, sp, count, cols, rows, step, k1, work); }
+    launch_collect_status(sa, static_cast<const int*>(work), 2, lane->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
+  }
+  if (k2 > 0) { PROF(lane, sa, "box_blur"); launch_box_blur_batch(sa, sp, count, cols, rows, k2); }   // the smoothed ramp lands in tmp
+  HIPCHK(lane, hipEventRecord(lane->ev_aux_done, sa));
+  HIPCHK(lane, hipStreamWaitEvent(sm, lane->ev_aux_done, 0));
+  { PROF(lane, sm, "blend"); launch_blend_batch(sm, bp, count, cols, rows); }
+  { PROF(lane, sm, "gather"); launch_gather_batch(sm, sp, count, cols, rows); }
+  HIPCHK(lane, hipGetLastError());
+  if (int e = finish(lane)) return e;
+  return check_sweeps(lane);
+}
+bool overlaps(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+}  // namespace
+
+int pf_stitch_step_batch_dev(pf_ctx* c, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
+                             uint8_t* const* d_out, int in_flight) {
+  if (int e = use(c)) return e;
+  c->vis_step_valid = false;   // lane 0 solves in this context's arena
+  if (n_frames < 0 || !d_l || !d_r || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
+  if (n_frames == 0) return 0;
+  if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
+  const size_t bytes = size_t(cols) * rows * 4;
+  for (int k = 0; k < n_frames; ++k)
+    if (!d_l[k] || !d_r[k] || !d_out[k]) return fail(c, PF_ERR_ARG, "null device pointer (frame %d)", k);
+  // a composite is written while the frame's inputs (and those of the frames in its launches) are still read: no aliasing
+  for (int k = 0; k < n_frames; ++k)
+    for (int j = 0; j < n_frames; ++j)
+      if (overlaps(d_out[k], d_l[j], bytes) || overlaps(d_out[k], d_r[j], bytes) || (j != k && overlaps(d_out[k], d_out[j], bytes)))
+        return fail(c, PF_ERR_ARG, "d_out[%d] overlaps an input or another output of the call (frame %d)", k, j);
+  return run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
+    return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out);
+  });
+}
+
+// Host form: one slot of three planes per frame index (12 B/px: left, right, composite), kept between calls so that frame k may
+// chain on its own previous composite.  The slots are separate from pf_stitch_step's chain ("ch_*") and prefetch records.
+int pf_stitch_step_batch(pf_ctx* c, int n_frames, const uint8_t* const* l, const uint8_t* const* r, int cols, int rows, size_t step, int max_pct,
+                         uint8_t* const* out, size_t ostep, int in_flight) {
+  if (int e = use(c)) return e;
+  c->vis_step_valid = false;
+  if (n_frames < 0 || !l) return fail(c, PF_ERR_ARG, "bad argument");
+  if (n_frames == 0) return 0;
+  for (int k = 0; k < n_frames; ++k) if (!l[k]) return fail(c, PF_ERR_ARG, "null pointer (frame %d)", k);
+  if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
+  if (step < size_t(cols) * 4 || (out && ostep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
+  for (int k = 0; k < n_frames; ++k)
+    if ((!r || !r[k]) && (c->sb_cols != cols || c->sb_rows != rows || k >= c->sb_frames))
+      return fail(c, PF_ERR_ARG, "pf_stitch_step_batch: frame %d has no previous batch result of this size to chain on", k);
+  const size_t n = size_t(cols) * rows;
+  std::vector<uint8_t*> dl(n_frames), dr(n_frames), dfin(n_frames);
+  for (int k = 0; k < n_frames; ++k) {
+    char name[32];
+    snprintf(name, sizeof name, "sb_l%d", k); dl[k] = (uint8_t*)ensure(c, name, n * 4);
+    snprintf(name, sizeof name, "sb_r%d", k); dr[k] = (uint8_t*)ensure(c, name, n * 4);
+    snprintf(name, sizeof name, "sb_fin%d", k); dfin[k] = (uint8_t*)ensure(c, name, n * 4);
+    if (!dl[k] || !dr[k] || !dfin[k]) return PF_ERR_NOMEM;
+  }
+  c->sb_frames = 0;   // the slots are rewritten from here on: chaining needs this call to succeed
+  {
+    CallGuard guard_(c);
+    for (int k = 0; k < n_frames; ++k) {
+      if (int e = up2d(c, dl[k], size_t(cols) * 4, l[k], step, size_t(cols) * 4, rows)) return e;
+      if (r && r[k]) { if (int e = up2d(c, dr[k], size_t(cols) * 4, r[k], step, size_t(cols) * 4, rows)) return e; }
+      else HIPCHK(c, hipMemcpyAsync(dr[k], dfin[k], n * 4, hipMemcpyDeviceToDevice, c->s_main));
+    }
+    if (int e = finish(c)) return e;   // the lanes' streams start from complete inputs
+  }
+  const int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
+    return stitch_group(lane, first, count, dl.data(), dr.data(), cols, rows, max_pct, dfin.data());
+  });
+  if (e) return e;
+  if (out) {
+    CallGuard guard_(c);
+    for (int k = 0; k < n_frames; ++k)
+      if (out[k]) if (int e2 = down2d(c, out[k], ostep, dfin[k], size_t(cols) * 4, size_t(cols) * 4, rows)) return e2;
+    HIPCHK(c, hipGetLastError());
+    if (int e2 = finish(c)) return e2;
+  }
+  c->sb_cols = cols; c->sb_rows = rows; c->sb_frames = n_frames;
+  return 0;
+}

@@ -188,6 +188,20 @@ size_t tile_blur_lds_bytes(int step, int k);
 void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work);
 void launch_gather(hipStream_t st, const uint8_t* L, const uint8_t* R, const uint8_t* merged, const uint8_t* map, int cols, int rows,
                    uint8_t* out);
+int countblend_step(int cols, int rows);   // the probe stride of countblend (StitchTool.cpp:151), at least 1
+// batched stitch step (pf_stitch_step_batch*): per-frame pointer tables, blockIdx.z = frame, nf <= kMaxBatch same-size frames per launch
+struct StitchPtrs {
+  const uint8_t* L[kMaxBatch]; const uint8_t* R[kMaxBatch];     // input images
+  uint8_t* map[kMaxBatch]; uint8_t* ovL[kMaxBatch]; uint8_t* ovR[kMaxBatch];
+  float* blend[kMaxBatch]; float* md[kMaxBatch];                // ramp (smoothed in place by the tile pass) and MergedDis
+  double* rs[kMaxBatch]; float* tmp[kMaxBatch];                 // box blur: fp64 row sums, result
+  const uint8_t* merged[kMaxBatch]; uint8_t* out[kMaxBatch];    // novel view, composite
+};
+void launch_match_images_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);   // L, R -> map, ovL, ovR
+void launch_countblend_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
+void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work);   // blend in place; work as launch_tile_blur's
+void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k); // blend -> tmp (rs: scratch)
+void launch_gather_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);         // L, R, merged, map -> out
 void launch_fill_u64(hipStream_t st, unsigned long long* p, size_t n, unsigned long long v, Batch bt = Batch());
 void launch_fill_u32(hipStream_t st, unsigned* p, size_t n, unsigned v, Batch bt = Batch());   // memset that knows the batch dimension
 void launch_checksum64(hipStream_t st, const void* p, size_t bytes, unsigned long long* acc /* zeroed by the caller */);

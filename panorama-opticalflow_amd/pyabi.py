@@ -93,6 +93,7 @@ EXPORTS = [
     "pf_device_count", "pf_create", "pf_config_init", "pf_create_cfg", "pf_destroy", "pf_last_error", "pf_last_warning", "pf_warning_count", "pf_version", "pf_max_percentage_by_name",
     "pf_solver_params_init", "pf_set_solver_params", "pf_get_solver_params",
     "pf_flow", "pf_flow_bidir", "pf_blend", "pf_novel_view", "pf_stitch_prepare", "pf_stitch_match", "pf_stitch_generate_blend", "pf_stitch_raw_blend", "pf_stitch_gather", "pf_stitch_step", "pf_stitch_prefetch",
+    "pf_stitch_step_batch", "pf_stitch_step_batch_dev",
     "pf_dev_alloc", "pf_dev_free", "pf_host_alloc", "pf_host_free", "pf_upload", "pf_download", "pf_sync", "pf_checksum_dev", "pf_selftest_packed_chains",
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
@@ -304,6 +305,32 @@ class Context:
                                         None if out is None else _p(out), C.c_size_t(cols * 4)))
         self._step_shape = (rows, cols)
         return out
+
+    def stitch_step_batch(self, Ls, Rs, max_pct, in_flight=8, want_out=True, out=None):
+        """n independent stitch steps of one size (frame k = one stitch_step of its own chain).  Rs=None, or a None entry, chains
+        frame k on its composite from the previous stitch_step_batch call.  Returns a list of (rows, cols, 4) arrays, or of None.
+        out: optional list of preallocated (rows, cols, 4) uint8 arrays for the composites (as stitch_step's `out`)."""
+        n = len(Ls)
+        ls = [_u8(a) for a in Ls]
+        rows, cols = ls[0].shape[:2] if n else (0, 0)
+        assert all(a.shape == (rows, cols, 4) for a in ls)
+        rs = None if Rs is None else [None if r is None else _u8(r) for r in Rs]
+        assert rs is None or (len(rs) == n and all(r is None or r.shape == (rows, cols, 4) for r in rs))
+        if out is not None:
+            assert len(out) == n and all(o.dtype == np.uint8 and o.shape == (rows, cols, 4) and o.flags["C_CONTIGUOUS"] for o in out)
+            outs, want_out = list(out), True
+        else:
+            outs = [np.empty((rows, cols, 4), np.uint8) for _ in range(n)] if want_out else [None] * n
+        arr = lambda v: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in v])
+        self._chk(self.l.pf_stitch_step_batch(self.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4), max_pct,
+                                              arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
+        return outs
+
+    def stitch_step_batch_dev(self, d_l, d_r, cols, rows, max_pct, d_out, in_flight=8):
+        """the device form: lists of device pointers (packed BGRA), every d_r entry non-NULL"""
+        n = len(d_l)
+        arr = lambda v: (C.c_void_p * max(n, 1))(*[C.c_void_p(int(x)) if x else None for x in v])
+        self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
 
     # ---- flow visualisation (CPU/OpticalFlow.cpp:147-204, the panel of CPU/main.cpp:20-45) ----
     def vis_grey_disparity(self, flow):

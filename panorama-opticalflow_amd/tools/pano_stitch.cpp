@@ -7,6 +7,9 @@
 //   LtoR_<alg>.png / RtoL_<alg>.png, so each step would overwrite the previous one; the step number keeps them all.
 // reads <dir>/<top_img> and <dir>/1.tif .. 5.tif (8-bit RGB/RGBA TIFF or PNG), writes ProcessResult{i}.png and
 // FinalResult.png (main.cpp:97-100).
+//   pano_stitch -test_dirs <dir1>,<dir2>,... -top_img top.tif -flow_alg ... [-steps 5] [-in_flight 8]: the -test_dir flow for every
+//   directory at once through the batched step (pf_stitch_step_batch, one frame per directory); each directory gets the same files as
+//   its own -test_dir run, and one "Part<i> Finished!" line is printed per batched step.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -14,6 +17,7 @@
 #include <iostream>
 #include <map>
 #include <string>
+#include <vector>
 
 #include "../include/OpticalFlow.hpp"
 #include "../include/StitchTool.hpp"
@@ -100,9 +104,70 @@ static int run4Input(const std::string& dir, const std::string& flow_alg) {
   return EXIT_SUCCESS;
 }
 
+// the -test_dir flow for several directories, step i of all of them in one pf_stitch_step_batch call (frame k = directory k; the
+// chain R_i = FinalResult_{i-1} of every directory stays in HBM)
+static std::vector<std::string> splitDirs(const std::string& list) {
+  std::vector<std::string> dirs;
+  size_t b = 0;
+  while (true) {
+    const size_t e = list.find(',', b);
+    const std::string d = list.substr(b, e == std::string::npos ? std::string::npos : e - b);
+    if (d.empty()) throw VrCamException("-test_dirs: empty directory name in '" + list + "'");
+    struct stat st;
+    if (stat(d.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) throw VrCamException("-test_dirs: no such directory: " + d);
+    dirs.push_back(d);
+    if (e == std::string::npos) return dirs;
+    b = e + 1;
+  }
+}
+static int runBatchDirs(const std::vector<std::string>& dirs, const std::string& top_img, const std::string& flow_alg, int nsteps, int in_flight) {
+  const int maxPct = pf_max_percentage_by_name(flow_alg.c_str());
+  if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + flow_alg);
+  double StartTime = getCurrTimeSec();
+  const int n = (int)dirs.size();
+  std::vector<Mat> tops(n), Ls(n), outs(n);
+  for (int k = 0; k < n; ++k) tops[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + top_img);
+  for (int i = 1; i <= nsteps; i++) {
+    double StepStart = getCurrTimeSec();
+    for (int k = 0; k < n; ++k) Ls[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + char(i + 48) + ".tif");
+    std::vector<const uint8_t*> l(n), r(n);
+    std::vector<uint8_t*> o(n);
+    for (int k = 0; k < n; ++k) {
+      auto same = [&](const Mat& m) { return m.type() == CV_8UC4 && m.rows == Ls[0].rows && m.cols == Ls[0].cols && m.step == Ls[0].step; };
+      if (!same(Ls[k]) || (i == 1 && !same(tops[k])))
+        throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
+      outs[k] = Mat(Ls[0].rows, Ls[0].cols, CV_8UC4);
+      l[k] = Ls[k].data; r[k] = tops[k].data; o[k] = outs[k].data;
+    }
+    pano::check(pf_stitch_step_batch(pano::context(), n, l.data(), i == 1 ? r.data() : nullptr, Ls[0].cols, Ls[0].rows, Ls[0].step, maxPct,
+                                     o.data(), outs[0].step, in_flight));
+    for (int k = 0; k < n; ++k) {
+      if (i == nsteps) pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "FinalResult.png", outs[k]);
+      else pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", outs[k]);
+    }
+    std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
+  }
+  std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
+  return EXIT_SUCCESS;
+}
+
 int main(int argc, char** argv) {
   try {
     auto flags = parseFlags(argc, argv);
+    if (flags.count("test_dirs")) {   // every refusal before any device call
+      if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
+      if (flags.count("fused") && atoi(flags["fused"].c_str()) == 0) throw VrCamException("-test_dirs runs the fused step only (-fused 0 is not supported)");
+      if (flags.count("visualize") && atoi(flags["visualize"].c_str()) != 0) throw VrCamException("-test_dirs does not support -visualize 1");
+      if (flags.count("inputs")) throw VrCamException("-test_dirs does not support -inputs");
+      if (flags["test_dirs"].empty()) throw VrCamException("-test_dirs: empty directory list");
+      const std::vector<std::string> dirs = splitDirs(flags["test_dirs"]);
+      requireArg(flags["top_img"], "top_img");
+      requireArg(flags["flow_alg"], "flow_alg");
+      const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
+      const int in_flight = flags.count("in_flight") ? atoi(flags["in_flight"].c_str()) : 8;
+      if (in_flight < 1 || in_flight > 32) throw VrCamException("-in_flight must be 1..32");
+      return runBatchDirs(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight);
+    }
     const std::string FLAGS_test_dir = flags["test_dir"], FLAGS_top_img = flags["top_img"], FLAGS_flow_alg = flags["flow_alg"];
     const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
     const bool fused = !flags.count("fused") || atoi(flags["fused"].c_str()) != 0;   // -fused 0: the reference's object-by-object sequence
