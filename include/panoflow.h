@@ -146,12 +146,13 @@ int pf_novel_view(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int
                   int max_percentage, const float* blend, size_t blend_step_bytes, uint8_t* out_bgra, size_t out_step_bytes,
                   float* flow_l2r, float* flow_r2l, size_t flow_step_bytes);
 
-/* Size limit of the stitch entry points that build the blend ramp (pf_stitch_prepare, pf_stitch_generate_blend, pf_stitch_step,
- * pf_stitch_step_batch*): the tile smoothing of GenerateBlend (CPU/StitchTool.cpp:130-143) keeps one tile's window, (step + k - 1)^2 floats
- * + (step + k - 1) x step doubles with step = min(cols, rows) / 200 and k = rows / 130, in the 160 KiB (163,840 B) of LDS of a CU.  For
- * canvases at least as wide as they are tall that allows up to 12,000 rows (24000x12000 is accepted, 24500x12250 is not; a 30000x15000
- * equirectangular panorama would need ~250 KiB); narrower canvases can have more rows.  Beyond the limit they return PF_ERR_ARG.  The
- * solver and blend entry points have no such limit. */
+/* Canvas sizes of the stitch entry points that build the blend ramp (pf_stitch_prepare, pf_stitch_generate_blend, pf_stitch_step,
+ * pf_stitch_step_batch*): any size the image checks accept.  The tile smoothing of GenerateBlend (CPU/StitchTool.cpp:130-143) works on
+ * one tile's window, (step + k - 1)^2 floats + (step + k - 1) x step doubles with step = min(cols, rows) / 200 and k = rows / 130.  Where
+ * that fits the 160 KiB (163,840 B) of LDS of a CU (24000x12000 does, 24500x12250 does not) the window stays resident; larger windows
+ * (a 30000x15000 equirectangular panorama: ~250 KiB; a 400x26200 strip) are streamed through the LDS in pieces, with the same
+ * bits and a per-block scratch area in the context's arena (pre-sized by pf_create).  The one exception: a window that reaches across
+ * the whole canvas (k/2 >= min(cols, rows): canvases more than ~260 times taller than wide) returns PF_ERR_ARG. */
 /* Stitchtools::prepare, CPU/StitchTool.cpp:7-36 (MatchImages :38-50, GenerateBlend :98-146,
  * countblend :148-191).  merged_dis may be NULL.  All planes cols x rows, packed rows of `step`. */
 int pf_stitch_prepare(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int cols, int rows, size_t step_bytes,
@@ -284,6 +285,11 @@ int pf_stage_adjust_initial_flow(pf_ctx* ctx, const float* i0, const float* i1, 
 int pf_stage_level(pf_ctx* ctx, const float* i0, const float* i1, const float* a0, const float* a1, int w, int h,
                    const float* flow_in /* nullable */, int hint, int max_percentage, float* flow_out); /* PixFlow.hpp:272-340 */
 int pf_stage_blend_smooth(pf_ctx* ctx, float* blend_inout, const float* merged_dis, int cols, int rows); /* StitchTool.cpp:130-143 */
+/* The tile pass of that smoothing alone (StitchTool.cpp:134-141, without the final rows/400 blur), tile size `step` and window `k` given
+ * explicitly: the kernel the stitch entry points run.  form: -1 = the form the library would choose, 0 = window resident in LDS
+ * (PF_ERR_ARG if it does not fit), 1 = streamed (any geometry whose window row, step + k - 1 floats, fits that LDS).  PF_ERR_ARG for
+ * step < 1, k < 1, step >= min(cols, rows) (no tile), max(k/2, k-1-k/2) >= min(cols, rows), null pointers. */
+int pf_stage_tile_blur(pf_ctx* ctx, float* blend_inout, const float* merged_dis, int cols, int rows, int step, int k, int form);
 
 /* ---- flow visualisation ---------------------------------------------------------------------
  * The reference's debugging views of a flow (CPU/OpticalFlow.cpp:147-204, declared in CPU/OpticalFlow.hpp:72-76), byte for byte,

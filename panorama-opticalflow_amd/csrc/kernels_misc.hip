@@ -516,12 +516,169 @@ __device__ __forceinline__ void d_tile_blur_one(float* __restrict__ img, int col
     }
   }
 }
+// The same tile through a FIXED amount of LDS (tile_stream_plan.hpp), for windows that do not fit a CU's 160 KB: the window is staged
+// in chunks of whole rows, the lane of a row walks it from its first to its last column (the sliding sum stays in its register, in
+// d_tile_blur_one's order), and every row sum goes to this block's scratch in HBM, column-major.  Only when ALL row sums exist --
+// i.e. after the last read of the image, which matters because the tile's own block lies inside its window -- do they come back,
+// in strips of whole output columns, for the column walk (again one lane from top to bottom, nothing carried between pieces).
+struct TileStreamArgs { TileStreamPlan plan; double* scratch; };   // scratch: plan.scratch_bytes per block
+// border index of the streamed form: its callers admit only windows that reach less than a whole canvas across the border, so one
+// reflection is enough (no loop: the staging below is a straight run of independent loads)
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at any float address
+__device__ __forceinline__ int d_reflect101_once(int p, int n) { return p < 0 ? -p : (p >= n ? 2 * n - 2 - p : p); }
+__device__ __forceinline__ void d_tile_blur_one_streamed(float* img, int cols, int rows, int step, int k, int x0, int y0, unsigned char* lds,
+                                                         const TileStreamPlan& pl, double* __restrict__ sums, double scale) {
+  const int a = k / 2, nr = pl.nr, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int ws = pl.win_stride, ss = pl.sum_stride;
+  float* win = reinterpret_cast<float*>(lds);
+  double* sms = reinterpret_cast<double*>(lds);
+  constexpr int U = 16;   // LDS reads in flight per lane in the two walks: the sums are serial, their operands are not
+  for (int j0 = 0; j0 < nr; j0 += pl.chunk_rows) {
+    const int nrow = nr - j0 < pl.chunk_rows ? nr - j0 : pl.chunk_rows;
+    __syncthreads();   // the previous piece (or tile) is no longer read
+    // A tile of a tall strip is a 160 KB window for four outputs and waits for little else than these loads (cold ones: the grid
+    // barrier before it dropped the cache), so as many as possible are in flight at once.
+    if (x0 - a >= 0 && x0 - a + nr <= cols && nr >= 4) {
+      // no column of the window is reflected (block-uniform): a wave stages 16 rows at a time with one 16-byte load per lane and
+      // row, the last lane of a row moved left to end with it (it stores a few values twice, the same ones)
+      for (int jb = wave; jb < nrow; jb += 64) {
+        for (int i0 = 4 * lane; i0 < nr; i0 += 256) {
+          const int is = i0 + 4 <= nr ? i0 : nr - 4;
+          float4u v[16];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) {
+            const int jl = jb + 4 * u < nrow ? jb + 4 * u : jb;
+            v[u] = *reinterpret_cast<const float4u*>(img + size_t(d_reflect101_once(y0 - a + j0 + jl, rows)) * cols + (x0 - a + is));
+          }
+#pragma unroll
+          for (int u = 0; u < 16; ++u) {
+            if (jb + 4 * u < nrow) {
+              float* d = win + (jb + 4 * u) * ws + is;
+              d[0] = v[u].x; d[1] = v[u].y; d[2] = v[u].z; d[3] = v[u].w;
+            }
+          }
+        }
+      }
+    } else {
+      // a wave stages eight rows at a time, four 64-column pieces of each: 32 independent loads per lane, because a tile of a tall
+      // strip is a 160 KB window for four outputs and waits for little else (rows / columns past the end repeat an earlier one
+      // and are not stored)
+      for (int jb = wave; jb < nrow; jb += 32) {
+        size_t roff[8];
+  #pragma unroll
+        for (int u = 0; u < 8; ++u) roff[u] = size_t(d_reflect101_once(y0 - a + j0 + (jb + 4 * u < nrow ? jb + 4 * u : jb), rows)) * cols;
+        for (int i0 = lane; i0 < nr; i0 += 256) {
+          int col[4];
+  #pragma unroll
+          for (int c = 0; c < 4; ++c) col[c] = d_reflect101_once(x0 - a + (i0 + 64 * c < nr ? i0 + 64 * c : i0), cols);
+          float v[8][4];
+  #pragma unroll
+          for (int u = 0; u < 8; ++u)
+  #pragma unroll
+            for (int c = 0; c < 4; ++c) v[u][c] = img[roff[u] + col[c]];
+  #pragma unroll
+          for (int u = 0; u < 8; ++u)
+  #pragma unroll
+            for (int c = 0; c < 4; ++c)
+              if (jb + 4 * u < nrow && i0 + 64 * c < nr) win[(jb + 4 * u) * ws + i0 + 64 * c] = v[u][c];
+        }
+      }
+    }
+    __syncthreads();
+    for (int jl = tid; jl < nrow; jl += 256) {
+      const float* r = win + jl * ws;
+      double* out = sums + j0 + jl;
+      double s = 0;
+      int i = 0;
+      for (; i + U <= k; i += U) {
+        float v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = r[i + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) s += (double)v[u];
+      }
+      for (; i < k; ++i) s += (double)r[i];
+      out[0] = s;
+      int x = 1;
+      for (; x + U <= step; x += U) {
+        float va[U], vs[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { va[u] = r[x + u - 1 + k]; vs[u] = r[x + u - 1]; }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          s += (double)va[u] - (double)vs[u];
+          out[size_t(x + u) * ss] = s;
+        }
+      }
+      for (; x < step; ++x) {
+        s += (double)r[x - 1 + k] - (double)r[x - 1];
+        out[size_t(x) * ss] = s;
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's row sums have left it before the block meets
+  for (int xs = 0; xs < step; xs += pl.strip_cols) {
+    const int nx = step - xs < pl.strip_cols ? step - xs : pl.strip_cols, cnt = nx * ss;
+    __syncthreads();   // the previous piece is no longer read; after the last chunk: every row sum is in scratch
+    const double* src = sums + size_t(xs) * ss;   // whole columns: one contiguous run
+    for (int base = 0; base < cnt; base += 256 * 4) {
+      double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const int idx = base + u * 256 + tid; v[u] = src[idx < cnt ? idx : cnt - 1]; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const int idx = base + u * 256 + tid; if (idx < cnt) sms[idx] = v[u]; }
+    }
+    __syncthreads();
+    for (int xl = tid; xl < nx; xl += 256) {
+      const double* c = sms + xl * ss;
+      float* o = img + size_t(y0) * cols + x0 + xs + xl;
+      double sum = 0;
+      int j = 0;
+      for (; j + U <= k - 1; j += U) {
+        double v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = c[j + u];
+#pragma unroll
+        for (int u = 0; u < U; ++u) sum += v[u];
+      }
+      for (; j < k - 1; ++j) sum += c[j];
+      int y = 0;
+      for (; y + U / 2 <= step; y += U / 2) {
+        double va[U / 2], vs[U / 2];
+#pragma unroll
+        for (int u = 0; u < U / 2; ++u) { va[u] = c[y + u + k - 1]; vs[u] = c[y + u]; }
+#pragma unroll
+        for (int u = 0; u < U / 2; ++u) {
+          const double s0 = sum + va[u];
+          o[size_t(y + u) * cols] = (float)(s0 * scale);
+          sum = s0 - vs[u];
+        }
+      }
+      for (; y < step; ++y) {
+        const double s0 = sum + c[y + k - 1];
+        o[size_t(y) * cols] = (float)(s0 * scale);
+        sum = s0 - c[y];
+      }
+    }
+  }
+}
+// the per-tile routine of both launchers: kStream = false is d_tile_blur_one on LDS split as before, true the streamed form
+template <bool kStream>
+__device__ __forceinline__ void d_tile_blur_tile(float* __restrict__ img, int cols, int rows, int step, int k, int x0, int y0, unsigned char* smraw,
+                                                 const TileStreamArgs& sa, double scale) {
+  if constexpr (kStream) {
+    d_tile_blur_one_streamed(img, cols, rows, step, k, x0, y0, smraw, sa.plan, sa.scratch + size_t(blockIdx.x) * (sa.plan.scratch_bytes / sizeof(double)), scale);
+  } else {
+    const int nr = step + k - 1;
+    double* sm = reinterpret_cast<double*>(smraw);                 // row sums: nr x step
+    float* win = reinterpret_cast<float*>(sm + size_t(nr) * step);  // the tile's input window: nr x nr
+    d_tile_blur_one(img, cols, rows, step, k, x0, y0, sm, win, scale);
+  }
+}
+template <bool kStream>
 __global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, const float* __restrict__ mergedDis, int cols, int rows, int step, int k,
-                                                   int dskew, int ntx, int nty, TileBlurWork* __restrict__ wk, long long budget_ticks) {
+                                                   int dskew, int ntx, int nty, TileBlurWork* __restrict__ wk, long long budget_ticks, TileStreamArgs sa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-  const int nr = step + k - 1;
-  double* sm = reinterpret_cast<double*>(smraw);                 // row sums: nr x step
-  float* win = reinterpret_cast<float*>(sm + size_t(nr) * step);  // the tile's input window: nr x nr
   const int tid = threadIdx.x, nblk = gridDim.x;
   const long long deadline = (long long)wall_clock64() + budget_ticks;
   const int tmax = (ntx - 1) + dskew * (nty - 1);
@@ -542,7 +699,7 @@ __global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, cons
     for (int ty = ty_min + blockIdx.x; ty <= ty_max; ty += nblk) {
       const int tx = t - dskew * ty;
       if (tx < 0 || tx >= ntx || !active(tx, ty)) continue;   // block-uniform
-      d_tile_blur_one(img, cols, rows, step, k, tx * step, ty * step, sm, win, scale);
+      d_tile_blur_tile<kStream>(img, cols, rows, step, k, tx * step, ty * step, smraw, sa, scale);
     }
     ++phase;
     if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
@@ -559,34 +716,68 @@ size_t tile_blur_work_bytes(int cols, int rows, int step, int k) {
   return sizeof(TileBlurWork) + sizeof(int) * size_t((ntx - 1) + dskew * (nty - 1) + 1);
 }
 size_t tile_blur_lds_bytes(int step, int k) { const size_t nr = size_t(step) + k - 1; return nr * step * sizeof(double) + nr * nr * sizeof(float); }
-// work: tile_blur_work_bytes() of device memory (zeroed here); work[1] != 0 afterwards = a grid barrier timed out (never expected)
-void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work) {
-  if (step < 1 || k < 1) return;
-  // tiles: y = 0, step, ... while y+step < rows  (StitchTool.cpp:134-135)
-  int nty = 0, ntx = 0;
-  for (int y = 0; y + step < rows; y += step) ++nty;
-  for (int x = 0; x + step < cols; x += step) ++ntx;
-  if (nty <= 0 || ntx <= 0) return;
-  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
-  const int d = (reach + step - 1) / step, dskew = d + 1;
-  const size_t shmem = tile_blur_lds_bytes(step, k);
-  // large canvases need more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU)
-  if (shmem > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_blur), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-  hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
-  // every block must be resident (grid barrier): one block per CU at most, and no more than the longest diagonal has tiles
-  // (the CU count of the device this launch goes to -- contexts on different GPU models may live in one process -- and what the
-  // occupancy calculator says fits beside nothing else: a block that can never be resident would leave the others spinning)
+bool tile_blur_resident_fits(int step, int k) { return tile_blur_lds_bytes(step, k) <= 160 * 1024; }
+bool tile_blur_stream_ok(int step, int k) { return tile_stream_plan(step, k).ok(); }
+size_t tile_blur_scratch_bytes(int step, int k) { return tile_blur_resident_fits(step, k) ? 0 : tile_blur_stream_scratch_bytes(step, k); }
+size_t tile_blur_stream_scratch_bytes(int step, int k) { return tile_stream_plan(step, k).scratch_bytes * kTileStreamMaxBlocks; }
+namespace {
+// every block must be resident (grid barrier): one block per CU at most, and no more than the longest diagonal has tiles
+// (the CU count of the device this launch goes to -- contexts on different GPU models may live in one process -- and what the
+// occupancy calculator says fits beside nothing else: a block that can never be resident would leave the others spinning)
+// Few blocks: a diagonal rarely holds more than a dozen active tiles, a barrier among 32 blocks is cheaper than among 128, and
+// in pf_stitch_step this launch runs BESIDE the two flow solves, whose latency-bound sweeps should not share their CUs and
+// the L2 channel of the barrier word with a crowd of pollers.
+int tile_blur_blocks(const void* kernel, size_t shmem, int items) {
   int dev = 0, ncu = 64, per_cu = 1;
   if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_tile_blur), 256, shmem) != hipSuccess || per_cu < 1) per_cu = 1;
-  // Few blocks: a diagonal rarely holds more than a dozen active tiles, a barrier among 32 blocks is cheaper than among 128, and
-  // in pf_stitch_step this launch runs BESIDE the two flow solves, whose latency-bound sweeps should not share their CUs and
-  // the L2 channel of the barrier word with a crowd of pollers.
-  int blocks = nty < 32 ? nty : 32;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, shmem) != hipSuccess || per_cu < 1) per_cu = 1;
+  int blocks = items < kTileStreamMaxBlocks ? items : kTileStreamMaxBlocks;
   if (blocks > ncu * per_cu / 2) blocks = ncu * per_cu / 2;
-  if (blocks < 1) blocks = 1;
-  const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks: the launch may queue behind other work of the process
-  hipLaunchKernelGGL(k_tile_blur, dim3(blocks), dim3(256), shmem, st, blend, mergedDis, cols, rows, step, k, dskew, ntx, nty, static_cast<TileBlurWork*>(work), budget);
+  return blocks < 1 ? 1 : blocks;
+}
+struct TileGrid { int ntx = 0, nty = 0, dskew = 0; };
+// tiles: y = 0, step, ... while y+step < rows  (StitchTool.cpp:134-135)
+TileGrid tile_grid(int cols, int rows, int step, int k) {
+  TileGrid g;
+  for (int y = 0; y + step < rows; y += step) ++g.nty;
+  for (int x = 0; x + step < cols; x += step) ++g.ntx;
+  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
+  g.dskew = (reach + step - 1) / step + 1;
+  return g;
+}
+// The streamed form's geometries have long windows and short tiles: a diagonal t = tx + dskew*ty holds one tile per dskew tile
+// columns (four on a 400x26200 canvas), so the loose bound "tile rows" would set 32 blocks to a barrier that at most four have
+// work for.  Its time budget grows with the number of diagonals (13,000 tile rows of such a canvas make 670,000 of them, each
+// with a barrier of its own): 10 s, as the resident form has, plus 100 us per diagonal.
+int stream_items(const TileGrid& g) { const int span = (g.ntx - 1) / g.dskew + 1; return span < g.nty ? span : g.nty; }
+long long stream_budget(const TileGrid& g) { return 200000000ll * 5 + 10000ll * ((g.ntx - 1) + (long long)g.dskew * (g.nty - 1) + 1); }
+}  // namespace
+// work: tile_blur_work_bytes() of device memory (zeroed here); work[1] != 0 afterwards = a grid barrier timed out (never expected)
+// streamed: the form of d_tile_blur_one_streamed, with tile_blur_stream_scratch_bytes() of device memory at `scratch`
+void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work, bool streamed, void* scratch) {
+  if (step < 1 || k < 1) return;
+  const TileGrid g = tile_grid(cols, rows, step, k);
+  if (g.nty <= 0 || g.ntx <= 0) return;
+  hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
+  TileStreamArgs sa{};
+  if (!streamed) {
+    const size_t shmem = tile_blur_lds_bytes(step, k);
+    const void* kern = reinterpret_cast<const void*>(k_tile_blur<false>);
+    // large canvases need more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU)
+    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    const int blocks = tile_blur_blocks(kern, shmem, g.nty);
+    const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks: the launch may queue behind other work of the process
+    hipLaunchKernelGGL(k_tile_blur<false>, dim3(blocks), dim3(256), shmem, st, blend, mergedDis, cols, rows, step, k, g.dskew, g.ntx, g.nty,
+                       static_cast<TileBlurWork*>(work), budget, sa);
+  } else {
+    sa.plan = tile_stream_plan(step, k); sa.scratch = static_cast<double*>(scratch);
+    const size_t shmem = sa.plan.lds_bytes;
+    const void* kern = reinterpret_cast<const void*>(k_tile_blur<true>);
+    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    const int blocks = tile_blur_blocks(kern, shmem, stream_items(g));
+    hipLaunchKernelGGL(k_tile_blur<true>, dim3(blocks), dim3(256), shmem, st, blend, mergedDis, cols, rows, step, k, g.dskew, g.ntx, g.nty,
+                       static_cast<TileBlurWork*>(work), stream_budget(g), sa);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -676,12 +867,10 @@ void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols
 // (same size), so diagonal t of every frame is one diagonal of the launch: the per-diagonal active-tile counts are summed over
 // the frames, and the blocks walk the diagonals together exactly as k_tile_blur does for one canvas.  Frames share no pixels,
 // so the tiles of different frames on one diagonal are independent as well: the wavefront stays exact.
+template <bool kStream>
 __global__ __launch_bounds__(256) void k_tile_blur_batch(StitchPtrs p, int nf, int cols, int rows, int step, int k, int dskew, int ntx, int nty,
-                                                         TileBlurWork* __restrict__ wk, long long budget_ticks) {
+                                                         TileBlurWork* __restrict__ wk, long long budget_ticks, TileStreamArgs sa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-  const int nr = step + k - 1;
-  double* sm = reinterpret_cast<double*>(smraw);
-  float* win = reinterpret_cast<float*>(sm + size_t(nr) * step);
   const int tid = threadIdx.x, nblk = gridDim.x;
   const long long deadline = (long long)wall_clock64() + budget_ticks;
   const int tmax = (ntx - 1) + dskew * (nty - 1), ntiles = ntx * nty;
@@ -703,34 +892,37 @@ __global__ __launch_bounds__(256) void k_tile_blur_batch(StitchPtrs p, int nf, i
     for (int item = blockIdx.x; item < nf * span; item += nblk) {   // (frame, tile) items of this diagonal
       const int f = item / span, ty = ty_min + (item - f * span), tx = t - dskew * ty;
       if (tx < 0 || tx >= ntx || !active(f, tx, ty)) continue;   // block-uniform
-      d_tile_blur_one(p.blend[f], cols, rows, step, k, tx * step, ty * step, sm, win, scale);
+      d_tile_blur_tile<kStream>(p.blend[f], cols, rows, step, k, tx * step, ty * step, smraw, sa, scale);
     }
     ++phase;
     if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
   }
 }
-void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work) {
+void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed, void* scratch) {
   if (step < 1 || k < 1) return;
-  int nty = 0, ntx = 0;
-  for (int y = 0; y + step < rows; y += step) ++nty;
-  for (int x = 0; x + step < cols; x += step) ++ntx;
-  if (nty <= 0 || ntx <= 0) return;
-  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
-  const int dskew = (reach + step - 1) / step + 1;
-  const size_t shmem = tile_blur_lds_bytes(step, k);
-  if (shmem > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_blur_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  const TileGrid g = tile_grid(cols, rows, step, k);
+  if (g.nty <= 0 || g.ntx <= 0) return;
   hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
   // the grid-size rule of launch_tile_blur: every block resident (at most half of what fits on the device beside nothing else),
   // no more blocks than a diagonal has items -- here the items of all frames
-  int dev = 0, ncu = 64, per_cu = 1;
-  if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_tile_blur_batch), 256, shmem) != hipSuccess || per_cu < 1) per_cu = 1;
-  int blocks = nty * nf < 32 ? nty * nf : 32;
-  if (blocks > ncu * per_cu / 2) blocks = ncu * per_cu / 2;
-  if (blocks < 1) blocks = 1;
-  const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks
-  hipLaunchKernelGGL(k_tile_blur_batch, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, dskew, ntx, nty,
-                     static_cast<TileBlurWork*>(work), budget);
+  TileStreamArgs sa{};
+  if (!streamed) {
+    const size_t shmem = tile_blur_lds_bytes(step, k);
+    const void* kern = reinterpret_cast<const void*>(k_tile_blur_batch<false>);
+    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    const int blocks = tile_blur_blocks(kern, shmem, g.nty * nf);
+    const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks
+    hipLaunchKernelGGL(k_tile_blur_batch<false>, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, g.dskew, g.ntx, g.nty,
+                       static_cast<TileBlurWork*>(work), budget, sa);
+  } else {
+    sa.plan = tile_stream_plan(step, k); sa.scratch = static_cast<double*>(scratch);
+    const size_t shmem = sa.plan.lds_bytes;
+    const void* kern = reinterpret_cast<const void*>(k_tile_blur_batch<true>);
+    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    const int blocks = tile_blur_blocks(kern, shmem, stream_items(g) * nf);
+    hipLaunchKernelGGL(k_tile_blur_batch<true>, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, g.dskew, g.ntx, g.nty,
+                       static_cast<TileBlurWork*>(work), stream_budget(g), sa);
+  }
 }
 
 __global__ __launch_bounds__(256) void k_gather_batch(StitchPtrs p, int cols, int rows) {

@@ -165,6 +165,9 @@ pf_ctx* create_ctx(const pf_config& cfg, bool lane) {
         {"ch_l", n * 4}, {"ch_r", n * 4}, {"ch_final", n * 4}, {"st_map", n}, {"st_ovl", n * 4}, {"st_ovr", n * 4}, {"st_blend", n * 4}, {"st_md", n * 4},
         {"st_merged", n * 4}, {"st_rowsum", n * 8}, {"st_blur_tmp", n * 4}};
     for (const auto& e : io) if (ok2 && (!lane || strncmp(e.name, "nv_", 3) == 0)) ok2 = ensure(c, e.name, e.bytes) != nullptr;
+    // the streamed tile smoothing's row sums (canvases whose tile window exceeds the LDS of a CU; nothing for the others)
+    const int tstep = (max_cols <= max_rows ? max_cols : max_rows) / 200, tk = max_rows / 130;
+    if (ok2 && !lane && tstep > 0 && tk > 0 && tile_blur_scratch_bytes(tstep, tk) > 0) ok2 = ensure(c, "st_tile_scratch", tile_blur_scratch_bytes(tstep, tk)) != nullptr;
     if (!ok2) { g_err = c->err; pf_destroy(c); return nullptr; }
   }
   return c;

@@ -184,6 +184,27 @@ int pf_stage_blend_smooth(pf_ctx* c, float* blend, const float* md, int cols, in
   if (int e = stage_down(c, blend, db, n * 4)) return e;
   return check_sweeps(c);
 }
+// The tile pass of the ramp smoothing alone (StitchTool.cpp:134-141, without the final rows/400 blur) with the geometry given
+// explicitly: the kernel the stitch entry points use, on images small enough to check against the reference.
+// form: -1 = the library's choice, 0 = resident, 1 = streamed.
+int pf_stage_tile_blur(pf_ctx* c, float* blend, const float* md, int cols, int rows, int step, int k, int form) {
+  STAGE_BEGIN(c);
+  if (!blend || !md) return fail(c, PF_ERR_ARG, "null pointer");
+  if (int e = check_image(c, cols, rows)) return e;
+  if (step < 1 || k < 1 || form < -1 || form > 1) return fail(c, PF_ERR_ARG, "bad step / k / form");
+  if (step >= (cols < rows ? cols : rows)) return fail(c, PF_ERR_ARG, "step %d leaves no tile on a %dx%d canvas", step, cols, rows);
+  if (!tile_reach_ok(cols, rows, k)) return fail(c, PF_ERR_ARG, "window %d reaches across the whole %dx%d canvas", k, cols, rows);
+  const bool fits = tile_blur_resident_fits(step, k);
+  if (form == 0 && !fits) return fail(c, PF_ERR_ARG, "step %d, k %d: the resident form needs %zu bytes of LDS", step, k, tile_blur_lds_bytes(step, k));
+  const bool streamed = form < 0 ? !fits : form == 1;
+  if (streamed && !tile_blur_stream_ok(step, k)) return fail(c, PF_ERR_ARG, "step %d, k %d: one window row exceeds the streamed form's LDS piece", step, k);
+  const size_t n = size_t(cols) * rows;
+  float* db = (float*)stage_up(c, "st_blend", blend, n * 4); float* dmd = (float*)stage_up(c, "st_md", md, n * 4);
+  if (!db || !dmd) return PF_ERR_NOMEM;
+  if (int e = tile_blur_dev(c, sm, db, dmd, cols, rows, step, k, streamed)) return e;
+  if (int e = stage_down(c, blend, db, n * 4)) return e;
+  return check_sweeps(c);
+}
 
 // ---- profiling ----
 int pf_profile_enable(pf_ctx* c, int on) { if (!c) return PF_ERR_ARG; c->prof = on < 0 ? 0 : (on > 2 ? 1 : on); return 0; }

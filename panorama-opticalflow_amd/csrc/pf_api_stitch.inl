@@ -1,22 +1,42 @@
 // Part of pf_api.hip (one translation unit, split along its seams in round 5): Stitchtools: prepare / match / blend ramp / gather, the device-resident chain step and its prefetch.
 
-// The tile kernel keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS, step = min(cols, rows)/200, k1 = rows/130:
-// 160 KB per CU.  For canvases at least as wide as they are tall that bounds them at 12,000 rows (24000x12000 fits, 24500x12250
-// does not; 30000x15000 would need 250 KB); narrower canvases can have more rows.
-static bool blend_ramp_fits(int cols, int rows) {
+// The tile smoothing has two forms of one per-tile routine (kernels_misc.hip), step = min(cols, rows)/200, k1 = rows/130.  The
+// resident form keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS and serves every geometry that fits the 160 KB
+// of a CU (24000x12000 does, 24500x12250 does not; narrower canvases can have more rows); the streamed form takes the rest through
+// LDS in pieces (tile_stream_plan.hpp) and a per-block scratch area of the arena.  What is left out is what neither form's single-reflection
+// border addressing covers: a window that reaches across the whole canvas (canvases more than ~260 times taller than wide).
+static bool blend_ramp_fits(int cols, int rows) {   // the form selector: true = resident
   const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130;
-  return !(step > 0 && k1 > 0) || tile_blur_lds_bytes(step, k1) <= 160 * 1024;
+  return !(step > 0 && k1 > 0) || tile_blur_resident_fits(step, k1);
+}
+static bool tile_reach_ok(int cols, int rows, int k) {
+  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
+  return reach < (cols < rows ? cols : rows);
+}
+// refuses a canvas whose ramp neither form smooths (never one that was accepted before the streamed form existed)
+static int check_blend_ramp(pf_ctx* c, int cols, int rows) {
+  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130;
+  if (blend_ramp_fits(cols, rows)) return 0;
+  if (!tile_reach_ok(cols, rows, k1) || !tile_blur_stream_ok(step, k1))
+    return fail(c, PF_ERR_ARG, "canvas %dx%d: the blend-ramp smoothing window (%d) reaches across the whole canvas", cols, rows, k1);
+  return 0;
+}
+// the tile pass alone on device buffers, explicit geometry; st_/sb_ = the arena names of the single / batched step
+static int tile_blur_dev(pf_ctx* c, hipStream_t sm, float* d_blend, const float* d_md, int cols, int rows, int step, int k, bool streamed) {
+  void* work = ensure(c, "st_tile_work", tile_blur_work_bytes(cols, rows, step, k) + 256);
+  void* scratch = streamed ? ensure(c, "st_tile_scratch", tile_blur_stream_scratch_bytes(step, k)) : nullptr;
+  if (!work || (streamed && !scratch)) return PF_ERR_NOMEM;
+  { PROF(c, sm, "tile_blur"); launch_tile_blur(sm, d_blend, d_md, cols, rows, step, k, work, streamed, scratch); }
+  launch_collect_status(sm, static_cast<const int*>(work), 2, c->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
+  return 0;
 }
 
 static int blend_smooth_dev(pf_ctx* c, float* d_blend, const float* d_md, int cols, int rows, hipStream_t sm = nullptr) {
   const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130, k2 = rows / 400;
   if (!sm) sm = c->s_main;
   if (step > 0 && k1 > 0) {
-    if (!blend_ramp_fits(cols, rows)) return fail(c, PF_ERR_ARG, "canvas %dx%d too large for the blend-ramp tile smoothing (LDS)", cols, rows);
-    void* work = ensure(c, "st_tile_work", tile_blur_work_bytes(cols, rows, step, k1) + 256);
-    if (!work) return PF_ERR_NOMEM;
-    { PROF(c, sm, "tile_blur"); launch_tile_blur(sm, d_blend, d_md, cols, rows, step, k1, work); }
-    launch_collect_status(sm, static_cast<const int*>(work), 2, c->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
+    if (int e = check_blend_ramp(c, cols, rows)) return e;
+    if (int e = tile_blur_dev(c, sm, d_blend, d_md, cols, rows, step, k1, !blend_ramp_fits(cols, rows))) return e;
   }
   if (k2 > 0) {
     double* rs = (double*)ensure(c, "st_rowsum", size_t(cols) * rows * 8);
@@ -253,7 +273,7 @@ namespace {
 // everything pf_stitch_step refuses about the canvas, before any work
 int check_stitch_canvas(pf_ctx* c, int cols, int rows, int max_pct) {
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  if (!blend_ramp_fits(cols, rows)) return fail(c, PF_ERR_ARG, "canvas %dx%d too large for the blend-ramp tile smoothing (LDS)", cols, rows);
+  if (int e = check_blend_ramp(c, cols, rows)) return e;
   if (max_pct < 0 || max_pct > 100) return fail(c, PF_ERR_ARG, "max_percentage %d out of range", max_pct);
   return 0;
 }
@@ -305,9 +325,11 @@ int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, 
   HIPCHK(lane, hipStreamWaitEvent(sa, lane->ev_aux_go, 0));
   { PROF(lane, sa, "countblend"); launch_countblend_batch(sa, sp, count, cols, rows); }
   if (step > 0 && k1 > 0) {
+    const bool streamed = !blend_ramp_fits(cols, rows);
     void* work = ensure(lane, "sb_tile_work", tile_blur_work_bytes(cols, rows, step, k1) + 256);
-    if (!work) return PF_ERR_NOMEM;
-    { PROF(lane, sa, "tile_blur"); launch_tile_blur_batch(sa, sp, count, cols, rows, step, k1, work); }
+    void* scratch = streamed ? ensure(lane, "sb_tile_scratch", tile_blur_stream_scratch_bytes(step, k1)) : nullptr;
+    if (!work || (streamed && !scratch)) return PF_ERR_NOMEM;
+    { PROF(lane, sa, "tile_blur"); launch_tile_blur_batch(sa, sp, count, cols, rows, step, k1, work, streamed, scratch); }
     launch_collect_status(sa, static_cast<const int*>(work), 2, lane->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
   }
   if (k2 > 0) { PROF(lane, sa, "box_blur"); launch_box_blur_batch(sa, sp, count, cols, rows, k2); }   // the smoothed ramp lands in tmp

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "tile_stream_plan.hpp"
 
 namespace pf {
 
@@ -184,8 +185,13 @@ void launch_match_images(hipStream_t st, const uint8_t* L, const uint8_t* R, int
 void launch_countblend(hipStream_t st, const uint8_t* map, int cols, int rows, float* blend, float* mergedDis);
 void launch_box_blur(hipStream_t st, const float* src, float* dst, double* rowsum_tmp, int cols, int rows, int k);
 size_t tile_blur_work_bytes(int cols, int rows, int step, int k);   // device scratch of launch_tile_blur (diagonal counts + barrier word)
-size_t tile_blur_lds_bytes(int step, int k);
-void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work);
+size_t tile_blur_lds_bytes(int step, int k);           // dynamic LDS of the resident form (whole window + all row sums)
+bool tile_blur_resident_fits(int step, int k);          // ... within the 160 KB of a CU: the launchers' callers pick the form by this
+bool tile_blur_stream_ok(int step, int k);              // the streamed form has a plan (one window row fits its LDS piece)
+size_t tile_blur_scratch_bytes(int step, int k);        // device scratch of the form the library picks (0 for the resident form)
+size_t tile_blur_stream_scratch_bytes(int step, int k); // device scratch of the streamed form (row sums of every block's tile)
+void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work, bool streamed = false,
+                      void* scratch = nullptr);
 void launch_gather(hipStream_t st, const uint8_t* L, const uint8_t* R, const uint8_t* merged, const uint8_t* map, int cols, int rows,
                    uint8_t* out);
 int countblend_step(int cols, int rows);   // the probe stride of countblend (StitchTool.cpp:151), at least 1
@@ -199,7 +205,8 @@ struct StitchPtrs {
 };
 void launch_match_images_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);   // L, R -> map, ovL, ovR
 void launch_countblend_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
-void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work);   // blend in place; work as launch_tile_blur's
+void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed = false,
+                            void* scratch = nullptr);   // blend in place; work / streamed / scratch as launch_tile_blur's
 void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k); // blend -> tmp (rs: scratch)
 void launch_gather_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);         // L, R, merged, map -> out
 void launch_fill_u64(hipStream_t st, unsigned long long* p, size_t n, unsigned long long v, Batch bt = Batch());

@@ -98,7 +98,7 @@ EXPORTS = [
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
     "pf_stage_diffusion", "pf_stage_upsample_cubic", "pf_stage_final", "pf_stage_adjust_initial_flow", "pf_stage_level",
-    "pf_stage_blend_smooth",
+    "pf_stage_blend_smooth", "pf_stage_tile_blur",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
@@ -503,6 +503,15 @@ class Context:
     def stage_blend_smooth(self, blend, md):
         b = _f32(blend).copy(); rows, cols = b.shape
         self._chk(self.l.pf_stage_blend_smooth(self.h, _p(b), _p(_f32(md)), cols, rows))
+        return b
+
+    def stage_tile_blur(self, blend, md, step, k, form=-1):
+        """the tile pass of the ramp smoothing alone, explicit geometry; form -1 = the library's choice, 0 = resident, 1 = streamed"""
+        b = _f32(blend).copy(); rows, cols = b.shape
+        m = _f32(md)
+        if m.shape != b.shape:
+            raise ValueError("blend and merged_dis differ in shape")
+        self._chk(self.l.pf_stage_tile_blur(self.h, _p(b), _p(m), cols, rows, int(step), int(k), int(form)))
         return b
 
     def set_solver_params(self, **kw):
