@@ -229,30 +229,28 @@ __device__ __forceinline__ void d_blend_px(const uchar4* __restrict__ L, const u
   }
   out[i] = o;
 }
-__global__ __launch_bounds__(256) void k_blend(const uchar4* __restrict__ L, const uchar4* __restrict__ R, const float2* __restrict__ flowLR,
-                                               const float2* __restrict__ flowRL, const float* __restrict__ blend, int cols, int rows,
-                                               uchar4* __restrict__ out) {
-  d_blend_px(L, R, flowLR, flowRL, blend, cols, rows, out);
-}
-__global__ __launch_bounds__(256) void k_blend_batch(BlendPtrs p, int cols, int rows) {
+__global__ __launch_bounds__(256) void k_blend(BlendPtrs p, int cols, int rows) {
   const int z = blockIdx.z;
   d_blend_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), reinterpret_cast<const float2*>(p.fLR[z]),
              reinterpret_cast<const float2*>(p.fRL[z]), p.blend[z], cols, rows, reinterpret_cast<uchar4*>(p.out[z]));
 }
 // n pairs in one launch (blockIdx.z = pair): every buffer is caller-owned or per-pair, so the pointers come as tables
-void launch_blend_batch(hipStream_t st, const BlendPtrs& p, int n, int cols, int rows) {
+void launch_blend(hipStream_t st, const BlendPtrs& p, int n, int cols, int rows) {
   dim3 grid((cols + 255) / 256, rows, n);
-  hipLaunchKernelGGL(k_blend_batch, grid, dim3(256), 0, st, p, cols, rows);
+  hipLaunchKernelGGL(k_blend, grid, dim3(256), 0, st, p, cols, rows);
 }
 void launch_blend(hipStream_t st, const uint8_t* L, const uint8_t* R, const float* flowLR, const float* flowRL, const float* blend, int cols,
                   int rows, uint8_t* out) {
-  dim3 grid((cols + 255) / 256, rows);
-  hipLaunchKernelGGL(k_blend, grid, dim3(256), 0, st, reinterpret_cast<const uchar4*>(L), reinterpret_cast<const uchar4*>(R),
-                     reinterpret_cast<const float2*>(flowLR), reinterpret_cast<const float2*>(flowRL), blend, cols, rows, reinterpret_cast<uchar4*>(out));
+  BlendPtrs p{};
+  p.L[0] = L; p.R[0] = R; p.fLR[0] = flowLR; p.fRL[0] = flowRL; p.blend[0] = blend; p.out[0] = out;
+  launch_blend(st, p, 1, cols, rows);
 }
 
 // ------------------------------------------------------------------------------------------------
-// K12 MatchImages + overlap masking (StitchTool.cpp:17-33, :38-50)
+// K12-K15, the StitchTool kernels: one launch covers nf same-size canvases of independent stitch steps (a lone pf_stitch_step is
+// nf = 1 with a one-frame table).  Every per-frame buffer comes from a pointer table (StitchPtrs) and blockIdx.z is the frame.
+// ------------------------------------------------------------------------------------------------
+// K12 MatchImages + overlap masking (StitchTool.cpp:17-33, :38-50): L, R -> map, ovL, ovR
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void d_match_px(const uchar4* __restrict__ L, const uchar4* __restrict__ R, int n, uint8_t* __restrict__ map,
                                            uchar4* __restrict__ ovL, uchar4* __restrict__ ovR) {
@@ -265,14 +263,14 @@ __device__ __forceinline__ void d_match_px(const uchar4* __restrict__ L, const u
   ovL[i] = ov ? l : make_uchar4(0, 0, 0, 0);
   ovR[i] = ov ? r : make_uchar4(0, 0, 0, 0);
 }
-__global__ __launch_bounds__(256) void k_match_images(const uchar4* __restrict__ L, const uchar4* __restrict__ R, int n, uint8_t* __restrict__ map,
-                                                      uchar4* __restrict__ ovL, uchar4* __restrict__ ovR) {
-  d_match_px(L, R, n, map, ovL, ovR);
+__global__ __launch_bounds__(256) void k_match_images(StitchPtrs p, int n) {
+  const int z = blockIdx.z;
+  d_match_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), n, p.map[z], reinterpret_cast<uchar4*>(p.ovL[z]),
+             reinterpret_cast<uchar4*>(p.ovR[z]));
 }
-void launch_match_images(hipStream_t st, const uint8_t* L, const uint8_t* R, int cols, int rows, uint8_t* map, uint8_t* ovL, uint8_t* ovR) {
+void launch_match_images(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
   const int n = cols * rows;
-  hipLaunchKernelGGL(k_match_images, dim3((n + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uchar4*>(L), reinterpret_cast<const uchar4*>(R), n,
-                     map, reinterpret_cast<uchar4*>(ovL), reinterpret_cast<uchar4*>(ovR));
+  hipLaunchKernelGGL(k_match_images, dim3((n + 255) / 256, 1, nf), dim3(256), 0, st, p, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -315,17 +313,29 @@ __device__ __forceinline__ void d_countblend_px(const uint8_t* __restrict__ map,
   blend[size_t(y) * cols + x0] = b;
   mergedDis[size_t(y) * cols + x0] = md;
 }
-__global__ __launch_bounds__(256) void k_countblend(const uint8_t* __restrict__ map, int cols, int rows, int length, int step, float* __restrict__ blend,
-                                                    float* __restrict__ mergedDis) {
-  d_countblend_px(map, cols, rows, length, step, blend, mergedDis);
+__global__ __launch_bounds__(256) void k_countblend(StitchPtrs p, int cols, int rows, int length, int step) {
+  const int z = blockIdx.z;
+  d_countblend_px(p.map[z], cols, rows, length, step, p.blend[z], p.md[z]);
+}
+// The ramp's geometry (StitchTool.cpp:130-143, :151).  The tile smoothing has two forms of one per-tile routine: the resident form
+// keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS and serves every geometry that fits the 160 KB of a CU
+// (24000x12000 does, 24500x12250 does not; narrower canvases can have more rows); the streamed form takes the rest through LDS in
+// pieces (tile_stream_plan.hpp).  What is left out is what neither form's single-reflection border addressing covers: a window that
+// reaches across the whole canvas (canvases more than ~260 times taller than wide).
+RampGeom ramp_geom(int cols, int rows) {
+  RampGeom g;
+  g.step = (cols <= rows ? cols : rows) / 200; g.k1 = rows / 130; g.k2 = rows / 400;
+  g.tiles = g.step > 0 && g.k1 > 0;
+  g.streamed = g.tiles && !tile_blur_resident_fits(g.step, g.k1);
+  g.ok = !g.streamed || (tile_blur_reach(g.k1) < (cols < rows ? cols : rows) && tile_blur_stream_ok(g.step, g.k1));
+  return g;
 }
 int countblend_step(int cols, int rows) {
-  const int step = cols <= rows ? cols / 200 : rows / 200;
+  const int step = ramp_geom(cols, rows).step;
   return step < 1 ? 1 : step;   // reference never terminates for step==0 (inputs < 200 px); defined as 1
 }
-void launch_countblend(hipStream_t st, const uint8_t* map, int cols, int rows, float* blend, float* mergedDis) {
-  dim3 grid((cols + 255) / 256, rows);
-  hipLaunchKernelGGL(k_countblend, grid, dim3(256), 0, st, map, cols, rows, cols / 5, countblend_step(cols, rows), blend, mergedDis);
+void launch_countblend(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
+  hipLaunchKernelGGL(k_countblend, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows, cols / 5, countblend_step(cols, rows));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -348,8 +358,9 @@ __device__ __forceinline__ void d_box_rows_wide(const float* __restrict__ src, d
     rs[size_t(y) * cols + x] = s;
   }
 }
-__global__ __launch_bounds__(64) void k_box_rows_wide(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
-  d_box_rows_wide(src, rs, cols, rows, k);
+__global__ __launch_bounds__(64) void k_box_rows_wide(StitchPtrs p, int cols, int rows, int k) {
+  const int z = blockIdx.z;
+  d_box_rows_wide(p.blend[z], p.rs[z], cols, rows, k);
 }
 // Row pass.  A block owns 64 rows and walks them in chunks of 64 columns: the chunk (+ the k-1 taps beside it, reflected) is staged
 // in LDS with coalesced loads, lane y then advances ITS row's sliding sum through the chunk in the reference's order -- the
@@ -404,10 +415,11 @@ __device__ __forceinline__ void d_box_rows(const float* __restrict__ src, double
     // the next chunk's staging writes tin only (read by the walking wave before the barrier above); tout is rewritten after the next barrier
   }
 }
-__global__ __launch_bounds__(256) void k_box_rows(const float* __restrict__ src, double* __restrict__ rs, int cols, int rows, int k) {
+__global__ __launch_bounds__(256) void k_box_rows(StitchPtrs p, int cols, int rows, int k) {
   __shared__ float tin[kBoxR][kBoxC + kBoxKMax + 1];   // odd row stride: the 64 lanes (rows) of the walking wave hit different banks
   __shared__ double tout[kBoxR][kBoxC + 1];
-  d_box_rows(src, rs, cols, rows, k, tin, tout);
+  const int z = blockIdx.z;
+  d_box_rows(p.blend[z], p.rs[z], cols, rows, k, tin, tout);
 }
 // Column pass: lanes are adjacent columns (coalesced already); the two taps of the next 8 rows are loaded before the 8 dependent
 // updates, so that a wave has 16 loads in flight instead of one round trip per row.
@@ -437,13 +449,15 @@ __device__ __forceinline__ void d_box_cols(const double* __restrict__ rs, float*
     }
   }
 }
-__global__ __launch_bounds__(64) void k_box_cols(const double* __restrict__ rs, float* __restrict__ dst, int cols, int rows, int k) {
-  d_box_cols(rs, dst, cols, rows, k);
+__global__ __launch_bounds__(64) void k_box_cols(StitchPtrs p, int cols, int rows, int k) {
+  const int z = blockIdx.z;
+  d_box_cols(p.rs[z], p.tmp[z], cols, rows, k);
 }
-void launch_box_blur(hipStream_t st, const float* src, float* dst, double* rowsum_tmp, int cols, int rows, int k) {
-  if (k <= kBoxKMax) hipLaunchKernelGGL(k_box_rows, dim3((rows + kBoxR - 1) / kBoxR), dim3(256), 0, st, src, rowsum_tmp, cols, rows, k);
-  else hipLaunchKernelGGL(k_box_rows_wide, dim3((rows + 63) / 64), dim3(64), 0, st, src, rowsum_tmp, cols, rows, k);   // canvases beyond 13000 rows
-  hipLaunchKernelGGL(k_box_cols, dim3((cols + 63) / 64), dim3(64), 0, st, rowsum_tmp, dst, cols, rows, k);
+// blend -> tmp of every frame (each frame its own fp64 row sums rs)
+void launch_box_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k) {
+  if (k <= kBoxKMax) hipLaunchKernelGGL(k_box_rows, dim3((rows + kBoxR - 1) / kBoxR, 1, nf), dim3(256), 0, st, p, cols, rows, k);
+  else hipLaunchKernelGGL(k_box_rows_wide, dim3((rows + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);   // canvases beyond 13000 rows
+  hipLaunchKernelGGL(k_box_cols, dim3((cols + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);
 }
 
 // Conditional per-tile box blur, in place, raster order (StitchTool.cpp:134-141).  A tile reads the
@@ -675,18 +689,22 @@ __device__ __forceinline__ void d_tile_blur_tile(float* __restrict__ img, int co
     d_tile_blur_one(img, cols, rows, step, k, x0, y0, sm, win, scale);
   }
 }
+// ONE persistent launch smooths the tiles of all nf canvases.  The work item is (frame, tile); the frames have one tile grid (same
+// size), so diagonal t of every frame is one diagonal of the launch: the per-diagonal active-tile counts are summed over the
+// frames, and the blocks walk the diagonals together.  Frames share no pixels, so the tiles of different frames on one diagonal
+// are independent as well: the wavefront stays exact.
 template <bool kStream>
-__global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, const float* __restrict__ mergedDis, int cols, int rows, int step, int k,
-                                                   int dskew, int ntx, int nty, TileBlurWork* __restrict__ wk, long long budget_ticks, TileStreamArgs sa) {
+__global__ __launch_bounds__(256) void k_tile_blur(StitchPtrs p, int nf, int cols, int rows, int step, int k, int dskew, int ntx, int nty,
+                                                   TileBlurWork* __restrict__ wk, long long budget_ticks, TileStreamArgs sa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   const int tid = threadIdx.x, nblk = gridDim.x;
   const long long deadline = (long long)wall_clock64() + budget_ticks;
-  const int tmax = (ntx - 1) + dskew * (nty - 1);
-  auto active = [&](int tx, int ty) { return mergedDis[size_t(ty) * step * cols + size_t(tx) * step] > step; };
-  // pass 0: active tiles per diagonal
-  for (int i = blockIdx.x * 256 + tid; i < ntx * nty; i += nblk * 256) {
-    const int ty = i / ntx, tx = i - ty * ntx;
-    if (active(tx, ty)) __hip_atomic_fetch_add(&wk->cnt[tx + dskew * ty], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int tmax = (ntx - 1) + dskew * (nty - 1), ntiles = ntx * nty;
+  auto active = [&](int f, int tx, int ty) { return p.md[f][size_t(ty) * step * cols + size_t(tx) * step] > step; };
+  // pass 0: active tiles per diagonal, summed over the frames
+  for (int i = blockIdx.x * 256 + tid; i < nf * ntiles; i += nblk * 256) {
+    const int f = i / ntiles, r = i - f * ntiles, ty = r / ntx, tx = r - ty * ntx;
+    if (active(f, tx, ty)) __hip_atomic_fetch_add(&wk->cnt[tx + dskew * ty], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   int phase = 1;
   if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
@@ -696,32 +714,29 @@ __global__ __launch_bounds__(256) void k_tile_blur(float* __restrict__ img, cons
     const int lo = t - (ntx - 1);
     const int ty_min = lo > 0 ? (lo + dskew - 1) / dskew : 0;
     const int ty_max = t / dskew < nty - 1 ? t / dskew : nty - 1;
-    for (int ty = ty_min + blockIdx.x; ty <= ty_max; ty += nblk) {
-      const int tx = t - dskew * ty;
-      if (tx < 0 || tx >= ntx || !active(tx, ty)) continue;   // block-uniform
-      d_tile_blur_tile<kStream>(img, cols, rows, step, k, tx * step, ty * step, smraw, sa, scale);
+    const int span = ty_max - ty_min + 1;
+    for (int item = blockIdx.x; item < nf * span; item += nblk) {   // (frame, tile) items of this diagonal
+      const int f = item / span, ty = ty_min + (item - f * span), tx = t - dskew * ty;
+      if (tx < 0 || tx >= ntx || !active(f, tx, ty)) continue;   // block-uniform
+      d_tile_blur_tile<kStream>(p.blend[f], cols, rows, step, k, tx * step, ty * step, smraw, sa, scale);
     }
     ++phase;
     if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
   }
 }
-size_t tile_blur_work_bytes(int cols, int rows, int step, int k) {
-  if (step < 1 || k < 1) return 0;
-  int nty = 0, ntx = 0;
-  for (int y = 0; y + step < rows; y += step) ++nty;
-  for (int x = 0; x + step < cols; x += step) ++ntx;
-  if (nty <= 0 || ntx <= 0) return 0;
-  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
-  const int dskew = (reach + step - 1) / step + 1;
-  return sizeof(TileBlurWork) + sizeof(int) * size_t((ntx - 1) + dskew * (nty - 1) + 1);
-}
-size_t tile_blur_lds_bytes(int step, int k) { const size_t nr = size_t(step) + k - 1; return nr * step * sizeof(double) + nr * nr * sizeof(float); }
-bool tile_blur_resident_fits(int step, int k) { return tile_blur_lds_bytes(step, k) <= 160 * 1024; }
-bool tile_blur_stream_ok(int step, int k) { return tile_stream_plan(step, k).ok(); }
-size_t tile_blur_scratch_bytes(int step, int k) { return tile_blur_resident_fits(step, k) ? 0 : tile_blur_stream_scratch_bytes(step, k); }
-size_t tile_blur_stream_scratch_bytes(int step, int k) { return tile_stream_plan(step, k).scratch_bytes * kTileStreamMaxBlocks; }
+int tile_blur_reach(int k) { const int a = k / 2; return a > (k - 1 - a) ? a : (k - 1 - a); }
 namespace {
-// every block must be resident (grid barrier): one block per CU at most, and no more than the longest diagonal has tiles
+struct TileGrid { int ntx = 0, nty = 0, dskew = 0; };
+// tiles: y = 0, step, ... while y+step < rows  (StitchTool.cpp:134-135); step, k >= 1
+TileGrid tile_grid(int cols, int rows, int step, int k) {
+  TileGrid g;
+  for (int y = 0; y + step < rows; y += step) ++g.nty;
+  for (int x = 0; x + step < cols; x += step) ++g.ntx;
+  g.dskew = (tile_blur_reach(k) + step - 1) / step + 1;
+  return g;
+}
+int tile_diagonals(const TileGrid& g) { return (g.ntx - 1) + g.dskew * (g.nty - 1) + 1; }
+// every block must be resident (grid barrier): one block per CU at most, and no more than the longest diagonal has items
 // (the CU count of the device this launch goes to -- contexts on different GPU models may live in one process -- and what the
 // occupancy calculator says fits beside nothing else: a block that can never be resident would leave the others spinning)
 // Few blocks: a diagonal rarely holds more than a dozen active tiles, a barrier among 32 blocks is cheaper than among 128, and
@@ -735,49 +750,41 @@ int tile_blur_blocks(const void* kernel, size_t shmem, int items) {
   if (blocks > ncu * per_cu / 2) blocks = ncu * per_cu / 2;
   return blocks < 1 ? 1 : blocks;
 }
-struct TileGrid { int ntx = 0, nty = 0, dskew = 0; };
-// tiles: y = 0, step, ... while y+step < rows  (StitchTool.cpp:134-135)
-TileGrid tile_grid(int cols, int rows, int step, int k) {
-  TileGrid g;
-  for (int y = 0; y + step < rows; y += step) ++g.nty;
-  for (int x = 0; x + step < cols; x += step) ++g.ntx;
-  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
-  g.dskew = (reach + step - 1) / step + 1;
-  return g;
-}
 // The streamed form's geometries have long windows and short tiles: a diagonal t = tx + dskew*ty holds one tile per dskew tile
 // columns (four on a 400x26200 canvas), so the loose bound "tile rows" would set 32 blocks to a barrier that at most four have
 // work for.  Its time budget grows with the number of diagonals (13,000 tile rows of such a canvas make 670,000 of them, each
 // with a barrier of its own): 10 s, as the resident form has, plus 100 us per diagonal.
 int stream_items(const TileGrid& g) { const int span = (g.ntx - 1) / g.dskew + 1; return span < g.nty ? span : g.nty; }
-long long stream_budget(const TileGrid& g) { return 200000000ll * 5 + 10000ll * ((g.ntx - 1) + (long long)g.dskew * (g.nty - 1) + 1); }
 }  // namespace
-// work: tile_blur_work_bytes() of device memory (zeroed here); work[1] != 0 afterwards = a grid barrier timed out (never expected)
-// streamed: the form of d_tile_blur_one_streamed, with tile_blur_stream_scratch_bytes() of device memory at `scratch`
-void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work, bool streamed, void* scratch) {
-  if (step < 1 || k < 1) return;
+size_t tile_blur_work_bytes(int cols, int rows, int step, int k) {
+  if (step < 1 || k < 1) return 0;
   const TileGrid g = tile_grid(cols, rows, step, k);
-  if (g.nty <= 0 || g.ntx <= 0) return;
-  hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
+  if (g.nty <= 0 || g.ntx <= 0) return 0;
+  return sizeof(TileBlurWork) + sizeof(int) * size_t(tile_diagonals(g));
+}
+size_t tile_blur_lds_bytes(int step, int k) { const size_t nr = size_t(step) + k - 1; return nr * step * sizeof(double) + nr * nr * sizeof(float); }
+bool tile_blur_resident_fits(int step, int k) { return tile_blur_lds_bytes(step, k) <= 160 * 1024; }
+bool tile_blur_stream_ok(int step, int k) { return tile_stream_plan(step, k).ok(); }
+size_t tile_blur_stream_scratch_bytes(int step, int k) { return tile_stream_plan(step, k).scratch_bytes * kTileStreamMaxBlocks; }
+// p.blend of every frame in place, by p.md.  work: tile_blur_work_bytes() of device memory (zeroed here); work[1] != 0 afterwards =
+// a grid barrier timed out (never expected).  streamed: the form of d_tile_blur_one_streamed, with
+// tile_blur_stream_scratch_bytes() of device memory at `scratch`.
+void launch_tile_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed, void* scratch) {
+  const size_t work_bytes = tile_blur_work_bytes(cols, rows, step, k);
+  if (!work_bytes) return;   // no tile
+  const TileGrid g = tile_grid(cols, rows, step, k);
+  hipMemsetAsync(work, 0, work_bytes, st);
   TileStreamArgs sa{};
-  if (!streamed) {
-    const size_t shmem = tile_blur_lds_bytes(step, k);
-    const void* kern = reinterpret_cast<const void*>(k_tile_blur<false>);
-    // large canvases need more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU)
-    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    const int blocks = tile_blur_blocks(kern, shmem, g.nty);
-    const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks: the launch may queue behind other work of the process
-    hipLaunchKernelGGL(k_tile_blur<false>, dim3(blocks), dim3(256), shmem, st, blend, mergedDis, cols, rows, step, k, g.dskew, g.ntx, g.nty,
-                       static_cast<TileBlurWork*>(work), budget, sa);
-  } else {
-    sa.plan = tile_stream_plan(step, k); sa.scratch = static_cast<double*>(scratch);
-    const size_t shmem = sa.plan.lds_bytes;
-    const void* kern = reinterpret_cast<const void*>(k_tile_blur<true>);
-    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    const int blocks = tile_blur_blocks(kern, shmem, stream_items(g));
-    hipLaunchKernelGGL(k_tile_blur<true>, dim3(blocks), dim3(256), shmem, st, blend, mergedDis, cols, rows, step, k, g.dskew, g.ntx, g.nty,
-                       static_cast<TileBlurWork*>(work), stream_budget(g), sa);
-  }
+  if (streamed) { sa.plan = tile_stream_plan(step, k); sa.scratch = static_cast<double*>(scratch); }
+  const auto kern = streamed ? k_tile_blur<true> : k_tile_blur<false>;
+  const size_t shmem = streamed ? sa.plan.lds_bytes : tile_blur_lds_bytes(step, k);
+  // large canvases need more than the default 64 KB of dynamic LDS (gfx950 has 160 KB per CU)
+  if (shmem > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  const int blocks = tile_blur_blocks(reinterpret_cast<const void*>(kern), shmem, (streamed ? stream_items(g) : g.nty) * nf);
+  // 10 s of 100 MHz ticks: the launch may queue behind other work of the process
+  const long long budget = 200000000ll * 5 + (streamed ? 10000ll * tile_diagonals(g) : 0);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, g.dskew, g.ntx, g.nty, static_cast<TileBlurWork*>(work),
+                     budget, sa);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -811,127 +818,13 @@ __device__ __forceinline__ void d_gather_px(const uchar4* __restrict__ L, const 
   }
   out[i] = o;
 }
-__global__ __launch_bounds__(256) void k_gather(const uchar4* __restrict__ L, const uchar4* __restrict__ R, const uchar4* __restrict__ merged,
-                                                const uint8_t* __restrict__ map, int cols, int rows, uchar4* __restrict__ out) {
-  d_gather_px(L, R, merged, map, cols, rows, out);
-}
-void launch_gather(hipStream_t st, const uint8_t* L, const uint8_t* R, const uint8_t* merged, const uint8_t* map, int cols, int rows, uint8_t* out) {
-  dim3 grid((cols + 255) / 256, rows);
-  hipLaunchKernelGGL(k_gather, grid, dim3(256), 0, st, reinterpret_cast<const uchar4*>(L), reinterpret_cast<const uchar4*>(R),
-                     reinterpret_cast<const uchar4*>(merged), map, cols, rows, reinterpret_cast<uchar4*>(out));
-}
-
-// ------------------------------------------------------------------------------------------------
-// K12-K15 batched: n same-size canvases of independent stitch steps in one launch each (pf_stitch_step_batch*).  Every
-// per-frame buffer comes from a pointer table (StitchPtrs); blockIdx.z is the frame, and the arithmetic per pixel is the
-// single-canvas kernels' own (the same device functions).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_match_images_batch(StitchPtrs p, int n) {
-  const int z = blockIdx.z;
-  d_match_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), n, p.map[z], reinterpret_cast<uchar4*>(p.ovL[z]),
-             reinterpret_cast<uchar4*>(p.ovR[z]));
-}
-void launch_match_images_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
-  const int n = cols * rows;
-  hipLaunchKernelGGL(k_match_images_batch, dim3((n + 255) / 256, 1, nf), dim3(256), 0, st, p, n);
-}
-__global__ __launch_bounds__(256) void k_countblend_batch(StitchPtrs p, int cols, int rows, int length, int step) {
-  const int z = blockIdx.z;
-  d_countblend_px(p.map[z], cols, rows, length, step, p.blend[z], p.md[z]);
-}
-void launch_countblend_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
-  hipLaunchKernelGGL(k_countblend_batch, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows, cols / 5, countblend_step(cols, rows));
-}
-__global__ __launch_bounds__(64) void k_box_rows_wide_batch(StitchPtrs p, int cols, int rows, int k) {
-  const int z = blockIdx.z;
-  d_box_rows_wide(p.blend[z], p.rs[z], cols, rows, k);
-}
-__global__ __launch_bounds__(256) void k_box_rows_batch(StitchPtrs p, int cols, int rows, int k) {
-  __shared__ float tin[kBoxR][kBoxC + kBoxKMax + 1];
-  __shared__ double tout[kBoxR][kBoxC + 1];
-  const int z = blockIdx.z;
-  d_box_rows(p.blend[z], p.rs[z], cols, rows, k, tin, tout);
-}
-__global__ __launch_bounds__(64) void k_box_cols_batch(StitchPtrs p, int cols, int rows, int k) {
-  const int z = blockIdx.z;
-  d_box_cols(p.rs[z], p.tmp[z], cols, rows, k);
-}
-// blend -> tmp of every frame (each frame its own fp64 row sums rs)
-void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k) {
-  if (k <= kBoxKMax) hipLaunchKernelGGL(k_box_rows_batch, dim3((rows + kBoxR - 1) / kBoxR, 1, nf), dim3(256), 0, st, p, cols, rows, k);
-  else hipLaunchKernelGGL(k_box_rows_wide_batch, dim3((rows + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);
-  hipLaunchKernelGGL(k_box_cols_batch, dim3((cols + 63) / 64, 1, nf), dim3(64), 0, st, p, cols, rows, k);
-}
-
-// The tile smoothing of nf canvases as ONE persistent launch.  The work item is (frame, tile); the frames have one tile grid
-// (same size), so diagonal t of every frame is one diagonal of the launch: the per-diagonal active-tile counts are summed over
-// the frames, and the blocks walk the diagonals together exactly as k_tile_blur does for one canvas.  Frames share no pixels,
-// so the tiles of different frames on one diagonal are independent as well: the wavefront stays exact.
-template <bool kStream>
-__global__ __launch_bounds__(256) void k_tile_blur_batch(StitchPtrs p, int nf, int cols, int rows, int step, int k, int dskew, int ntx, int nty,
-                                                         TileBlurWork* __restrict__ wk, long long budget_ticks, TileStreamArgs sa) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
-  const int tid = threadIdx.x, nblk = gridDim.x;
-  const long long deadline = (long long)wall_clock64() + budget_ticks;
-  const int tmax = (ntx - 1) + dskew * (nty - 1), ntiles = ntx * nty;
-  auto active = [&](int f, int tx, int ty) { return p.md[f][size_t(ty) * step * cols + size_t(tx) * step] > step; };
-  // pass 0: active tiles per diagonal, summed over the frames
-  for (int i = blockIdx.x * 256 + tid; i < nf * ntiles; i += nblk * 256) {
-    const int f = i / ntiles, r = i - f * ntiles, ty = r / ntx, tx = r - ty * ntx;
-    if (active(f, tx, ty)) __hip_atomic_fetch_add(&wk->cnt[tx + dskew * ty], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  int phase = 1;
-  if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
-  const double scale = 1. / ((double)k * k);
-  for (int t = 0; t <= tmax; ++t) {
-    if (__hip_atomic_load(&wk->cnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) continue;   // the same answer in every block
-    const int lo = t - (ntx - 1);
-    const int ty_min = lo > 0 ? (lo + dskew - 1) / dskew : 0;
-    const int ty_max = t / dskew < nty - 1 ? t / dskew : nty - 1;
-    const int span = ty_max - ty_min + 1;
-    for (int item = blockIdx.x; item < nf * span; item += nblk) {   // (frame, tile) items of this diagonal
-      const int f = item / span, ty = ty_min + (item - f * span), tx = t - dskew * ty;
-      if (tx < 0 || tx >= ntx || !active(f, tx, ty)) continue;   // block-uniform
-      d_tile_blur_tile<kStream>(p.blend[f], cols, rows, step, k, tx * step, ty * step, smraw, sa, scale);
-    }
-    ++phase;
-    if (!d_grid_barrier(&wk->bar, &wk->err, phase * nblk, deadline)) return;
-  }
-}
-void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed, void* scratch) {
-  if (step < 1 || k < 1) return;
-  const TileGrid g = tile_grid(cols, rows, step, k);
-  if (g.nty <= 0 || g.ntx <= 0) return;
-  hipMemsetAsync(work, 0, tile_blur_work_bytes(cols, rows, step, k), st);
-  // the grid-size rule of launch_tile_blur: every block resident (at most half of what fits on the device beside nothing else),
-  // no more blocks than a diagonal has items -- here the items of all frames
-  TileStreamArgs sa{};
-  if (!streamed) {
-    const size_t shmem = tile_blur_lds_bytes(step, k);
-    const void* kern = reinterpret_cast<const void*>(k_tile_blur_batch<false>);
-    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    const int blocks = tile_blur_blocks(kern, shmem, g.nty * nf);
-    const long long budget = 200000000ll * 5;   // 10 s of 100 MHz ticks
-    hipLaunchKernelGGL(k_tile_blur_batch<false>, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, g.dskew, g.ntx, g.nty,
-                       static_cast<TileBlurWork*>(work), budget, sa);
-  } else {
-    sa.plan = tile_stream_plan(step, k); sa.scratch = static_cast<double*>(scratch);
-    const size_t shmem = sa.plan.lds_bytes;
-    const void* kern = reinterpret_cast<const void*>(k_tile_blur_batch<true>);
-    if (shmem > 48 * 1024) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    const int blocks = tile_blur_blocks(kern, shmem, stream_items(g) * nf);
-    hipLaunchKernelGGL(k_tile_blur_batch<true>, dim3(blocks), dim3(256), shmem, st, p, nf, cols, rows, step, k, g.dskew, g.ntx, g.nty,
-                       static_cast<TileBlurWork*>(work), stream_budget(g), sa);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gather_batch(StitchPtrs p, int cols, int rows) {
+__global__ __launch_bounds__(256) void k_gather(StitchPtrs p, int cols, int rows) {
   const int z = blockIdx.z;
   d_gather_px(reinterpret_cast<const uchar4*>(p.L[z]), reinterpret_cast<const uchar4*>(p.R[z]), reinterpret_cast<const uchar4*>(p.merged[z]),
               p.map[z], cols, rows, reinterpret_cast<uchar4*>(p.out[z]));
 }
-void launch_gather_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
-  hipLaunchKernelGGL(k_gather_batch, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows);
+void launch_gather(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows) {
+  hipLaunchKernelGGL(k_gather, dim3((cols + 255) / 256, rows, nf), dim3(256), 0, st, p, cols, rows);
 }
 
 }  // namespace pf

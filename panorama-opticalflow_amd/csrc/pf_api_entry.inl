@@ -79,7 +79,7 @@ int novel_view_group(pf_ctx* lane, int first, int count, const uint8_t* const* d
   if (int e = solve_n(lane, count, d_l + first, d_r + first, cols, rows, cols / 20, max_pct, 2, hints, outs, used)) return e;
   BlendPtrs bp{};
   for (int p = 0; p < count; ++p) { bp.L[p] = d_l[first + p]; bp.R[p] = d_r[first + p]; bp.fLR[p] = used[2 * p]; bp.fRL[p] = used[2 * p + 1]; bp.blend[p] = d_blend[first + p]; bp.out[p] = d_out[first + p]; }
-  { PROF(lane, lane->s_main, "blend"); launch_blend_batch(lane->s_main, bp, count, cols, rows); }
+  { PROF(lane, lane->s_main, "blend"); launch_blend(lane->s_main, bp, count, cols, rows); }
   HIPCHK(lane, hipGetLastError());
   if (int e = finish(lane)) return e;
   return check_sweeps(lane);

@@ -166,8 +166,8 @@ pf_ctx* create_ctx(const pf_config& cfg, bool lane) {
         {"st_merged", n * 4}, {"st_rowsum", n * 8}, {"st_blur_tmp", n * 4}};
     for (const auto& e : io) if (ok2 && (!lane || strncmp(e.name, "nv_", 3) == 0)) ok2 = ensure(c, e.name, e.bytes) != nullptr;
     // the streamed tile smoothing's row sums (canvases whose tile window exceeds the LDS of a CU; nothing for the others)
-    const int tstep = (max_cols <= max_rows ? max_cols : max_rows) / 200, tk = max_rows / 130;
-    if (ok2 && !lane && tstep > 0 && tk > 0 && tile_blur_scratch_bytes(tstep, tk) > 0) ok2 = ensure(c, "st_tile_scratch", tile_blur_scratch_bytes(tstep, tk)) != nullptr;
+    const RampGeom rg = ramp_geom(max_cols, max_rows);
+    if (ok2 && !lane && rg.streamed && tile_blur_stream_scratch_bytes(rg.step, rg.k1) > 0) ok2 = ensure(c, "st_tile_scratch", tile_blur_stream_scratch_bytes(rg.step, rg.k1)) != nullptr;
     if (!ok2) { g_err = c->err; pf_destroy(c); return nullptr; }
   }
   return c;

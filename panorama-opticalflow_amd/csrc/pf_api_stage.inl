@@ -180,8 +180,13 @@ int pf_stage_blend_smooth(pf_ctx* c, float* blend, const float* md, int cols, in
   const size_t n = size_t(cols) * rows;
   float* db = (float*)stage_up(c, "st_blend", blend, n * 4); float* dmd = (float*)stage_up(c, "st_md", md, n * 4);
   if (!db || !dmd) return PF_ERR_NOMEM;
-  if (int e = blend_smooth_dev(c, db, dmd, cols, rows)) return e;
-  if (int e = stage_down(c, blend, db, n * 4)) return e;
+  const RampGeom g = ramp_geom(cols, rows);
+  StitchPtrs p{}; p.blend[0] = db; p.md[0] = dmd;
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
+  const float* ramp = nullptr;
+  if (int e = blend_ramp_dev(c, sm, p, 1, cols, rows, g, w, false, &ramp)) return e;
+  if (int e = stage_down(c, blend, ramp, n * 4)) return e;
   return check_sweeps(c);
 }
 // The tile pass of the ramp smoothing alone (StitchTool.cpp:134-141, without the final rows/400 blur) with the geometry given

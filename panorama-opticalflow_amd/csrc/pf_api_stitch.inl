@@ -1,51 +1,89 @@
 // Part of pf_api.hip (one translation unit, split along its seams in round 5): Stitchtools: prepare / match / blend ramp / gather, the device-resident chain step and its prefetch.
 
-// The tile smoothing has two forms of one per-tile routine (kernels_misc.hip), step = min(cols, rows)/200, k1 = rows/130.  The
-// resident form keeps a (step+k1-1)^2 window and (step+k1-1) x step row sums in LDS and serves every geometry that fits the 160 KB
-// of a CU (24000x12000 does, 24500x12250 does not; narrower canvases can have more rows); the streamed form takes the rest through
-// LDS in pieces (tile_stream_plan.hpp) and a per-block scratch area of the arena.  What is left out is what neither form's single-reflection
-// border addressing covers: a window that reaches across the whole canvas (canvases more than ~260 times taller than wide).
-static bool blend_ramp_fits(int cols, int rows) {   // the form selector: true = resident
-  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130;
-  return !(step > 0 && k1 > 0) || tile_blur_resident_fits(step, k1);
+// The ramp's geometry is ramp_geom()'s (kernels_misc.hip), computed once per call.
+static bool tile_reach_ok(int cols, int rows, int k) { return tile_blur_reach(k) < (cols < rows ? cols : rows); }
+// refuses a canvas whose ramp neither form of the tile smoothing covers (never one that was accepted before the streamed form existed)
+static int check_blend_ramp(pf_ctx* c, int cols, int rows, const RampGeom& g) {
+  if (g.ok) return 0;
+  return fail(c, PF_ERR_ARG, "canvas %dx%d: the blend-ramp smoothing window (%d) reaches across the whole canvas", cols, rows, g.k1);
 }
-static bool tile_reach_ok(int cols, int rows, int k) {
-  const int a = k / 2, reach = a > (k - 1 - a) ? a : (k - 1 - a);
-  return reach < (cols < rows ? cols : rows);
+namespace {
+// per-frame planes of a group, `count` frames back to back in one arena buffer (256-byte aligned frames)
+extern "C++" template <class T> T* frame_planes(pf_ctx* c, const char* name, int count, size_t per_frame, size_t& stride) {
+  stride = (per_frame + 255) & ~size_t(255);
+  return (T*)ensure(c, name, stride * count);
 }
-// refuses a canvas whose ramp neither form smooths (never one that was accepted before the streamed form existed)
-static int check_blend_ramp(pf_ctx* c, int cols, int rows) {
-  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130;
-  if (blend_ramp_fits(cols, rows)) return 0;
-  if (!tile_reach_ok(cols, rows, k1) || !tile_blur_stream_ok(step, k1))
-    return fail(c, PF_ERR_ARG, "canvas %dx%d: the blend-ramp smoothing window (%d) reaches across the whole canvas", cols, rows, k1);
-  return 0;
-}
-// the tile pass alone on device buffers, explicit geometry; st_/sb_ = the arena names of the single / batched step
-static int tile_blur_dev(pf_ctx* c, hipStream_t sm, float* d_blend, const float* d_md, int cols, int rows, int step, int k, bool streamed) {
-  void* work = ensure(c, "st_tile_work", tile_blur_work_bytes(cols, rows, step, k) + 256);
-  void* scratch = streamed ? ensure(c, "st_tile_scratch", tile_blur_stream_scratch_bytes(step, k)) : nullptr;
-  if (!work || (streamed && !scratch)) return PF_ERR_NOMEM;
-  { PROF(c, sm, "tile_blur"); launch_tile_blur(sm, d_blend, d_md, cols, rows, step, k, work, streamed, scratch); }
-  launch_collect_status(sm, static_cast<const int*>(work), 2, c->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
-  return 0;
-}
-
-static int blend_smooth_dev(pf_ctx* c, float* d_blend, const float* d_md, int cols, int rows, hipStream_t sm = nullptr) {
-  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130, k2 = rows / 400;
-  if (!sm) sm = c->s_main;
-  if (step > 0 && k1 > 0) {
-    if (int e = check_blend_ramp(c, cols, rows)) return e;
-    if (int e = tile_blur_dev(c, sm, d_blend, d_md, cols, rows, step, k1, !blend_ramp_fits(cols, rows))) return e;
+}  // namespace
+// What the ramp of `count` frames needs beside blend / md: the tile pass's work area and (streamed form) row sums, the box blur's
+// fp64 row sums and result planes (p.rs / p.tmp).  From the arena buffers named here: the lone entry points' (pre-sized by
+// pf_create) or the batched step's.
+struct RampArena { const char* work; const char* scratch; const char* rowsum; const char* blur_tmp; };
+static const RampArena kRampLone = {"st_tile_work", "st_tile_scratch", "st_rowsum", "st_blur_tmp"}, kRampBatch = {"sb_tile_work", "sb_tile_scratch", "sb_rowsum", "sb_blur_tmp"};
+struct RampWork { void* work = nullptr; void* scratch = nullptr; };
+static int ramp_planes(pf_ctx* c, const RampArena& a, int count, int cols, int rows, const RampGeom& g, StitchPtrs& p, RampWork& w) {
+  if (!g.ok) return 0;   // blend_ramp_dev refuses the canvas
+  const size_t n = size_t(cols) * rows;
+  if (g.tiles) {
+    w.work = ensure(c, a.work, tile_blur_work_bytes(cols, rows, g.step, g.k1) + 256);
+    if (g.streamed) w.scratch = ensure(c, a.scratch, tile_blur_stream_scratch_bytes(g.step, g.k1));
+    if (!w.work || (g.streamed && !w.scratch)) return PF_ERR_NOMEM;
   }
-  if (k2 > 0) {
-    double* rs = (double*)ensure(c, "st_rowsum", size_t(cols) * rows * 8);
-    float* tmp = (float*)ensure(c, "st_blur_tmp", size_t(cols) * rows * 4);
+  if (g.k2 > 0) {
+    size_t s8, s4;
+    double* rs = frame_planes<double>(c, a.rowsum, count, n * 8, s8); float* tmp = frame_planes<float>(c, a.blur_tmp, count, n * 4, s4);
     if (!rs || !tmp) return PF_ERR_NOMEM;
-    PROF(c, sm, "box_blur");
-    launch_box_blur(sm, d_blend, tmp, rs, cols, rows, k2);
-    HIPCHK(c, hipMemcpyAsync(d_blend, tmp, size_t(cols) * rows * 4, hipMemcpyDeviceToDevice, sm));
+    for (int f = 0; f < count; ++f) { p.rs[f] = (double*)((char*)rs + f * s8); p.tmp[f] = (float*)((char*)tmp + f * s4); }
   }
+  return 0;
+}
+// the tile pass alone: p.blend of `count` frames in place, explicit geometry
+static void tile_pass_dev(pf_ctx* c, hipStream_t sm, const StitchPtrs& p, int count, int cols, int rows, int step, int k, bool streamed, const RampWork& w) {
+  { PROF(c, sm, "tile_blur"); launch_tile_blur(sm, p, count, cols, rows, step, k, w.work, streamed, w.scratch); }
+  launch_collect_status(sm, static_cast<const int*>(w.work), 2, c->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
+}
+// ... of one canvas on the lone entry points' arena buffers (pf_stage_tile_blur)
+static int tile_blur_dev(pf_ctx* c, hipStream_t sm, float* d_blend, float* d_md, int cols, int rows, int step, int k, bool streamed) {
+  RampGeom g; g.step = step; g.k1 = k; g.tiles = true; g.streamed = streamed;
+  StitchPtrs p{}; p.blend[0] = d_blend; p.md[0] = d_md;
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
+  tile_pass_dev(c, sm, p, 1, cols, rows, step, k, streamed, w);
+  return 0;
+}
+// The blend ramp of `count` frames on stream sm (GenerateBlend + countblend + smoothing, StitchTool.cpp:98-191): countblend from
+// p.map (from_map; otherwise p.blend / p.md are given), the tile pass in place, its status word, the rows/400 box blur into p.tmp.
+// ramp[f] = where frame f's finished ramp lies: p.tmp[f] if the box blur ran, else p.blend[f].
+static int blend_ramp_dev(pf_ctx* c, hipStream_t sm, const StitchPtrs& p, int count, int cols, int rows, const RampGeom& g, const RampWork& w, bool from_map,
+                          const float** ramp) {
+  if (int e = check_blend_ramp(c, cols, rows, g)) return e;
+  if (from_map) { PROF(c, sm, "countblend"); launch_countblend(sm, p, count, cols, rows); }
+  if (g.tiles) tile_pass_dev(c, sm, p, count, cols, rows, g.step, g.k1, g.streamed, w);
+  if (g.k2 > 0) { PROF(c, sm, "box_blur"); launch_box_blur(sm, p, count, cols, rows, g.k2); }
+  for (int f = 0; f < count; ++f) ramp[f] = g.k2 > 0 ? p.tmp[f] : p.blend[f];
+  return 0;
+}
+// One iteration of the reference's stitch loop (CPU/main.cpp:70-95) for `count` frames on device planes the caller supplies (p: all
+// but L / R / out are working planes; w and p.rs / p.tmp from ramp_planes; flows[2f], flows[2f + 1]: frame f's two flow planes):
+// Stitchtools::prepare -> NovelViewGeneratorAsymmetricFlow::prepare/generateNovelView -> Gather, enqueued, not drained.
+static int stitch_step_dev(pf_ctx* c, const StitchPtrs& p, int count, float* const* flows, int cols, int rows, int max_pct, const RampGeom& g, const RampWork& w) {
+  hipStream_t sm = c->s_main;
+  { PROF(c, sm, "match_images"); launch_match_images(sm, p, count, cols, rows); }
+  // The blend ramp only depends on the map and is only needed by the final blend: it runs on its own stream beside the two flow
+  // solves.  Its launches (a dozen since the tile smoothing became ONE persistent launch in round 3; ~850 before) are enqueued AFTER
+  // the solver's, so that the solver's first kernel is not kept waiting by them.
+  if (!c->s_aux) HIPCHK(c, hipStreamCreateWithFlags(&c->s_aux, hipStreamNonBlocking));
+  hipStream_t sa = c->s_aux;
+  HIPCHK(c, hipEventRecord(c->ev_aux_go, sm));
+  const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT};
+  if (int e = solve_n(c, count, p.ovL, p.ovR, cols, rows, cols / 20, max_pct, 2, hints, flows)) return e;
+  HIPCHK(c, hipStreamWaitEvent(sa, c->ev_aux_go, 0));
+  BlendPtrs bp{};
+  if (int e = blend_ramp_dev(c, sa, p, count, cols, rows, g, w, true, bp.blend)) return e;
+  HIPCHK(c, hipEventRecord(c->ev_aux_done, sa));
+  HIPCHK(c, hipStreamWaitEvent(sm, c->ev_aux_done, 0));
+  for (int f = 0; f < count; ++f) { bp.L[f] = p.ovL[f]; bp.R[f] = p.ovR[f]; bp.fLR[f] = flows[2 * f]; bp.fRL[f] = flows[2 * f + 1]; bp.out[f] = p.merged[f]; }
+  { PROF(c, sm, "blend"); launch_blend(sm, bp, count, cols, rows); }
+  { PROF(c, sm, "gather"); launch_gather(sm, p, count, cols, rows); }
   return 0;
 }
 
@@ -61,16 +99,20 @@ int pf_stitch_prepare(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, i
   uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
   float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
   if (!dl || !dr || !dm || !dol || !dor || !db || !dmd) return PF_ERR_NOMEM;
+  const RampGeom g = ramp_geom(cols, rows);
+  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd;
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   hipStream_t sm = c->s_main;
   if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
   if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  { PROF(c, sm, "match_images"); launch_match_images(sm, dl, dr, cols, rows, dm, dol, dor); }
-  { PROF(c, sm, "countblend"); launch_countblend(sm, dm, cols, rows, db, dmd); }
-  if (int e = blend_smooth_dev(c, db, dmd, cols, rows)) return e;
+  { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
+  const float* ramp = nullptr;
+  if (int e = blend_ramp_dev(c, sm, p, 1, cols, rows, g, w, true, &ramp)) return e;
   if (map_out) if (int e = down2d(c, map_out, mstep, dm, cols, cols, rows)) return e;
   if (ovl) if (int e = down2d(c, ovl, step, dol, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   if (ovr) if (int e = down2d(c, ovr, step, dor, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (blend_out) if (int e = down2d(c, blend_out, bstep, db, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (blend_out) if (int e = down2d(c, blend_out, bstep, ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
@@ -90,7 +132,8 @@ int pf_stitch_match(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int
   if (!dl || !dr || !dm || !dol || !dor) return PF_ERR_NOMEM;
   if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
   if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  { PROF(c, c->s_main, "match_images"); launch_match_images(c->s_main, dl, dr, cols, rows, dm, dol, dor); }
+  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor;
+  { PROF(c, c->s_main, "match_images"); launch_match_images(c->s_main, p, 1, cols, rows); }
   if (map_out) if (int e = down2d(c, map_out, mstep, dm, cols, cols, rows)) return e;
   if (ovl) if (int e = down2d(c, ovl, step, dol, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   if (ovr) if (int e = down2d(c, ovr, step, dor, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
@@ -109,10 +152,14 @@ int pf_stitch_generate_blend(pf_ctx* c, const uint8_t* map, size_t mstep, int co
   const size_t n = size_t(cols) * rows;
   uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
   if (!dm || !db || !dmd) return PF_ERR_NOMEM;
+  const RampGeom g = ramp_geom(cols, rows);
+  StitchPtrs p{}; p.map[0] = dm; p.blend[0] = db; p.md[0] = dmd;
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   if (int e = up2d(c, dm, cols, map, mstep, cols, rows)) return e;
-  { PROF(c, c->s_main, "countblend"); launch_countblend(c->s_main, dm, cols, rows, db, dmd); }
-  if (int e = blend_smooth_dev(c, db, dmd, cols, rows)) return e;
-  if (int e = down2d(c, blend_out, bstep, db, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  const float* ramp = nullptr;
+  if (int e = blend_ramp_dev(c, c->s_main, p, 1, cols, rows, g, w, true, &ramp)) return e;
+  if (int e = down2d(c, blend_out, bstep, ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
@@ -135,8 +182,9 @@ int pf_stitch_raw_blend(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols,
   hipStream_t sm = c->s_main;
   if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
   if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  { PROF(c, sm, "match_images"); launch_match_images(sm, dl, dr, cols, rows, dm, dol, dor); }
-  { PROF(c, sm, "countblend"); launch_countblend(sm, dm, cols, rows, db, dmd); }
+  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd;
+  { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
+  { PROF(c, sm, "countblend"); launch_countblend(sm, p, 1, cols, rows); }
   if (int e = down2d(c, raw_blend, bstep, db, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   HIPCHK(c, hipGetLastError());
@@ -158,16 +206,16 @@ int pf_stitch_gather(pf_ctx* c, const uint8_t* l, const uint8_t* r, const uint8_
   if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
   if (int e = up2d(c, dg, size_t(cols) * 4, merged, step, size_t(cols) * 4, rows)) return e;
   if (int e = up2d(c, dm, cols, map, mstep, cols, rows)) return e;
-  { PROF(c, c->s_main, "gather"); launch_gather(c->s_main, dl, dr, dg, dm, cols, rows, dout); }
+  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.merged[0] = dg; p.map[0] = dm; p.out[0] = dout;
+  { PROF(c, c->s_main, "gather"); launch_gather(c->s_main, p, 1, cols, rows); }
   if (int e = down2d(c, out, ostep, dout, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }
 
 
-// One whole iteration of the reference's stitch loop (CPU/main.cpp:70-95) without leaving the device:
-// Stitchtools::prepare -> NovelViewGeneratorAsymmetricFlow::prepare/generateNovelView -> Gather.
-// r_bgra == NULL chains on the previous call's result, which stays resident in HBM (main.cpp:64-65).
+// One whole iteration of the reference's stitch loop without leaving the device (stitch_step_dev with one frame on the arena's
+// own planes).  r_bgra == NULL chains on the previous call's result, which stays resident in HBM (main.cpp:64-65).
 // Content signature of a host image: 16 evenly spaced rows, 8 bytes at a time (~0.1 ms at 9000x4000).  The prefetched device copy of
 // an image is only used if the caller's buffer still carries the signature it had when it was uploaded: pointer, size and step alone
 // cannot tell a buffer from another image that an allocator later placed at the same address (the intended use is one cv::Mat freed and
@@ -199,6 +247,10 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
   hipStream_t sm = c->s_main;
   uint8_t* dnext = (uint8_t*)ensure(c, "ch_l_next", n * 4);
   if (!dnext) return PF_ERR_NOMEM;
+  const RampGeom g = ramp_geom(cols, rows);
+  StitchPtrs p{};
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   // both prefetch records are one-shot: latched and cleared here, whatever this step does with them
   const pf_ctx::HostImage ready = c->ready, hint = c->hint;
   c->ready = pf_ctx::HostImage(); c->hint = pf_ctx::HostImage();
@@ -215,25 +267,10 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
     if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "pf_stitch_step: no previous result of this size to chain on");
     HIPCHK(c, hipMemcpyAsync(dr, dfin, n * 4, hipMemcpyDeviceToDevice, sm));
   }
-  { PROF(c, sm, "match_images"); launch_match_images(sm, dl, dr, cols, rows, dm, dol, dor); }
-  // The blend ramp (GenerateBlend + countblend + smoothing, StitchTool.cpp:98-191) only depends on the map and is only
-  // needed by the final blend: it runs on its own stream beside the two flow solves.  Its launches (a dozen since the tile smoothing
-  // became ONE persistent launch in round 3; ~850 before) are enqueued AFTER the solver's, so that the solver's first kernel is not
-  // kept waiting by them.
-  if (!c->s_aux) HIPCHK(c, hipStreamCreateWithFlags(&c->s_aux, hipStreamNonBlocking));
   if (!c->s_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
-  hipStream_t sa = c->s_aux;
-  HIPCHK(c, hipEventRecord(c->ev_aux_go, sm));
-  const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT}; float* outs[2] = {f0, f1};
-  const int pad = cols / 20;
-  if (int e = solve(c, dol, dor, cols, rows, pad, max_pct, 2, hints, outs)) return e;
-  HIPCHK(c, hipStreamWaitEvent(sa, c->ev_aux_go, 0));
-  { PROF(c, sa, "countblend"); launch_countblend(sa, dm, cols, rows, db, dmd); }
-  if (int e = blend_smooth_dev(c, db, dmd, cols, rows, sa)) return e;
-  HIPCHK(c, hipEventRecord(c->ev_aux_done, sa));
-  HIPCHK(c, hipStreamWaitEvent(sm, c->ev_aux_done, 0));
-  { PROF(c, sm, "blend"); launch_blend(sm, dol, dor, f0, f1, db, cols, rows, dmerged); }
-  { PROF(c, sm, "gather"); launch_gather(sm, dl, dr, dmerged, dm, cols, rows, dfin); }
+  p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd; p.merged[0] = dmerged; p.out[0] = dfin;
+  float* const flows[2] = {f0, f1};
+  if (int e = stitch_step_dev(c, p, 1, flows, cols, rows, max_pct, g, w)) return e;
   if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   // everything of this step is enqueued: upload the NEXT step's left image now (announced with pf_stitch_prefetch); the
   // host-side staging of a pageable source runs while the GPU computes
@@ -273,70 +310,35 @@ namespace {
 // everything pf_stitch_step refuses about the canvas, before any work
 int check_stitch_canvas(pf_ctx* c, int cols, int rows, int max_pct) {
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  if (int e = check_blend_ramp(c, cols, rows)) return e;
+  if (int e = check_blend_ramp(c, cols, rows, ramp_geom(cols, rows))) return e;
   if (max_pct < 0 || max_pct > 100) return fail(c, PF_ERR_ARG, "max_percentage %d out of range", max_pct);
   return 0;
-}
-// per-frame planes of a group, `count` frames back to back in one arena buffer (256-byte aligned frames)
-extern "C++" template <class T> T* frame_planes(pf_ctx* c, const char* name, int count, size_t per_frame, size_t& stride) {
-  stride = (per_frame + 255) & ~size_t(255);
-  return (T*)ensure(c, name, stride * count);
 }
 int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
                  uint8_t* const* d_out) {
   if (int e = use(lane)) return e;
   CallGuard guard_(lane);
   const size_t n = size_t(cols) * rows;
-  const int step = cols <= rows ? cols / 200 : rows / 200, k1 = rows / 130, k2 = rows / 400;
+  const RampGeom g = ramp_geom(cols, rows);
   // 33 B/px of StitchTool planes per frame (map 1, overlaps 8, ramp + MergedDis 8, box blur 12, novel view 4) + 16 B/px of flows
-  size_t s1, s4, s8, s16;
+  size_t s1, s4, s16;
   uint8_t* map = frame_planes<uint8_t>(lane, "sb_map", count, n, s1);
   uint8_t* ovl = frame_planes<uint8_t>(lane, "sb_ovl", count, n * 4, s4); uint8_t* ovr = frame_planes<uint8_t>(lane, "sb_ovr", count, n * 4, s4);
   float* blend = frame_planes<float>(lane, "sb_blend", count, n * 4, s4); float* md = frame_planes<float>(lane, "sb_md", count, n * 4, s4);
   uint8_t* merged = frame_planes<uint8_t>(lane, "sb_merged", count, n * 4, s4);
   float* flow = frame_planes<float>(lane, "sb_flow", count, n * 16, s16);
   if (!map || !ovl || !ovr || !blend || !md || !merged || !flow) return PF_ERR_NOMEM;
-  double* rs = nullptr; float* tmp = nullptr;
-  if (k2 > 0) {
-    rs = frame_planes<double>(lane, "sb_rowsum", count, n * 8, s8); tmp = frame_planes<float>(lane, "sb_blur_tmp", count, n * 4, s4);
-    if (!rs || !tmp) return PF_ERR_NOMEM;
-  }
   StitchPtrs sp{};
-  BlendPtrs bp{};
-  const uint8_t* i0[kMaxBatch]; const uint8_t* i1[kMaxBatch]; float* outs[2 * kMaxBatch];
+  RampWork w;
+  if (int e = ramp_planes(lane, kRampBatch, count, cols, rows, g, sp, w)) return e;
+  float* flows[2 * kMaxBatch];
   for (int p = 0; p < count; ++p) {
     sp.L[p] = d_l[first + p]; sp.R[p] = d_r[first + p]; sp.out[p] = d_out[first + p];
     sp.map[p] = map + p * s1; sp.ovL[p] = ovl + p * s4; sp.ovR[p] = ovr + p * s4;
     sp.blend[p] = (float*)((char*)blend + p * s4); sp.md[p] = (float*)((char*)md + p * s4); sp.merged[p] = merged + p * s4;
-    sp.rs[p] = rs ? (double*)((char*)rs + p * s8) : nullptr; sp.tmp[p] = tmp ? (float*)((char*)tmp + p * s4) : nullptr;
-    i0[p] = sp.ovL[p]; i1[p] = sp.ovR[p];
-    outs[2 * p] = (float*)((char*)flow + p * s16); outs[2 * p + 1] = outs[2 * p] + n * 2;
-    bp.L[p] = sp.ovL[p]; bp.R[p] = sp.ovR[p]; bp.fLR[p] = outs[2 * p]; bp.fRL[p] = outs[2 * p + 1];
-    bp.blend[p] = k2 > 0 ? sp.tmp[p] : sp.blend[p]; bp.out[p] = merged + p * s4;
+    flows[2 * p] = (float*)((char*)flow + p * s16); flows[2 * p + 1] = flows[2 * p] + n * 2;
   }
-  hipStream_t sm = lane->s_main;
-  { PROF(lane, sm, "match_images"); launch_match_images_batch(sm, sp, count, cols, rows); }
-  // the blend ramp depends on the maps only: aux stream, enqueued after the solver's launches (as in pf_stitch_step)
-  if (!lane->s_aux) HIPCHK(lane, hipStreamCreateWithFlags(&lane->s_aux, hipStreamNonBlocking));
-  hipStream_t sa = lane->s_aux;
-  HIPCHK(lane, hipEventRecord(lane->ev_aux_go, sm));
-  const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT};
-  if (int e = solve_n(lane, count, i0, i1, cols, rows, cols / 20, max_pct, 2, hints, outs)) return e;
-  HIPCHK(lane, hipStreamWaitEvent(sa, lane->ev_aux_go, 0));
-  { PROF(lane, sa, "countblend"); launch_countblend_batch(sa, sp, count, cols, rows); }
-  if (step > 0 && k1 > 0) {
-    const bool streamed = !blend_ramp_fits(cols, rows);
-    void* work = ensure(lane, "sb_tile_work", tile_blur_work_bytes(cols, rows, step, k1) + 256);
-    void* scratch = streamed ? ensure(lane, "sb_tile_scratch", tile_blur_stream_scratch_bytes(step, k1)) : nullptr;
-    if (!work || (streamed && !scratch)) return PF_ERR_NOMEM;
-    { PROF(lane, sa, "tile_blur"); launch_tile_blur_batch(sa, sp, count, cols, rows, step, k1, work, streamed, scratch); }
-    launch_collect_status(sa, static_cast<const int*>(work), 2, lane->d_status, 4);   // word 1 = a grid barrier of the tile smoothing gave up
-  }
-  if (k2 > 0) { PROF(lane, sa, "box_blur"); launch_box_blur_batch(sa, sp, count, cols, rows, k2); }   // the smoothed ramp lands in tmp
-  HIPCHK(lane, hipEventRecord(lane->ev_aux_done, sa));
-  HIPCHK(lane, hipStreamWaitEvent(sm, lane->ev_aux_done, 0));
-  { PROF(lane, sm, "blend"); launch_blend_batch(sm, bp, count, cols, rows); }
-  { PROF(lane, sm, "gather"); launch_gather_batch(sm, sp, count, cols, rows); }
+  if (int e = stitch_step_dev(lane, sp, count, flows, cols, rows, max_pct, g, w)) return e;
   HIPCHK(lane, hipGetLastError());
   if (int e = finish(lane)) return e;
   return check_sweeps(lane);

@@ -176,39 +176,40 @@ void launch_adjust_initial_flow(hipStream_t st, const float* i0, const float* i1
                                 int max_pct, float* i1eq_tmp, float* flow, Batch bt = Batch());
 // blend
 void launch_blend_tables(hipStream_t st);   // once per device before the first blend (create_ctx)
-void launch_blend(hipStream_t st, const uint8_t* L, const uint8_t* R, const float* flowLR, const float* flowRL, const float* blend, int cols,
-                  int rows, uint8_t* out);
 struct BlendPtrs { const uint8_t* L[kMaxBatch]; const uint8_t* R[kMaxBatch]; const float* fLR[kMaxBatch]; const float* fRL[kMaxBatch]; const float* blend[kMaxBatch]; uint8_t* out[kMaxBatch]; };
-void launch_blend_batch(hipStream_t st, const BlendPtrs& p, int n, int cols, int rows);
-// stitch
-void launch_match_images(hipStream_t st, const uint8_t* L, const uint8_t* R, int cols, int rows, uint8_t* map, uint8_t* ovL, uint8_t* ovR);
-void launch_countblend(hipStream_t st, const uint8_t* map, int cols, int rows, float* blend, float* mergedDis);
-void launch_box_blur(hipStream_t st, const float* src, float* dst, double* rowsum_tmp, int cols, int rows, int k);
-size_t tile_blur_work_bytes(int cols, int rows, int step, int k);   // device scratch of launch_tile_blur (diagonal counts + barrier word)
-size_t tile_blur_lds_bytes(int step, int k);           // dynamic LDS of the resident form (whole window + all row sums)
-bool tile_blur_resident_fits(int step, int k);          // ... within the 160 KB of a CU: the launchers' callers pick the form by this
-bool tile_blur_stream_ok(int step, int k);              // the streamed form has a plan (one window row fits its LDS piece)
-size_t tile_blur_scratch_bytes(int step, int k);        // device scratch of the form the library picks (0 for the resident form)
-size_t tile_blur_stream_scratch_bytes(int step, int k); // device scratch of the streamed form (row sums of every block's tile)
-void launch_tile_blur(hipStream_t st, float* blend, const float* mergedDis, int cols, int rows, int step, int k, void* work, bool streamed = false,
-                      void* scratch = nullptr);
-void launch_gather(hipStream_t st, const uint8_t* L, const uint8_t* R, const uint8_t* merged, const uint8_t* map, int cols, int rows,
-                   uint8_t* out);
-int countblend_step(int cols, int rows);   // the probe stride of countblend (StitchTool.cpp:151), at least 1
-// batched stitch step (pf_stitch_step_batch*): per-frame pointer tables, blockIdx.z = frame, nf <= kMaxBatch same-size frames per launch
+void launch_blend(hipStream_t st, const BlendPtrs& p, int n, int cols, int rows);   // n pairs, blockIdx.z = pair
+void launch_blend(hipStream_t st, const uint8_t* L, const uint8_t* R, const float* flowLR, const float* flowRL, const float* blend, int cols,
+                  int rows, uint8_t* out);   // one pair: fills a one-pair table
+// stitch (K12-K15): per-frame pointer tables, blockIdx.z = frame, nf <= kMaxBatch same-size frames per launch; a lone canvas is nf = 1
 struct StitchPtrs {
   const uint8_t* L[kMaxBatch]; const uint8_t* R[kMaxBatch];     // input images
   uint8_t* map[kMaxBatch]; uint8_t* ovL[kMaxBatch]; uint8_t* ovR[kMaxBatch];
   float* blend[kMaxBatch]; float* md[kMaxBatch];                // ramp (smoothed in place by the tile pass) and MergedDis
   double* rs[kMaxBatch]; float* tmp[kMaxBatch];                 // box blur: fp64 row sums, result
-  const uint8_t* merged[kMaxBatch]; uint8_t* out[kMaxBatch];    // novel view, composite
+  uint8_t* merged[kMaxBatch]; uint8_t* out[kMaxBatch];          // novel view, composite
 };
-void launch_match_images_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);   // L, R -> map, ovL, ovR
-void launch_countblend_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
-void launch_tile_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed = false,
-                            void* scratch = nullptr);   // blend in place; work / streamed / scratch as launch_tile_blur's
-void launch_box_blur_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k); // blend -> tmp (rs: scratch)
-void launch_gather_batch(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);         // L, R, merged, map -> out
+void launch_match_images(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);   // L, R -> map, ovL, ovR
+void launch_countblend(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
+void launch_tile_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed = false,
+                      void* scratch = nullptr);                                                // blend in place, by md
+void launch_box_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k); // blend -> tmp (rs: scratch)
+void launch_gather(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);         // L, R, merged, map -> out
+// a canvas's blend-ramp geometry (StitchTool.cpp:130-143): the probe stride / tile size, the tile pass's window k1 and its form, the
+// final box blur's window k2 (0 = none)
+struct RampGeom {
+  int step = 0, k1 = 0, k2 = 0;
+  bool tiles = false;      // there is a tile pass (step > 0 && k1 > 0)
+  bool streamed = false;   // ... in the streamed form: its window exceeds the LDS of a CU
+  bool ok = true;          // false = neither form smooths this canvas (the window reaches across all of it): the entry points refuse it
+};
+RampGeom ramp_geom(int cols, int rows);
+int countblend_step(int cols, int rows);   // the probe stride of countblend (StitchTool.cpp:151), at least 1
+int tile_blur_reach(int k);                // how far a k-wide window (anchor k/2) reaches beyond its own pixel: max(k/2, k-1-k/2)
+size_t tile_blur_work_bytes(int cols, int rows, int step, int k);   // device scratch of launch_tile_blur (diagonal counts + barrier word)
+size_t tile_blur_lds_bytes(int step, int k);           // dynamic LDS of the resident form (whole window + all row sums)
+bool tile_blur_resident_fits(int step, int k);          // ... within the 160 KB of a CU: the launcher's callers pick the form by this
+bool tile_blur_stream_ok(int step, int k);              // the streamed form has a plan (one window row fits its LDS piece)
+size_t tile_blur_stream_scratch_bytes(int step, int k); // device scratch of the streamed form (row sums of every block's tile)
 void launch_fill_u64(hipStream_t st, unsigned long long* p, size_t n, unsigned long long v, Batch bt = Batch());
 void launch_fill_u32(hipStream_t st, unsigned* p, size_t n, unsigned v, Batch bt = Batch());   // memset that knows the batch dimension
 void launch_checksum64(hipStream_t st, const void* p, size_t bytes, unsigned long long* acc /* zeroed by the caller */);

@@ -80,20 +80,28 @@ def test_batch_chains_equal_single_chains(pf, rigs1200, chains1200):
 
 
 @pytest.mark.gpu
-def test_batch_step_equals_oracle_chain(pf, orc, synth):
-    cols, rows = 640, 320
+@pytest.mark.parametrize("cols,rows", [(640, 320), (400, 820)], ids=["640x320", "400x820"])
+def test_batch_step_equals_oracle_chain(pf, orc, synth, cols, rows):
+    """640x320 has no box blur (k2 = rows/400 = 0).  400x820 is the smallest canvas at which all three ramp stages run
+    non-trivially for a frame with blockIdx.z > 0: step 2, k1 6 (resident tile pass), k2 2."""
     rigs = [synth.make_stitch_set(cols, rows, s, 1) for s in (1234, 1235)]
     rigs = [(t.numpy(), [im.numpy() for im in ims]) for t, ims in rigs]
     c = pf.Context(0)
     outs = c.stitch_step_batch([ims[0] for _, ims in rigs], [t for t, _ in rigs], PCT, in_flight=2)
+    lone = [c.stitch_step(ims[0], t, PCT) for t, ims in rigs]
     c.close()
+    step, k2 = min(cols, rows) // 200, rows // 400
     for k, (top, ims) in enumerate(rigs):
         L, R = ims[0], top
-        mp, ovl, ovr, blend, _ = orc.stitch_prepare(L, R, True)
+        mp, ovl, ovr, blend, md = orc.stitch_prepare(L, R, True)
+        if (cols, rows) == (400, 820):   # the geometry is what this case is for
+            active = int((md[0:rows - step:step, 0:cols - step:step] > step).sum())
+            assert k2 >= 2 and active >= 1000, "frame %d: k2 %d, %d active tiles" % (k, k2, active)
         f0, f1 = orc.flow_bidir(ovl, ovr, PCT)
         merged = orc.combine_novel_views(ovl, ovr, f0, f1, blend)
         ref = orc.stitch_gather(L, R, merged, mp)
         assert np.array_equal(outs[k], ref), "frame %d: %d bytes differ from the oracle chain" % (k, _ndiff(outs[k], ref))
+        assert np.array_equal(lone[k], ref), "frame %d: stitch_step differs from the oracle chain in %d bytes" % (k, _ndiff(lone[k], ref))
 
 
 @pytest.mark.gpu
