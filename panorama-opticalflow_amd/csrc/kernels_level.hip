@@ -1,5 +1,8 @@
 // Per-level kernels of PixFlow::patchMatchPropagationAndSearch (CPU/PixFlow.hpp:272-340) except the
 // sweeps, plus the inter-level and final upsampling (:122-134).  All stencil/streaming, HBM-bound.
+// One kernel per stage: gradients and gate + boxes + count cover every level of a level table in one launch (the stage entry
+// points and the largest canvases hand them a one-level table), the Gaussian 15 is the fused LDS kernel in all its uses.  The two
+// stages with two forms (median 5, cubic upsample: direct and tiled) pick by level size / scale, and both forms are used.
 #include <stdio.h>
 #include <stdlib.h>
 #include "pf_common.hpp"
@@ -11,7 +14,7 @@ namespace pf {
 // BORDER_REFLECT_101 (PixFlow.hpp:281-294).  Output interleaved (Ix,Iy) so the sweep's bilinear
 // gather fetches both with one 8-byte load per texel.
 // ------------------------------------------------------------------------------------------------
-// Sobel(ksize 1) + Gauss3 sigma 0.5 at one pixel (PixFlow.hpp:281-294); shared by the per-level and the all-levels kernel
+// Sobel(ksize 1) + Gauss3 sigma 0.5 at one pixel (PixFlow.hpp:281-294)
 __device__ __forceinline__ float2 d_gradient_px(const float* __restrict__ img, int w, int h, int x, int y, const Gauss& g) {
   const float k0 = g.k[1], k1 = g.k[2];
   const int xm = d_reflect101(x - 1, w), xp = d_reflect101(x + 1, w);
@@ -103,12 +106,7 @@ __device__ __forceinline__ void d_gradient_quad_interior(const float* __restrict
 __device__ __forceinline__ float2 d_gradient_any(const float* __restrict__ img, int w, int h, int x, int y, const Gauss& g) {
   return (x >= 2 && x < w - 2 && y >= 2 && y < h - 2) ? d_gradient_px_interior(img, w, x, y, g) : d_gradient_px(img, w, h, x, y, g);
 }
-__global__ __launch_bounds__(256) void k_gradients(const float* __restrict__ img, int w, int h, float2* __restrict__ gxy, Gauss g) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  gxy[size_t(y) * w + x] = d_gradient_any(img, w, h, x, y, g);
-}
-// All pyramid levels of both images in ONE launch (the per-level launches of the small levels are pure launch latency):
+// All pyramid levels of both images in ONE launch (per-level launches of the small levels are pure launch latency):
 // a thread's flat index inside the pyramid plane -> level by binary search in the offset table -> (x, y).
 __global__ __launch_bounds__(256) void k_gradients_all(const float* __restrict__ img0, const float* __restrict__ img1, float2* __restrict__ g0,
                                                        float2* __restrict__ g1, LevelTable t, unsigned first, unsigned total, Gauss g, size_t bstride) {
@@ -145,12 +143,9 @@ __global__ __launch_bounds__(256) void k_gradients_all(const float* __restrict__
     }
   }
 }
-void launch_gradients(hipStream_t st, const float* img, int w, int h, float* gxy, const Gauss& g3) {
-  dim3 grid((w + 255) / 256, h);
-  hipLaunchKernelGGL(k_gradients, grid, dim3(256), 0, st, img, w, h, reinterpret_cast<float2*>(gxy), g3);
-}
 // max_blocks > 0 caps the blocks per image: a launch that runs BESIDE latency-critical kernels (the finest levels' gradients
 // next to the coarse levels' sweeps) is made narrow so that it takes a few wave slots per CU instead of all of them.
+// pyr1 == nullptr: one image (gridDim.y = 1; the kernel picks its image by blockIdx.y).
 void launch_gradients_all(hipStream_t st, const float* pyr0, const float* pyr1, float* grad0, float* grad1, const LevelTable& t, size_t first,
                           size_t total, const Gauss& g3, int max_blocks, Batch bt) {
   if (total <= first) return;
@@ -161,58 +156,8 @@ void launch_gradients_all(hipStream_t st, const float* pyr0, const float* pyr1, 
   if (!aligned) { fprintf(stderr, "[panoflow] launch_gradients_all: level offsets must be multiples of 4 elements\n"); abort(); }
   size_t blocks = (total - first + 1023) / 1024;   // four elements per thread
   if (max_blocks > 0 && blocks > size_t(max_blocks)) blocks = size_t(max_blocks);
-  hipLaunchKernelGGL(k_gradients_all, dim3((unsigned)blocks, 2, bt.n), dim3(256), 0, st, pyr0, pyr1, reinterpret_cast<float2*>(grad0),
+  hipLaunchKernelGGL(k_gradients_all, dim3((unsigned)blocks, pyr1 ? 2 : 1, bt.n), dim3(256), 0, st, pyr0, pyr1, reinterpret_cast<float2*>(grad0),
                      reinterpret_cast<float2*>(grad1), t, (unsigned)first, (unsigned)total, g3, bt.stride);
-}
-
-// update gate of the sweeps (PixFlow.hpp:317,330): alpha0 > 0.9 && alpha1 > 0.9
-__global__ __launch_bounds__(256) void k_gate(const float* __restrict__ a0, const float* __restrict__ a1, int n, uint8_t* __restrict__ gate) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) gate[i] = (a0[i] > kUpdateAlphaThreshold && a1[i] > kUpdateAlphaThreshold) ? 1 : 0;
-}
-void launch_gate(hipStream_t st, const float* a0, const float* a1, int n, uint8_t* gate) {
-  hipLaunchKernelGGL(k_gate, dim3((n + 255) / 256), dim3(256), 0, st, a0, a1, n, gate);
-}
-
-// Bounding box of the gated pixels of every pyramid level in one launch: box[4*l + {0,1,2,3}] = (min x, min y, max x, max y),
-// initialised by the caller to (INT_MAX, INT_MAX, -1, -1).  A block scans 16 Ki consecutive plane elements, reduces in
-// registers / LDS and issues at most four atomics per level it touched (a chunk spans at most a few of the small levels).
-__global__ __launch_bounds__(256) void k_gate_bbox(const uint8_t* __restrict__ gate, LevelTable t, unsigned total, int* __restrict__ box) {
-  __shared__ int sbox[4];
-  const unsigned base = blockIdx.x * 16384u;
-  int lvl = -1, w = 1, mnx = 0x7fffffff, mny = 0x7fffffff, mxx = -1, mxy = -1;
-  unsigned off = 0, cnt = 0;
-  auto flush = [&]() {   // block-level reduction of one level's partial box, then the atomics
-    if (threadIdx.x < 4) sbox[threadIdx.x] = (threadIdx.x < 2) ? 0x7fffffff : -1;
-    __syncthreads();
-    if (mxx >= 0) { atomicMin(&sbox[0], mnx); atomicMin(&sbox[1], mny); atomicMax(&sbox[2], mxx); atomicMax(&sbox[3], mxy); }
-    __syncthreads();
-    if (threadIdx.x == 0 && sbox[2] >= 0) {
-      atomicMin(&box[4 * lvl + 0], sbox[0]); atomicMin(&box[4 * lvl + 1], sbox[1]);
-      atomicMax(&box[4 * lvl + 2], sbox[2]); atomicMax(&box[4 * lvl + 3], sbox[3]);
-    }
-    __syncthreads();
-    mnx = 0x7fffffff; mny = 0x7fffffff; mxx = -1; mxy = -1;
-  };
-  // all threads of the block walk the levels the chunk intersects in the same order (block-uniform control flow)
-  int l0 = 0, hi = t.n - 1;
-  while (l0 < hi) { const int mid = (l0 + hi + 1) >> 1; if (base >= t.off[mid]) l0 = mid; else hi = mid - 1; }
-  const unsigned end = (base + 16384u < total) ? base + 16384u : total;
-  for (int l = l0; l < t.n && t.off[l] < end; ++l) {
-    lvl = l; w = t.w[l]; off = t.off[l]; cnt = unsigned(t.w[l]) * unsigned(t.h[l]);
-    const unsigned lo = off > base ? off : base, hiE = (off + cnt < end) ? off + cnt : end;
-    for (unsigned i = lo + threadIdx.x; i < hiE; i += 256) {
-      if (gate[i]) {
-        const unsigned local = i - off;
-        const int y = int(local / unsigned(w)), x = int(local - unsigned(y) * unsigned(w));
-        mnx = min(mnx, x); mny = min(mny, y); mxx = max(mxx, x); mxy = max(mxy, y);
-      }
-    }
-    flush();
-  }
-}
-void launch_gate_bbox(hipStream_t st, const uint8_t* gate, const LevelTable& t, size_t total, int* box) {
-  hipLaunchKernelGGL(k_gate_bbox, dim3((unsigned)((total + 16383) / 16384)), dim3(256), 0, st, gate, t, (unsigned)total, box);
 }
 
 // Gate + bounding boxes + level-0 count of ALL levels in ONE launch, published straight into mapped pinned host memory:
@@ -221,10 +166,7 @@ void launch_gate_bbox(hipStream_t st, const uint8_t* gate, const LevelTable& t, 
 // The last block to finish copies boxes + count to `host` (system-scope stores), stores the call's epoch behind them as the
 // "ready" flag, and resets the work area for the next call -- the host polls that flag instead of synchronising the stream
 // (no pageable copies, no blocking wait: the round trip costs microseconds).
-#ifndef PF_GATE_PER
-#define PF_GATE_PER 16384
-#endif
-constexpr unsigned kGatePer = PF_GATE_PER;   // level-pixels per block
+constexpr unsigned kGatePer = 16384;   // level-pixels per block
 __global__ __launch_bounds__(256) void k_gate_bbox_all(const float* __restrict__ a0, const float* __restrict__ a1, uint8_t* __restrict__ gate, LevelTable t,
                                                        unsigned total, int* __restrict__ work, int* __restrict__ host, int epoch, size_t bstride, size_t hstride) {
   { const size_t bo = size_t(blockIdx.z) * bstride; PF_BOFF(a0, bo); PF_BOFF(a1, bo); PF_BOFF(gate, bo); PF_BOFF(work, bo); PF_BOFF(host, size_t(blockIdx.z) * hstride); }
@@ -328,17 +270,6 @@ void launch_gate_bbox_all(hipStream_t st, const float* a0, const float* a1, uint
                      epoch, bt.stride, host_stride);
 }
 
-__global__ __launch_bounds__(256) void k_count_gate(const uint8_t* __restrict__ gate, int n, unsigned* __restrict__ count) {
-  int c = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) c += gate[i];
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned)c);
-}
-void launch_count_gate(hipStream_t st, const uint8_t* gate, int n, unsigned* count) {
-  const int blocks = (n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256;
-  hipLaunchKernelGGL(k_count_gate, dim3(blocks), dim3(256), 0, st, gate, n, count);
-}
-
 // ------------------------------------------------------------------------------------------------
 // K7 medianBlur(5) on float2, per channel, BORDER_REPLICATE, out of place (PixFlow.hpp:325,338).
 // A median is a pure selection: the element of rank 13 of the window, whatever finds it.  Two horizontally adjacent outputs per
@@ -414,39 +345,11 @@ __device__ __forceinline__ float2 d_upsample_cubic_px(const float2* __restrict__
 // [OpenCV filter.cpp] row pass = RowFilter (plain left-to-right accumulation), column pass =
 // SymmColumnFilter (centre, then symmetric pairs outward).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gauss15_row(const float2* __restrict__ src, float2* __restrict__ tmp, int w, int h, Gauss g) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const float2* r = src + size_t(y) * w;
-  float2 v = r[d_reflect101(x - 7, w)];
-  float sx = g.k[0] * v.x, sy = g.k[0] * v.y;
-#pragma unroll
-  for (int j = 1; j < 15; ++j) {
-    v = r[d_reflect101(x - 7 + j, w)];
-    sx += g.k[j] * v.x; sy += g.k[j] * v.y;
-  }
-  tmp[size_t(y) * w + x] = make_float2(sx, sy);
-}
-__device__ __forceinline__ float2 d_gauss15_col(const float2* __restrict__ tmp, int w, int h, int x, int y, const Gauss& g) {
-  float2 c = tmp[size_t(y) * w + x];
-  float sx = g.k[7] * c.x + 0.0f, sy = g.k[7] * c.y + 0.0f;
-#pragma unroll
-  for (int j = 1; j <= 7; ++j) {
-    const float2 a = tmp[size_t(d_reflect101(y + j, h)) * w + x], b = tmp[size_t(d_reflect101(y - j, h)) * w + x];
-    sx += g.k[7 + j] * (a.x + b.x); sy += g.k[7 + j] * (a.y + b.y);
-  }
-  return make_float2(sx, sy);
-}
-__global__ __launch_bounds__(256) void k_gauss15_col(const float2* __restrict__ tmp, float2* __restrict__ dst, int w, int h, Gauss g) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  dst[size_t(y) * w + x] = d_gauss15_col(tmp, w, h, x, y, g);
-}
 // Row + column pass in ONE launch, staged through LDS: a block owns a 64 x 32 output tile.  (1) the source tile with its
 // 7-pixel ring (reflect-101 on both indices) is loaded once, coalesced, into LDS; (2) the row pass (RowFilter: plain
 // left-to-right accumulation) of the 46 rows the column pass needs goes from LDS to LDS; (3) the column pass
-// (SymmColumnFilter: centre, then symmetric pairs outward) reads LDS.  Same operations in the same order as the two-kernel
-// form => identical bits.  Both passes are register-blocked along their filter axis -- a thread reads a run of 16 + 14 (row
+// (SymmColumnFilter: centre, then symmetric pairs outward) reads LDS.  Same operations in the same order as OpenCV's
+// two passes => identical bits.  Both passes are register-blocked along their filter axis -- a thread reads a run of 16 + 14 (row
 // pass) or 8 + 14 (column pass) values once and produces 16 / 8 outputs from registers, 1.9 / 2.75 LDS reads per output
 // instead of 15 -- because the first fused version was bound by LDS bandwidth.  In the row pass a wave's lanes run along y
 // (one source row each), so the LDS row strides are odd numbers of float2 (79, 65): at most 2-way bank conflicts.
@@ -638,8 +541,7 @@ static inline void gauss15_grid(int w, int h, int& ntx, int& ntiles, unsigned& b
   if (per < 1) per = 1;
   blocks = (unsigned)(ntiles < per ? ntiles : per);
 }
-void launch_gauss15(hipStream_t st, const float* src, float* tmp, float* dst, int w, int h, const Gauss& g15, Batch bt) {
-  (void)tmp;
+void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt) {
   int ntx, ntiles; unsigned blocks;
   gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
   hipLaunchKernelGGL((k_gauss15_fused<false, false, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, reinterpret_cast<const float2*>(src), reinterpret_cast<float2*>(dst), w, h, g15, nullptr, nullptr, ntx, ntiles, UpsSrc{}, bt.stride);
@@ -653,19 +555,8 @@ void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh
   hipLaunchKernelGGL((k_gauss15_fused<false, true, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, nullptr, reinterpret_cast<float2*>(dst), w, h, g15, nullptr, nullptr, ntx, ntiles, u, bt.stride);
 }
 
-// K8 lowAlphaFlowDiffusion (PixFlow.hpp:388-405): column pass fused with the alpha mix.
-__global__ __launch_bounds__(256) void k_gauss15_col_mix(const float2* __restrict__ tmp, const float2* __restrict__ flow, const float* __restrict__ a0,
-                                                         const float* __restrict__ a1, float2* __restrict__ out, int w, int h, Gauss g) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= w) return;
-  const size_t i = size_t(y) * w + x;
-  const float2 b = d_gauss15_col(tmp, w, h, x, y, g);
-  const float2 f = flow[i];
-  const float diffusionCoef = 1.0f - a0[i] * a1[i];
-  out[i] = make_float2(diffusionCoef * b.x + (1.0f - diffusionCoef) * f.x, diffusionCoef * b.y + (1.0f - diffusionCoef) * f.y);
-}
-void launch_gauss15_mix(hipStream_t st, float* flow, float* tmp, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt) {
-  (void)tmp;
+// K8 lowAlphaFlowDiffusion (PixFlow.hpp:388-405): the alpha mix is the fused kernel's epilogue (MIX).
+void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt) {
   int ntx, ntiles; unsigned blocks;
   gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
   hipLaunchKernelGGL((k_gauss15_fused<true, false, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, reinterpret_cast<const float2*>(flow), reinterpret_cast<float2*>(out), w, h, g15, a0, a1, ntx, ntiles, UpsSrc{}, bt.stride);
@@ -697,11 +588,7 @@ __global__ __launch_bounds__(256) void k_median5(const float2* __restrict__ src,
 // Tile shape: until round 4 a block was 1024 threads (128 x 16) -- at 71 VGPRs ONE such block fits a CU, so every block's HBM round trip
 // stood in front of its network with nothing beside it.  Small blocks interleave (profiles/r04_median_tile_ab.txt: median family of a
 // dense pair 3.11 -> 2.78 ms, 8 pairs in flight +1.5 %).
-#ifndef PF_MEDX
-#define PF_MEDX 32
-#define PF_MEDY 16
-#endif
-constexpr int kMedX = PF_MEDX, kMedY = PF_MEDY, kMedSX = kMedX + 4, kMedSY = kMedY + 4, kMedT = (kMedX / 2) * kMedY;
+constexpr int kMedX = 32, kMedY = 16, kMedSX = kMedX + 4, kMedSY = kMedY + 4, kMedT = (kMedX / 2) * kMedY;
 __global__ __launch_bounds__(kMedT) void k_median5_tiled(const float2* __restrict__ src, float2* __restrict__ dst, int w, int h, size_t bstride) {
   { const size_t bo = size_t(blockIdx.z) * bstride; PF_BOFF(src, bo); PF_BOFF(dst, bo); }
   __shared__ __attribute__((aligned(16))) float2 tile[kMedSY][kMedSX];
@@ -740,10 +627,7 @@ __global__ __launch_bounds__(kMedT) void k_median5_tiled(const float2* __restric
   }
 }
 // (threshold re-measured with the small blocks, same file: 3 M -> 20 k pixels; the direct form only keeps the levels of a few blocks)
-#ifndef PF_MED_MINPX
-#define PF_MED_MINPX 20000
-#endif
-constexpr long kMedTiledMinPx = PF_MED_MINPX;
+constexpr long kMedTiledMinPx = 20000;
 void launch_median5_form(hipStream_t st, const float* src, float* dst, int w, int h, bool tiled, Batch bt) {
   if (tiled) {
     dim3 grid((w + kMedX - 1) / kMedX, (h + kMedY - 1) / kMedY, bt.n);

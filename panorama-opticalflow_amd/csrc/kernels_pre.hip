@@ -102,24 +102,6 @@ void launch_gauss_small(hipStream_t st, const float* src, float* dst, int w, int
   else hipLaunchKernelGGL((k_gauss_small<2, 2>), grid, dim3(256), 0, st, src, dst, w, h, g, bt.stride);
 }
 
-template <int CN>
-__global__ __launch_bounds__(256) void k_resize_linear(const float* __restrict__ src, int sw, int sh, float* __restrict__ dst, int dw, int dh,
-                                                       double scale_x, double scale_y, float mul, int do_mul) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
-  if (dx >= dw) return;
-  float v[CN];
-  d_resize_linear_px<CN>(src, sw, sh, dw, dh, scale_x, scale_y, dx, dy, v);
-#pragma unroll
-  for (int c = 0; c < CN; ++c) dst[(size_t(dy) * dw + dx) * CN + c] = do_mul ? v[c] * mul + 0.0f : v[c];
-}
-
-void launch_resize_linear(hipStream_t st, const float* src, int sw, int sh, float* dst, int dw, int dh, int cn, float mul, bool do_mul) {
-  const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-  dim3 grid((dw + 255) / 256, dh);
-  if (cn == 1) hipLaunchKernelGGL((k_resize_linear<1>), grid, dim3(256), 0, st, src, sw, sh, dst, dw, dh, sx, sy, mul, int(do_mul));
-  else hipLaunchKernelGGL((k_resize_linear<2>), grid, dim3(256), 0, st, src, sw, sh, dst, dw, dh, sx, sy, mul, int(do_mul));
-}
-
 struct Ptr4 { const float* s[4]; float* d[4]; };
 __global__ __launch_bounds__(256) void k_pyr_down4(Ptr4 p, int sw, int sh, int dw, int dh, double scale_x, double scale_y, int nplanes, size_t bstride) {
   const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y, pl = blockIdx.z % nplanes;
@@ -132,20 +114,13 @@ __global__ __launch_bounds__(256) void k_pyr_down4(Ptr4 p, int sw, int sh, int d
   dst[size_t(dy) * dw + dx] = v[0];
 }
 
+// nplanes = 1..4 of the planes s0..s3 -> d0..d3 (the solver: both grey and both alpha pyramids; a stage test: one plane)
 void launch_pyr_down4(hipStream_t st, const float* s0, const float* s1, const float* s2, const float* s3, int sw, int sh, float* d0,
-                      float* d1, float* d2, float* d3, int dw, int dh, Batch bt) {
+                      float* d1, float* d2, float* d3, int dw, int dh, Batch bt, int nplanes) {
   Ptr4 p{{s0, s1, s2, s3}, {d0, d1, d2, d3}};
   const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-  dim3 grid((dw + 255) / 256, dh, 4 * bt.n);
-  hipLaunchKernelGGL(k_pyr_down4, grid, dim3(256), 0, st, p, sw, sh, dw, dh, sx, sy, 4, bt.stride);
-}
-
-// two planes per launch: the alpha pyramids and the grey pyramids are built on different streams (pf_api.hip: solve)
-void launch_pyr_down2(hipStream_t st, const float* s0, const float* s1, int sw, int sh, float* d0, float* d1, int dw, int dh) {
-  Ptr4 p{{s0, s1, s0, s1}, {d0, d1, d0, d1}};
-  const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-  dim3 grid((dw + 255) / 256, dh, 2);
-  hipLaunchKernelGGL(k_pyr_down4, grid, dim3(256), 0, st, p, sw, sh, dw, dh, sx, sy, 2, size_t(0));
+  dim3 grid((dw + 255) / 256, dh, nplanes * bt.n);
+  hipLaunchKernelGGL(k_pyr_down4, grid, dim3(256), 0, st, p, sw, sh, dw, dh, sx, sy, nplanes, bt.stride);
 }
 
 // Several pyramid levels per launch.  The levels form a dependency chain (level l+1 is a bilinear resize of level l), and for the

@@ -22,7 +22,7 @@ void run_level(pf_ctx* c, hipStream_t st, const float* g0, const float* g1, cons
   // ups_src: flow_a does not hold this level's incoming flow yet -- it is the upsample of the coarser level's result (ups_w x ups_h),
   // computed by the Gaussian's tile loader on the way (small levels: one launch instead of two)
   if (ups_src) { PROF(c, st, "gauss15_blurredFlow"); launch_gauss15_upsample(st, ups_src, ups_w, ups_h, 1.0f / c->sp.pyr_scale_factor, b.flow_a, b.blurred, w, h, c->g15, bt); }
-  else { PROF(c, st, "gauss15_blurredFlow"); launch_gauss15(st, b.flow_a, b.tmp, b.blurred, w, h, c->g15, bt); }
+  else { PROF(c, st, "gauss15_blurredFlow"); launch_gauss15(st, b.flow_a, b.blurred, w, h, c->g15, bt); }
   SweepArgs sa;
   sa.bt = bt; sa.cf = c->cf;
   sa.g0 = reinterpret_cast<const float2*>(g0); sa.g1 = reinterpret_cast<const float2*>(g1);
@@ -64,21 +64,8 @@ void run_level(pf_ctx* c, hipStream_t st, const float* g0, const float* g1, cons
     return;
   }
   { PROF(c, st, "median5"); launch_median5(st, b.flow_b, b.flow_a, w, h, bt); }
-  { PROF(c, st, "gauss15_diffusion"); launch_gauss15_mix(st, b.flow_a, b.tmp, a0, a1, w, h, c->g15, b.flow_b, bt); }
+  { PROF(c, st, "gauss15_diffusion"); launch_gauss15_mix(st, b.flow_a, a0, a1, w, h, c->g15, b.flow_b, bt); }
   *result = b.flow_b;
-}
-
-// bounding boxes of the gated pixels of the levels described by t (device gate plane) -> host; one stream sync
-int gate_boxes_to_host(pf_ctx* c, hipStream_t st, const uint8_t* gate, const LevelTable& t, size_t total, std::vector<int>& box) {
-  box.assign(size_t(t.n) * 4, 0);
-  for (int l = 0; l < t.n; ++l) { box[4 * l] = 0x7fffffff; box[4 * l + 1] = 0x7fffffff; box[4 * l + 2] = -1; box[4 * l + 3] = -1; }
-  int* d_box = (int*)ensure(c, "gate_box", size_t(kLevelTableMax) * 4 * sizeof(int));
-  if (!d_box) return PF_ERR_NOMEM;
-  HIPCHK(c, hipMemcpyAsync(d_box, box.data(), box.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  launch_gate_bbox(st, gate, t, total, d_box);
-  HIPCHK(c, hipMemcpyAsync(box.data(), d_box, box.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  return 0;
 }
 
 // Everything one solve keeps in HBM (named grow-only arena): shared pyramids / gradients / gate, per-direction flow
@@ -139,11 +126,18 @@ int alloc_solve(Carver& cv, const Geometry& g, int ndirs, SolveBufs& b) {
   if (cv.slab) {
     b.gate_work = (int*)cv.get("gate_work", (4 * kLevelTableMax + 2) * sizeof(int));
     for (int d = 0; d < 2; ++d) b.nv_flow[d] = (float*)cv.get(d ? "nv_flow_r2l" : "nv_flow_l2r", size_t(g.cols) * g.rows * 8);
-  } else if (!ensure(c, "gate_box", size_t(kLevelTableMax) * 4 * sizeof(int)) || !ensure(c, "gate_count", 256)) return PF_ERR_NOMEM;
+  }
   (void)c;
   return 0;
 }
 int alloc_solve(pf_ctx* c, const Geometry& g, int ndirs, SolveBufs& b) { Carver cv{c, false, nullptr, 0}; return alloc_solve(cv, g, ndirs, b); }
+// initial content of a work area of k_gate_bbox_all: (INT_MAX, INT_MAX, -1, -1) per level, count 0, blocks finished 0.  The kernel
+// leaves the area in this state (self-resetting), so it is written once per allocation.
+std::vector<int> gate_work_init() {
+  std::vector<int> init(kGateWords, 0);
+  for (int l = 0; l < kLevelTableMax; ++l) { init[4 * l] = 0x7fffffff; init[4 * l + 1] = 0x7fffffff; init[4 * l + 2] = -1; init[4 * l + 3] = -1; }
+  return init;
+}
 // slabs of a batch of nb pairs: returns pair 0's buffers and the slab stride
 int alloc_solve_batch(pf_ctx* c, const Geometry& g, int nb, SolveBufs& b, size_t& stride) {
   Carver sizing{c, true, nullptr, 0};
@@ -156,8 +150,7 @@ int alloc_solve_batch(pf_ctx* c, const Geometry& g, int nb, SolveBufs& b, size_t
   if (int e = alloc_solve(cv, g, 2, b)) return e;
   const size_t work_off = size_t(reinterpret_cast<char*>(b.gate_work) - base);
   if (fresh || c->slab_stride != stride || c->slab_work_off != work_off || c->slab_pairs < nb) {   // new memory or a new layout: (re)initialise the self-resetting work areas
-    std::vector<int> init(4 * kLevelTableMax + 2, 0);
-    for (int l = 0; l < kLevelTableMax; ++l) { init[4 * l] = 0x7fffffff; init[4 * l + 1] = 0x7fffffff; init[4 * l + 2] = -1; init[4 * l + 3] = -1; }
+    const std::vector<int> init = gate_work_init();
     for (int p = 0; p < nb; ++p)
       if (hipMemcpy(reinterpret_cast<char*>(b.gate_work) + size_t(p) * stride, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(c, PF_ERR_DEVICE, "initialising the batch slabs failed");
@@ -171,15 +164,14 @@ int* gate_work(pf_ctx* c) {
   const bool fresh = c->bufs.find("gate_work") == c->bufs.end() || !c->bufs["gate_work"].p;
   int* w = (int*)ensure(c, "gate_work", (4 * kLevelTableMax + 2) * sizeof(int));
   if (w && fresh) {
-    std::vector<int> init(4 * kLevelTableMax + 2, 0);
-    for (int l = 0; l < kLevelTableMax; ++l) { init[4 * l] = 0x7fffffff; init[4 * l + 1] = 0x7fffffff; init[4 * l + 2] = -1; init[4 * l + 3] = -1; }
+    const std::vector<int> init = gate_work_init();
     if (hipMemcpy(w, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
   }
   return w;
 }
 // Host side of k_gate_bbox_all: poll the epoch flag in mapped pinned memory (microseconds) instead of synchronising the
 // stream; boxes (4 ints per level) and the level-0 count are then already in host memory.
-int wait_gate_boxes(pf_ctx* c, hipStream_t st, int epoch, int nlevels, std::vector<int>& box, unsigned& count0, int pair = 0) {
+int wait_gate_boxes(pf_ctx* c, hipStream_t st, int epoch, int nlevels, int* box /* [4 * nlevels] */, unsigned& count0, int pair = 0) {
   const int* hg = c->h_gate + size_t(pair) * kGateWords;
   volatile const int* flag = hg + 4 * kLevelTableMax + 1;
   const auto t0 = std::chrono::steady_clock::now();
@@ -196,8 +188,22 @@ int wait_gate_boxes(pf_ctx* c, hipStream_t st, int epoch, int nlevels, std::vect
       if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != epoch) return fail(c, PF_ERR_DEVICE, "gate bounding boxes never arrived");
     }
   }
-  box.assign(hg, hg + size_t(nlevels) * 4);
+  std::copy(hg, hg + size_t(nlevels) * 4, box);
   count0 = (unsigned)hg[4 * kLevelTableMax];
+  return 0;
+}
+// Gate, bounding box and gated-pixel count of ONE w x h level (a one-level table), waited for: what the stage entry points run, and a
+// solve whose pyramid does not fit a level table, level by level.  a0 / a1 16-byte aligned, gate 4-byte aligned.
+// Uses the context's one gate_work / h_gate area of pair 0: not to be called while another gate launch of the same context is pending.
+int gate_level(pf_ctx* c, hipStream_t st, const float* a0, const float* a1, uint8_t* gate, int w, int h, int box[4], unsigned* count) {
+  LevelTable t{}; t.n = 1; t.w[0] = w; t.h[0] = h;
+  int* work = gate_work(c);
+  if (!work) return PF_ERR_NOMEM;
+  const int epoch = ++c->gate_epoch;
+  { PROF(c, st, "gate"); launch_gate_bbox_all(st, a0, a1, gate, t, size_t(w) * h, work, c->d_gate, epoch); }
+  unsigned n = 0;
+  if (int e = wait_gate_boxes(c, st, epoch, 1, box, n)) return e;
+  if (count) *count = n;
   return 0;
 }
 
@@ -259,28 +265,33 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
   // or sparse sweep variant; full-canvas inputs, CPU/StitchTool.cpp:17-33): one fused kernel computes gate, boxes and count
   // and publishes them into mapped pinned memory; the host polls its epoch flag (microseconds, no blocking sync, no pageable
   // copies) while the gradients of all levels and the hand-off initialisation are still running behind it.
-  bool have_table = false; LevelTable table;
-  const int split = g.n > 10 ? 8 : 0;   // levels [0, split) are "fine": 80 % of the pixels of a 0.9x pyramid
+  LevelTable table{};   // n == 0: the pyramid does not fit one launch's table (below)
+  if (g.n <= kLevelTableMax && g.P < (size_t(1) << 31)) {
+    table.n = g.n;
+    for (int l = 0; l < g.n; ++l) { table.w[l] = g.ws[l]; table.h[l] = g.hs[l]; table.off[l] = (unsigned)g.off[l]; }
+  }
+  const int split = table.n > 10 ? 8 : 0;   // levels [0, split) are "fine": 80 % of the pixels of a 0.9x pyramid
   unsigned h_cnt = 0;
   std::vector<int> boxes;
   int epoch = 0;
-  if (g.n <= kLevelTableMax && g.P < (size_t(1) << 31)) {
-    LevelTable t; t.n = g.n;
-    for (int l = 0; l < g.n; ++l) { t.w[l] = g.ws[l]; t.h[l] = g.hs[l]; t.off[l] = (unsigned)g.off[l]; }
+  if (table.n) {
     int* work = nb == 1 ? gate_work(c) : sb.gate_work;
     if (!work) return PF_ERR_NOMEM;
     epoch = ++c->gate_epoch;
-    { PROF(c, sg, "gate"); launch_gate_bbox_all(sg, pyrA[0], pyrA[1], gate, t, g.P, work, c->d_gate, epoch, bt, kGateWords * sizeof(int)); }
+    { PROF(c, sg, "gate"); launch_gate_bbox_all(sg, pyrA[0], pyrA[1], gate, table, g.P, work, c->d_gate, epoch, bt, kGateWords * sizeof(int)); }
     // gradients: the coarse levels first (a few percent of the pixels) -- the directions start on those -- the fine levels in a
     // second launch that runs while the coarse levels are already being solved (ev_fine, waited for at level split - 1)
-    { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], t, g.off[split], g.P, c->g3_05, 0, bt); }
-    have_table = true; table = t;
+    { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], table, g.off[split], g.P, c->g3_05, 0, bt); }
   } else {
+    // A pyramid plane of 2^31 elements or more (a lone canvas of ~1.48 Gpix and up): the same two kernels level by level, each on a
+    // one-level table, everything in front of ev_pre; the host waits for each level's box.  Built from the pieces the stage tests hold
+    // to the oracle -- at its own sizes (a solve of ~190 GB) this branch has never been run.
+    boxes.assign(size_t(g.n) * 4, 0);
     for (int l = 0; l < g.n; ++l) {
-      PROF(c, sm, "gradients");
-      launch_gradients(sm, pyrI[0] + g.off[l], g.ws[l], g.hs[l], grad[0] + 2 * g.off[l], c->g3_05);
-      launch_gradients(sm, pyrI[1] + g.off[l], g.ws[l], g.hs[l], grad[1] + 2 * g.off[l], c->g3_05);
-      launch_gate(sg, pyrA[0] + g.off[l], pyrA[1] + g.off[l], g.ws[l] * g.hs[l], gate + g.off[l]);
+      LevelTable t1{}; t1.n = 1; t1.w[0] = g.ws[l]; t1.h[0] = g.hs[l];
+      const size_t o = g.off[l];   // a multiple of 64 elements
+      { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0] + o, pyrI[1] + o, grad[0] + 2 * o, grad[1] + 2 * o, t1, 0, size_t(g.ws[l]) * g.hs[l], c->g3_05); }
+      if (int e = gate_level(c, sg, pyrA[0] + o, pyrA[1] + o, gate + o, g.ws[l], g.hs[l], &boxes[4 * l], l == 0 ? &h_cnt : nullptr)) return e;
     }
   }
   for (int d = 0; d < ndirs; ++d) {
@@ -300,16 +311,16 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
   // for the whole solve: full width, pf_config::full_width_batch_gradients)
   const int fineBlocks = (nb > 1 && c->cfg.full_width_batch_gradients) ? 0 : c->cfg.fine_gradient_blocks;
   const int split2 = split > 4 ? 4 : 0;
-  if (have_table && split > 0) { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], table, g.off[split2], g.off[split], c->g3_05, fineBlocks, bt); }
+  if (split > 0) { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], table, g.off[split2], g.off[split], c->g3_05, fineBlocks, bt); }
   HIPCHK(c, hipEventRecord(c->ev_fine, sm));
-  if (have_table && split2 > 0) { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], table, 0, g.off[split2], c->g3_05, fineBlocks, bt); }
+  if (split2 > 0) { PROF(c, sm, "gradients"); launch_gradients_all(sm, pyrI[0], pyrI[1], grad[0], grad[1], table, 0, g.off[split2], c->g3_05, fineBlocks, bt); }
   HIPCHK(c, hipEventRecord(c->ev_fine2, sm));
   double area0 = (double)g.ws[0] * g.hs[0];   // the sweeps only cover the window of gated pixels: density inside that window is what counts
-  if (have_table) {
+  if (table.n) {
     // one set of boxes per pair; a batch sweeps the union (a superset of each pair's own window: same results)
     for (int p = 0; p < nb; ++p) {
-      std::vector<int> bp; unsigned cnt = 0;
-      if (int e = wait_gate_boxes(c, sg, epoch, g.n, bp, cnt, p)) return e;
+      std::vector<int> bp(size_t(g.n) * 4); unsigned cnt = 0;
+      if (int e = wait_gate_boxes(c, sg, epoch, g.n, bp.data(), cnt, p)) return e;
       h_cnt += cnt;
       if (p == 0) boxes = bp;
       else for (int l = 0; l < g.n; ++l) {
@@ -319,15 +330,8 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
         boxes[4 * l + 2] = std::max(boxes[4 * l + 2], bp[4 * l + 2]); boxes[4 * l + 3] = std::max(boxes[4 * l + 3], bp[4 * l + 3]);
       }
     }
-    if (!c->cfg.sweep_window) boxes.clear();
-  } else {
-    unsigned* d_cnt = (unsigned*)ensure(c, "gate_count", 256);
-    if (!d_cnt) return PF_ERR_NOMEM;
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4, sg));
-    launch_count_gate(sg, gate, g.ws[0] * g.hs[0], d_cnt);
-    HIPCHK(c, hipMemcpyAsync(&h_cnt, d_cnt, 4, hipMemcpyDeviceToHost, sg));
-    HIPCHK(c, hipStreamSynchronize(sg));
   }
+  if (!c->cfg.sweep_window) boxes.clear();
   if (!boxes.empty() && boxes[2] >= boxes[0] && boxes[3] >= boxes[1]) area0 = double(boxes[2] - boxes[0] + 1) * double(boxes[3] - boxes[1] + 1);
   int sparse = (double)h_cnt < 0.5 * area0 * nb ? 1 : 0;
   if (c->cfg.sparse_sweep >= 0) sparse = c->cfg.sparse_sweep ? 1 : 0;   // forced variant: results are identical either way

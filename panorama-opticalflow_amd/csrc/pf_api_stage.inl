@@ -28,24 +28,25 @@ int pf_stage_pyr_down(pf_ctx* c, const float* src, int sw, int sh, float* dst, i
   STAGE_BEGIN(c);
   float* s = (float*)stage_up(c, "sg_a", src, size_t(sw) * sh * 4); float* d = (float*)ensure(c, "sg_b", size_t(dw) * dh * 4);
   if (!s || !d) return PF_ERR_NOMEM;
-  launch_resize_linear(sm, s, sw, sh, d, dw, dh, 1, 1.f, false);
+  launch_pyr_down4(sm, s, nullptr, nullptr, nullptr, sw, sh, d, nullptr, nullptr, nullptr, dw, dh, Batch(), 1);
   return stage_down(c, dst, d, size_t(dw) * dh * 4);
 }
 int pf_stage_gradients(pf_ctx* c, const float* img, int w, int h, float* gxy) {
   STAGE_BEGIN(c);
   float* s = (float*)stage_up(c, "sg_a", img, size_t(w) * h * 4); float* d = (float*)ensure(c, "sg_b", size_t(w) * h * 8);
   if (!s || !d) return PF_ERR_NOMEM;
-  launch_gradients(sm, s, w, h, d, c->g3_05);
+  LevelTable t{}; t.n = 1; t.w[0] = w; t.h[0] = h;
+  launch_gradients_all(sm, s, nullptr, d, nullptr, t, 0, size_t(w) * h, c->g3_05);
   return stage_down(c, gxy, d, size_t(w) * h * 8);
 }
 int pf_stage_gauss(pf_ctx* c, const float* src, int w, int h, int cn, int ksize, double sigma, float* dst) {
   STAGE_BEGIN(c);
   if (!((ksize == 3 || ksize == 5) && (cn == 1 || cn == 2)) && !(ksize == 15 && cn == 2)) return fail(c, PF_ERR_ARG, "unsupported gaussian %d/%d", ksize, cn);
   const size_t nb = size_t(w) * h * cn * 4;
-  float* s = (float*)stage_up(c, "sg_a", src, nb); float* d = (float*)ensure(c, "sg_b", nb); float* t = (float*)ensure(c, "sg_c", nb);
-  if (!s || !d || !t) return PF_ERR_NOMEM;
+  float* s = (float*)stage_up(c, "sg_a", src, nb); float* d = (float*)ensure(c, "sg_b", nb);
+  if (!s || !d) return PF_ERR_NOMEM;
   const Gauss g = make_gauss(ksize, sigma);
-  if (ksize == 15) launch_gauss15(sm, s, t, d, w, h, g); else launch_gauss_small(sm, s, d, w, h, cn, g);
+  if (ksize == 15) launch_gauss15(sm, s, d, w, h, g); else launch_gauss_small(sm, s, d, w, h, cn, g);
   return stage_down(c, dst, d, nb);
 }
 int pf_stage_median5(pf_ctx* c, const float* flow, int w, int h, float* out) {
@@ -74,7 +75,6 @@ int pf_stage_sweep(pf_ctx* c, const float* g0, const float* g1, const float* blu
   const size_t nb = sweep_boundary_elems(w, h);
   unsigned long long* bnd = (unsigned long long*)ensure(c, "sg_h", nb * 8); int* ctrl = (int*)ensure(c, "sg_i", 16);
   if (!dg0 || !dg1 || !dbl || !da0 || !da1 || !df || !gate || !bnd || !ctrl) return PF_ERR_NOMEM;
-  launch_gate(sm, da0, da1, (int)n, gate);
   launch_fill_u64(sm, bnd, nb, kNotReady);
   HIPCHK(c, hipMemsetAsync(ctrl, 0, 16, sm));
   int* pcnt = (int*)ensure(c, "sg_pc", 2 * size_t(sweep2_num_wgs_max(w, h)) * sizeof(int));
@@ -85,8 +85,8 @@ int pf_stage_sweep(pf_ctx* c, const float* g0, const float* g1, const float* blu
   sa.wide = c->cfg.sweep_wide > 0 ? c->cfg.sweep_wide : 0;   // the sweep form the context was created for (auto = latency form: one pair)
   if (sa.wide == 2) sa.sparse = 0;            // (the throughput form has no sparse variant)
   {
-    std::vector<int> box; LevelTable t; t.n = 1; t.w[0] = w; t.h[0] = h; t.off[0] = 0;
-    if (int e = gate_boxes_to_host(c, sm, gate, t, n, box)) return e;
+    int box[4];
+    if (int e = gate_level(c, sm, da0, da1, gate, w, h, box, nullptr)) return e;
     sa.ax0 = box[0]; sa.ay0 = box[1]; sa.ax1 = box[2] + 1; sa.ay1 = box[3] + 1;
   }
   float* rec = (float*)ensure(c, "sg_rec", sweep2_rec_bytes(w, h));
@@ -109,9 +109,9 @@ int pf_stage_diffusion(pf_ctx* c, const float* a0, const float* a1, float* flow,
   STAGE_BEGIN(c);
   const size_t n = size_t(w) * h;
   float* da0 = (float*)stage_up(c, "sg_a", a0, n * 4); float* da1 = (float*)stage_up(c, "sg_b", a1, n * 4); float* df = (float*)stage_up(c, "sg_c", flow, n * 8);
-  float* t = (float*)ensure(c, "sg_d", n * 8); float* o = (float*)ensure(c, "sg_e", n * 8);
-  if (!da0 || !da1 || !df || !t || !o) return PF_ERR_NOMEM;
-  launch_gauss15_mix(sm, df, t, da0, da1, w, h, c->g15, o);
+  float* o = (float*)ensure(c, "sg_d", n * 8);
+  if (!da0 || !da1 || !df || !o) return PF_ERR_NOMEM;
+  launch_gauss15_mix(sm, df, da0, da1, w, h, c->g15, o);
   return stage_down(c, flow, o, n * 8);
 }
 int pf_stage_upsample_cubic(pf_ctx* c, const float* flow, int sw, int sh, float* out, int dw, int dh, float scale) {
@@ -151,9 +151,7 @@ int pf_stage_level(pf_ctx* c, const float* i0, const float* i1, const float* a0,
   const size_t nb = sweep_boundary_elems(w, h);
   unsigned long long* bnd = (unsigned long long*)ensure(c, "sg_l", nb * 16); int* ctrl = (int*)ensure(c, "sg_m", 16); float* rt = (float*)ensure(c, "sg_n", 256);
   if (!d0 || !d1 || !da0 || !da1 || !g0 || !g1 || !gate || !b.flow_a || !b.flow_b || !b.blurred || !b.tmp || !bnd || !ctrl || !rt) return PF_ERR_NOMEM;
-  launch_gradients(sm, d0, w, h, g0, c->g3_05);
-  launch_gradients(sm, d1, w, h, g1, c->g3_05);
-  launch_gate(sm, da0, da1, (int)n, gate);
+  { LevelTable t{}; t.n = 1; t.w[0] = w; t.h[0] = h; launch_gradients_all(sm, d0, d1, g0, g1, t, 0, n, c->g3_05); }
   launch_fill_u64(sm, bnd, nb * 2, kNotReady);
   HIPCHK(c, hipMemsetAsync(ctrl, 0, 16, sm));
   if (flow_in) HIPCHK(c, hipMemcpyAsync(b.flow_a, flow_in, n * 8, hipMemcpyHostToDevice, sm));
@@ -162,13 +160,13 @@ int pf_stage_level(pf_ctx* c, const float* i0, const float* i1, const float* a0,
     if (max_pct > 0 && hint != PF_HINT_UNKNOWN) launch_adjust_initial_flow(sm, d0, d1, da0, da1, w, h, hint, max_pct, rt, b.flow_a);
   }
   float* res = nullptr;
-  std::vector<int> box;
-  { LevelTable t; t.n = 1; t.w[0] = w; t.h[0] = h; t.off[0] = 0; if (int e = gate_boxes_to_host(c, sm, gate, t, n, box)) return e; }
+  int box[4];
+  if (int e = gate_level(c, sm, da0, da1, gate, w, h, box, nullptr)) return e;
   const size_t npc = size_t(sweep2_num_wgs_max(w, h));
   int* pcnt = (int*)ensure(c, "sg_pc", 2 * npc * sizeof(int));
   if (!pcnt) return PF_ERR_NOMEM;
   HIPCHK(c, hipMemsetAsync(pcnt, 0, 2 * npc * sizeof(int), sm));
-  run_level(c, sm, g0, g1, da0, da1, gate, w, h, (w + h) % 2, box.data(), b, bnd, bnd + nb, ctrl, ctrl + 2, &res, pcnt, pcnt + npc);
+  run_level(c, sm, g0, g1, da0, da1, gate, w, h, (w + h) % 2, box, b, bnd, bnd + nb, ctrl, ctrl + 2, &res, pcnt, pcnt + npc);
   int hc[4] = {0, 0, 0, 0};
   HIPCHK(c, hipMemcpyAsync(hc, ctrl, 16, hipMemcpyDeviceToHost, sm));
   if (int e = stage_down(c, flow_out, res, n * 8)) return e;

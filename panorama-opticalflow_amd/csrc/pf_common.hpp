@@ -103,32 +103,25 @@ struct ExtPtrs { const void* p[kMaxBatch]; };   // caller-owned buffers of the p
 void launch_downscale_gray(hipStream_t st, const uint8_t* bgra, int cols, int rows, int pad, float* gray, float* alpha, int dw, int dh, Batch bt = Batch(),
                            const ExtPtrs* imgs = nullptr /* batched: the pairs' input images instead of bgra */);
 void launch_gauss_small(hipStream_t st, const float* src, float* dst, int w, int h, int cn, const Gauss& g, Batch bt = Batch());
-void launch_resize_linear(hipStream_t st, const float* src, int sw, int sh, float* dst, int dw, int dh, int cn, float mul, bool do_mul);
 void launch_pyr_down4(hipStream_t st, const float* s0, const float* s1, const float* s2, const float* s3, int sw, int sh, float* d0,
-                      float* d1, float* d2, float* d3, int dw, int dh, Batch bt = Batch());
+                      float* d1, float* d2, float* d3, int dw, int dh, Batch bt = Batch(), int nplanes = 4 /* 1..4 of the planes */);
 void launch_pyr_chain4(hipStream_t st, float* p0, float* p1, float* p2, float* p3, const int* ws, const int* hs, const size_t* off, int first, int k,
                        Batch bt = Batch());
-void launch_pyr_down2(hipStream_t st, const float* s0, const float* s1, int sw, int sh, float* d0, float* d1, int dw, int dh);
-// per level
-void launch_gradients(hipStream_t st, const float* img, int w, int h, float* gxy, const Gauss& g3);
 // offsets/sizes of the pyramid levels inside one pyramid plane, passed by value to kernels that cover all levels at once
 constexpr int kLevelTableMax = 96;
 struct LevelTable { int n; int w[kLevelTableMax]; int h[kLevelTableMax]; unsigned off[kLevelTableMax]; };
-void launch_gate_bbox(hipStream_t st, const uint8_t* gate, const LevelTable& t, size_t total, int* box);   // box[4*l..]: min x, min y, max x, max y
-// elements [first, total) of the pyramid planes (levels lie back to back, level 0 first)
+// elements [first, total) of the pyramid planes (levels lie back to back, level 0 first); pyr1 == nullptr: one image
 void launch_gradients_all(hipStream_t st, const float* pyr0, const float* pyr1, float* grad0, float* grad1, const LevelTable& t, size_t first,
                           size_t total, const Gauss& g3, int max_blocks = 0, Batch bt = Batch());
-void launch_gate(hipStream_t st, const float* a0, const float* a1, int n, uint8_t* gate);
 // gate + per-level bounding boxes + level-0 count in one launch, published to mapped pinned host memory behind an epoch flag
-// (work: 4*kLevelTableMax + 2 ints, initialised once to (INT_MAX, INT_MAX, -1, -1)*, 0, 0; host_mapped: same size)
+// (work: 4*kLevelTableMax + 2 ints, initialised once to (INT_MAX, INT_MAX, -1, -1)*, 0, 0; host_mapped: same size);
+// work[4*l..]: min x, min y, max x, max y of level l
 void launch_gate_bbox_all(hipStream_t st, const float* a0, const float* a1, uint8_t* gate, const LevelTable& t, size_t total, int* work, int* host_mapped,
                           int epoch, Batch bt = Batch(), size_t host_stride = 0 /* bytes between the pairs' mapped host areas */);
-void launch_count_gate(hipStream_t st, const uint8_t* gate, int n, unsigned* count /* zeroed by the caller */);
-void launch_gauss15(hipStream_t st, const float* src, float* tmp, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch());
+void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch());
 void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch());
 void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh, float mul, float* up, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch());
-void launch_gauss15_mix(hipStream_t st, float* flow, float* tmp, const float* a0, const float* a1, int w, int h, const Gauss& g15,
-                        float* out, Batch bt = Batch());
+void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch());
 void launch_median5(hipStream_t st, const float* src, float* dst, int w, int h, Batch bt = Batch());   // direct form below 3 Mpix, LDS-tiled form above
 void launch_median5_form(hipStream_t st, const float* src, float* dst, int w, int h, bool tiled, Batch bt = Batch());   // a given form at any size (tests)
 void launch_upsample_cubic(hipStream_t st, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul, Batch bt = Batch());

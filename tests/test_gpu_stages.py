@@ -48,8 +48,17 @@ def test_pyr_down(ctx, orc):
         src = ref
 
 
-def test_gradients(ctx, orc):
-    img = rng.random((97, 131)).astype(np.float32)
+# k_gradients_all on a one-level table: a thread takes four consecutive pixels, as one quad away from the border, else one by one
+@pytest.mark.parametrize("w,h", [
+    (131, 97),   # w % 4 = 3: groups straddle rows; 13 blocks
+    (64, 9),     # w % 4 = 0: every group inside a row, quad-interior on almost all of them
+    (26, 24),    # the pyramid's smallest real level size
+    (7, 5),      # w < 9: no group qualifies for the quad path; single-pixel interior + border only
+    (40, 4),     # h < 5: no interior row at all
+    (2, 2),      # the smallest level check_dims admits
+])
+def test_gradients(ctx, orc, w, h):
+    img = np.random.default_rng(1000 * w + h).random((h, w)).astype(np.float32)
     ix, iy = orc.gradients(img)
     g = ctx.stage_gradients(img)
     assert np.array_equal(g[..., 0], ix) and np.array_equal(g[..., 1], iy)
@@ -384,3 +393,14 @@ def test_product_library_ships_one_sweep(pf):
     blob = open(pf.SO_PATH, "rb").read()
     assert b"PANOFLOW_" not in blob and b"k_sweep_relax" not in blob
     assert b"k_sweep_relax" in open(pf.SO_PATH_EXP, "rb").read()
+
+
+def test_libraries_ship_one_kernel_per_front_end_stage(pf):
+    """The first-generation per-level kernels (gradients, gate, gate boxes, gate count, two-kernel Gaussian 15, bilinear resize) are in
+    neither library: the stage tests above and a solve run the same kernels.  Mangled names where a surviving kernel's name starts
+    with a removed one's (k_gradients_all, k_gate_bbox_all)."""
+    gone = [b"2pf11k_gradientsE", b"2pf6k_gateE", b"2pf11k_gate_bboxE", b"k_count_gate", b"k_gauss15_row", b"k_gauss15_col", b"k_resize_linear"]
+    for path in (pf.SO_PATH, pf.SO_PATH_EXP):
+        blob = open(path, "rb").read()
+        assert b"2pf15k_gradients_allE" in blob and b"2pf15k_gate_bbox_allE" in blob   # the name scheme this test relies on
+        assert [n for n in gone if n in blob] == [], path
