@@ -211,6 +211,45 @@ int pf_stitch_step_batch(pf_ctx* ctx, int n_frames, const uint8_t* const* l_bgra
 int pf_stitch_step_batch_dev(pf_ctx* ctx, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows,
                              int max_percentage, uint8_t* const* d_out, int in_flight);
 
+/* ---- stitch plans: one rig's overlap map and blend ramp, reused across frames ----------------
+ * Stitchtools::prepare derives Map (MatchImages, CPU/StitchTool.cpp:38-50) and the blend ramp (GenerateBlend, :98-146) from the two
+ * alpha masks alone, and Gather (:52-96) gives the composite an alpha that is > 0 exactly where L's or R's is -- so for a fixed camera
+ * rig every frame of a step has the same map and ramp.  A plan holds them in HBM (5 B/px: map 1, ramp 4) with cols, rows and the
+ * overlap pixel count; a planned step uses them instead of recomputing them: no countblend, tile-smoothing or box-blur launch, no
+ * blend-ramp stream, and 12 B/px of StitchTool planes per frame in flight (two overlap images and the novel view) instead of 33.
+ * A planned step VERIFIES: its match kernel derives every pixel's region code (100 = L only, 50 = R only, 150 = both, 0 = none) from
+ * the frame's alphas and compares it with the plan's.  The bytes of a planned call are those of the unplanned call on the same
+ * inputs; a call in which any frame differs from the plan in even one pixel's code (alpha 255 -> 0 or 0 -> 1 does, 255 -> 1 does not)
+ * fails as a whole with PF_ERR_ARG -- pf_last_error names the first such frame and its pixel count --, delivers no composite (the host
+ * forms download nothing, the device form zero-fills every d_out of the call) and leaves nothing to chain on.
+ * A plan belongs to the context that made it: passing it to another context (hence another device), after pf_stitch_plan_destroy, or
+ * with another cols x rows is PF_ERR_ARG before any work (a handle is looked up in the context's list, never dereferenced first).
+ * Creation runs the kernels of pf_stitch_prepare, accepts and refuses the canvases pf_stitch_step does, and leaves the chain state,
+ * the prefetch records and pf_stitch_visualize's inputs alone.  r_bgra == NULL takes the R mask from the composite pf_stitch_step /
+ * pf_stitch_step_planned left in HBM (PF_ERR_ARG if there is none of this size).  pf_destroy frees the plans still alive. */
+typedef struct pf_stitch_plan pf_stitch_plan;
+int pf_stitch_plan_create(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int cols, int rows, size_t step_bytes,
+                          pf_stitch_plan** plan_out);
+int pf_stitch_plan_create_dev(pf_ctx* ctx, const uint8_t* d_l, const uint8_t* d_r, int cols, int rows, pf_stitch_plan** plan_out);
+int pf_stitch_plan_destroy(pf_ctx* ctx, pf_stitch_plan* plan);
+/* geometry of a LIVE plan (outputs may be NULL) */
+int pf_stitch_plan_info(const pf_stitch_plan* plan, int* cols, int* rows, long long* overlap_px);
+/* the plan's Map (1 B/px) and finished ramp (4 B/px, what pf_stitch_prepare gives as blend_out); either output may be NULL */
+int pf_stitch_plan_download(pf_ctx* ctx, const pf_stitch_plan* plan, uint8_t* map_out, size_t map_step_bytes, float* blend_out,
+                            size_t blend_step_bytes);
+/* pf_stitch_step with a plan: the same arguments, chain state ("r_bgra == NULL" chains on the last composite whichever of the two
+ * calls made it), pf_stitch_prefetch records and pf_stitch_visualize inputs; the same bytes. */
+int pf_stitch_step_planned(pf_ctx* ctx, const pf_stitch_plan* plan, const uint8_t* l_bgra, const uint8_t* r_bgra, int cols, int rows,
+                           size_t step_bytes, int max_percentage, uint8_t* out_bgra, size_t out_step_bytes);
+/* pf_stitch_step_batch / _dev with ONE plan for all frames; the host form shares the unplanned one's frame slots, so the two may be
+ * interleaved step by step.  HBM per frame in flight: 12 B/px of StitchTool planes + 16 B/px of flows + the solver slab. */
+int pf_stitch_step_batch_planned(pf_ctx* ctx, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* l_bgra,
+                                 const uint8_t* const* r_bgra, int cols, int rows, size_t step_bytes, int max_percentage,
+                                 uint8_t* const* out_bgra, size_t out_step_bytes, int in_flight);
+int pf_stitch_step_batch_planned_dev(pf_ctx* ctx, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* d_l,
+                                     const uint8_t* const* d_r, int cols, int rows, int max_percentage, uint8_t* const* d_out,
+                                     int in_flight);
+
 /* ---- device-resident entry points (packed buffers already in this context's HBM) -----------
  * Same semantics as above; used by bench.py (inputs resident when the clock starts) and by the
  * multi-GPU driver.  Pointers are device pointers on the context's device.  The calls are synchronous on

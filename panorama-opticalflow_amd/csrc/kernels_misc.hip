@@ -272,6 +272,76 @@ void launch_match_images(hipStream_t st, const StitchPtrs& p, int nf, int cols, 
   const int n = cols * rows;
   hipLaunchKernelGGL(k_match_images, dim3((n + 255) / 256, 1, nf), dim3(256), 0, st, p, n);
 }
+// K12 against a stitch plan: p.map[z] is the PLAN's map (read, never written).  Frame z's region code is derived from its two alphas as
+// above and COMPARED with the plan's; the overlap-masked images are written from the plan's code, so the step that follows is well
+// defined whatever the frame holds.  Differing pixels are counted per frame into diff[z], a word of mapped host memory that the host
+// reads after the call's final sync (the sweep status word's mechanism): a wave that saw none -- every wave of a matching frame --
+// issues no atomic at all.  HBM-streaming: 4 pixels per thread, 16-byte loads and stores (4-byte map load); `vec` = every image
+// pointer of the launch is 16-byte aligned (caller-owned inputs of the device form need not be); the last n % 4 pixels go one by one.
+__global__ __launch_bounds__(256) void k_match_verify(StitchPtrs p, int n, int vec, unsigned* __restrict__ diff) {
+  const int z = blockIdx.z;
+  const uint32_t* __restrict__ L = reinterpret_cast<const uint32_t*>(p.L[z]);
+  const uint32_t* __restrict__ R = reinterpret_cast<const uint32_t*>(p.R[z]);
+  const uint8_t* __restrict__ map = p.map[z];
+  uint32_t* __restrict__ ovL = reinterpret_cast<uint32_t*>(p.ovL[z]);
+  uint32_t* __restrict__ ovR = reinterpret_cast<uint32_t*>(p.ovR[z]);
+  const long long i0 = (long long)(blockIdx.x * 256u + threadIdx.x) * 4;
+  unsigned d = 0;
+  // alpha is the top byte of a little-endian BGRA word
+  auto px = [&d](uint32_t l, uint32_t r, uint32_t m, uint32_t& ol, uint32_t& orr) {
+    const uint32_t code = (l >> 24 ? 100u : 0u) + (r >> 24 ? 50u : 0u);
+    d += code != m;
+    const bool ov = m > 140;
+    ol = ov ? l : 0u; orr = ov ? r : 0u;
+  };
+  if (vec && i0 + 3 < n) {
+    const uint4 l = *reinterpret_cast<const uint4*>(L + i0), r = *reinterpret_cast<const uint4*>(R + i0);
+    const uint32_t m4 = *reinterpret_cast<const uint32_t*>(map + i0);
+    uint4 ol, orr;
+    px(l.x, r.x, m4 & 0xffu, ol.x, orr.x);
+    px(l.y, r.y, (m4 >> 8) & 0xffu, ol.y, orr.y);
+    px(l.z, r.z, (m4 >> 16) & 0xffu, ol.z, orr.z);
+    px(l.w, r.w, m4 >> 24, ol.w, orr.w);
+    *reinterpret_cast<uint4*>(ovL + i0) = ol;
+    *reinterpret_cast<uint4*>(ovR + i0) = orr;
+  } else {
+    for (long long i = i0; i < i0 + 4 && i < n; ++i) {
+      uint32_t ol, orr;
+      px(L[i], R[i], map[i], ol, orr);
+      ovL[i] = ol; ovR[i] = orr;
+    }
+  }
+  // every thread arrives here (no early return above): the vote and the shuffles see whole waves
+  if (__any(d != 0)) {
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o);
+    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(diff + z, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+void launch_match_verify(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, unsigned* diff_mapped) {
+  const int n = cols * rows;
+  uintptr_t bits = 0;
+  for (int f = 0; f < nf; ++f) bits |= (uintptr_t)p.L[f] | (uintptr_t)p.R[f] | (uintptr_t)p.ovL[f] | (uintptr_t)p.ovR[f] | ((uintptr_t)p.map[f] << 2);
+  hipLaunchKernelGGL(k_match_verify, dim3((n + 1023) / 1024, 1, nf), dim3(256), 0, st, p, n, (bits & 15) == 0 ? 1 : 0, diff_mapped);
+}
+// pixels of a map that carry `code` (a plan's overlap count): 16 bytes per thread and trip, one device-scope atomic per wave that saw any
+__global__ __launch_bounds__(256) void k_count_code(const uint8_t* __restrict__ map, int n, unsigned code, unsigned* __restrict__ count) {
+  const uint4* __restrict__ m16 = reinterpret_cast<const uint4*>(map);
+  const int n16 = n / 16;
+  const unsigned tid = blockIdx.x * 256u + threadIdx.x, nthreads = gridDim.x * 256u;
+  unsigned c = 0;
+  auto word = [&c, code](uint32_t w) { c += ((w & 0xffu) == code) + (((w >> 8) & 0xffu) == code) + (((w >> 16) & 0xffu) == code) + ((w >> 24) == code); };
+  for (unsigned i = tid; i < (unsigned)n16; i += nthreads) { const uint4 v = m16[i]; word(v.x); word(v.y); word(v.z); word(v.w); }
+  if (tid < (unsigned)(n - n16 * 16)) c += map[n16 * 16 + tid] == code;
+  if (__any(c != 0)) {
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0) atomicAdd(count, c);
+  }
+}
+void launch_count_code(hipStream_t st, const uint8_t* map, int cols, int rows, int code, unsigned* count) {
+  const int n = cols * rows;
+  int blocks = (n / 16 + 255) / 256; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_count_code, dim3(blocks), dim3(256), 0, st, map, n, (unsigned)code, count);
+}
 
 // ------------------------------------------------------------------------------------------------
 // K13 GenerateBlend's per-pixel part + countblend (StitchTool.cpp:98-128, :148-191).  The map extended

@@ -14,6 +14,15 @@ struct ProfPending { int id; hipEvent_t a, b; };
 
 }  // namespace
 
+// A stitch plan (pf_stitch_plan_create): what Stitchtools::prepare derives from the two alpha masks alone, kept in HBM for every
+// later step on the same masks.  5 B/px; owned by the context whose `plans` list holds it, which is what makes a handle valid.
+struct pf_stitch_plan {
+  int cols = 0, rows = 0;
+  long long overlap_px = 0;   // pixels of code 150
+  uint8_t* map = nullptr;     // Map, 1 B/px
+  float* ramp = nullptr;      // the finished blend ramp, 4 B/px
+};
+
 struct pf_ctx {
   int device = 0;
   hipStream_t s_main = nullptr, s_dir[2] = {nullptr, nullptr}, s_aux = nullptr;
@@ -54,6 +63,9 @@ struct pf_ctx {
   int* h_gate = nullptr; int* d_gate = nullptr; int gate_epoch = 0;   // mapped pinned: per-level gate boxes + count + epoch flag (k_gate_bbox_all)
   int* h_status = nullptr;              // mapped pinned host word: bit d set = a sweep band of direction d timed out
   int* d_status = nullptr;              // the same word as the device sees it
+  unsigned* h_plan_diff = nullptr;      // mapped pinned, kMaxBatch words: pixels of frame f of a planned group whose region code differs from the plan's
+  unsigned* d_plan_diff = nullptr;      // (k_match_verify adds, the host reads after the group's final sync and zeroes)
+  std::vector<pf_stitch_plan*> plans;   // the stitch plans this context owns (pf_stitch_plan_create .. _destroy / pf_destroy)
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;
   std::vector<ProfPending> prof_pending;

@@ -116,7 +116,9 @@ pf_ctx* create_ctx(const pf_config& cfg, bool lane) {
   ok = ok && hipHostMalloc((void**)&c->h_status, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void**)&c->d_status, c->h_status, 0) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->h_gate, kMaxBatch * kGateWords * sizeof(int), hipHostMallocMapped) == hipSuccess &&   // one area per pair of a batch
        hipHostGetDevicePointer((void**)&c->d_gate, c->h_gate, 0) == hipSuccess;
-  if (ok) { *c->h_status = 0; memset(c->h_gate, 0, kMaxBatch * kGateWords * sizeof(int)); }
+  ok = ok && hipHostMalloc((void**)&c->h_plan_diff, kMaxBatch * sizeof(unsigned), hipHostMallocMapped) == hipSuccess &&
+       hipHostGetDevicePointer((void**)&c->d_plan_diff, c->h_plan_diff, 0) == hipSuccess;
+  if (ok) { *c->h_status = 0; memset(c->h_gate, 0, kMaxBatch * kGateWords * sizeof(int)); memset(c->h_plan_diff, 0, kMaxBatch * sizeof(unsigned)); }
   if (!ok) { fail(nullptr, PF_ERR_DEVICE, "stream/event creation failed"); delete c; return nullptr; }
   c->cfg = cfg;
   {
@@ -212,6 +214,7 @@ void pf_destroy(pf_ctx* c) {
   hipSetDevice(c->device);
   hipDeviceSynchronize();
   for (auto& kv : c->bufs) if (kv.second.p) hipFree(kv.second.p);
+  for (pf_stitch_plan* pl : c->plans) { hipFree(pl->map); hipFree(pl->ramp); delete pl; }
   for (auto e : c->ev_pool) hipEventDestroy(e);
   for (auto& p : c->prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   if (c->ev_pre) hipEventDestroy(c->ev_pre);
@@ -228,6 +231,7 @@ void pf_destroy(pf_ctx* c) {
   if (c->s_main) hipStreamDestroy(c->s_main);
   if (c->h_status) hipHostFree(c->h_status);
   if (c->h_gate) hipHostFree(c->h_gate);
+  if (c->h_plan_diff) hipHostFree(c->h_plan_diff);
   delete c;
 }
 

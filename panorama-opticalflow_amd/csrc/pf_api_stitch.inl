@@ -65,22 +65,32 @@ static int blend_ramp_dev(pf_ctx* c, hipStream_t sm, const StitchPtrs& p, int co
 // One iteration of the reference's stitch loop (CPU/main.cpp:70-95) for `count` frames on device planes the caller supplies (p: all
 // but L / R / out are working planes; w and p.rs / p.tmp from ramp_planes; flows[2f], flows[2f + 1]: frame f's two flow planes):
 // Stitchtools::prepare -> NovelViewGeneratorAsymmetricFlow::prepare/generateNovelView -> Gather, enqueued, not drained.
-static int stitch_step_dev(pf_ctx* c, const StitchPtrs& p, int count, float* const* flows, int cols, int rows, int max_pct, const RampGeom& g, const RampWork& w) {
+// With a plan (stitch plans, further down): p.map[f] = the plan's map for every frame, the match verifies against it
+// (c->h_plan_diff[f], read by the caller after its final sync), the ramp is the plan's, and there is no ramp launch, stream or event.
+static int stitch_step_dev(pf_ctx* c, const StitchPtrs& p, int count, float* const* flows, int cols, int rows, int max_pct, const RampGeom& g, const RampWork& w,
+                           const pf_stitch_plan* plan = nullptr) {
   hipStream_t sm = c->s_main;
-  { PROF(c, sm, "match_images"); launch_match_images(sm, p, count, cols, rows); }
-  // The blend ramp only depends on the map and is only needed by the final blend: it runs on its own stream beside the two flow
-  // solves.  Its launches (a dozen since the tile smoothing became ONE persistent launch in round 3; ~850 before) are enqueued AFTER
-  // the solver's, so that the solver's first kernel is not kept waiting by them.
-  if (!c->s_aux) HIPCHK(c, hipStreamCreateWithFlags(&c->s_aux, hipStreamNonBlocking));
-  hipStream_t sa = c->s_aux;
-  HIPCHK(c, hipEventRecord(c->ev_aux_go, sm));
   const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT};
-  if (int e = solve_n(c, count, p.ovL, p.ovR, cols, rows, cols / 20, max_pct, 2, hints, flows)) return e;
-  HIPCHK(c, hipStreamWaitEvent(sa, c->ev_aux_go, 0));
   BlendPtrs bp{};
-  if (int e = blend_ramp_dev(c, sa, p, count, cols, rows, g, w, true, bp.blend)) return e;
-  HIPCHK(c, hipEventRecord(c->ev_aux_done, sa));
-  HIPCHK(c, hipStreamWaitEvent(sm, c->ev_aux_done, 0));
+  if (plan) {
+    for (int f = 0; f < count; ++f) c->h_plan_diff[f] = 0;
+    { PROF(c, sm, "match_verify"); launch_match_verify(sm, p, count, cols, rows, c->d_plan_diff); }
+    if (int e = solve_n(c, count, p.ovL, p.ovR, cols, rows, cols / 20, max_pct, 2, hints, flows)) return e;
+    for (int f = 0; f < count; ++f) bp.blend[f] = plan->ramp;
+  } else {
+    { PROF(c, sm, "match_images"); launch_match_images(sm, p, count, cols, rows); }
+    // The blend ramp only depends on the map and is only needed by the final blend: it runs on its own stream beside the two flow
+    // solves.  Its launches (a dozen since the tile smoothing became ONE persistent launch in round 3; ~850 before) are enqueued AFTER
+    // the solver's, so that the solver's first kernel is not kept waiting by them.
+    if (!c->s_aux) HIPCHK(c, hipStreamCreateWithFlags(&c->s_aux, hipStreamNonBlocking));
+    hipStream_t sa = c->s_aux;
+    HIPCHK(c, hipEventRecord(c->ev_aux_go, sm));
+    if (int e = solve_n(c, count, p.ovL, p.ovR, cols, rows, cols / 20, max_pct, 2, hints, flows)) return e;
+    HIPCHK(c, hipStreamWaitEvent(sa, c->ev_aux_go, 0));
+    if (int e = blend_ramp_dev(c, sa, p, count, cols, rows, g, w, true, bp.blend)) return e;
+    HIPCHK(c, hipEventRecord(c->ev_aux_done, sa));
+    HIPCHK(c, hipStreamWaitEvent(sm, c->ev_aux_done, 0));
+  }
   for (int f = 0; f < count; ++f) { bp.L[f] = p.ovL[f]; bp.R[f] = p.ovR[f]; bp.fLR[f] = flows[2 * f]; bp.fRL[f] = flows[2 * f + 1]; bp.out[f] = p.merged[f]; }
   { PROF(c, sm, "blend"); launch_blend(sm, bp, count, cols, rows); }
   { PROF(c, sm, "gather"); launch_gather(sm, p, count, cols, rows); }
@@ -230,27 +240,49 @@ static uint64_t host_image_sig(const uint8_t* p, int cols, int rows, size_t step
   return h;
 }
 
-int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, int max_pct, uint8_t* out, size_t ostep) {
+// a handle is valid if the context lists it (no dereference before that: a destroyed plan, or another context's, is refused by address)
+static int check_plan(pf_ctx* c, const pf_stitch_plan* plan, int cols, int rows, const char* what) {
+  if (std::find(c->plans.begin(), c->plans.end(), plan) == c->plans.end()) return fail(c, PF_ERR_ARG, "%s: not a live stitch plan of this context", what);
+  if (plan->cols != cols || plan->rows != rows) return fail(c, PF_ERR_ARG, "%s: the plan is %dx%d, the canvas %dx%d", what, plan->cols, plan->rows, cols, rows);
+  return 0;
+}
+// after the final sync of a planned group of `count` frames (first = index of its frame 0 in the call): pixels per frame that differ
+// from the plan, into diff[first ..] (the caller reports); the words are left zeroed
+static void collect_plan_diff(pf_ctx* lane, int first, int count, unsigned* diff) {
+  for (int f = 0; f < count; ++f) { diff[first + f] = __atomic_load_n(lane->h_plan_diff + f, __ATOMIC_ACQUIRE); lane->h_plan_diff[f] = 0; }
+}
+// (tools/pano_stitch.cpp reads the frame index out of this message to name the directory: keep "frame %d differs from the stitch plan")
+static int report_plan_diff(pf_ctx* c, const char* what, const unsigned* diff, int n_frames) {
+  for (int k = 0; k < n_frames; ++k)
+    if (diff[k]) return fail(c, PF_ERR_ARG, "%s: frame %d differs from the stitch plan in %u pixels' region codes (alpha masks are not the plan's)", what, k, diff[k]);
+  return 0;
+}
+
+static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, int max_pct, uint8_t* out, size_t ostep) {
+  const char* const what = plan ? "pf_stitch_step_planned" : "pf_stitch_step";
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!l) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  if (plan) if (int e = check_plan(c, plan, cols, rows, what)) return e;
   if (step < size_t(cols) * 4 || (out && ostep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
-  check_hw_queues(c, 5, "pf_stitch_step");   // front end, two flow directions, blend ramp, prefetch copy
+  check_hw_queues(c, plan ? 4 : 5, what);   // front end, two flow directions, blend ramp (unplanned), prefetch copy
   c->vis_step_valid = false;
   const size_t n = size_t(cols) * rows;
   uint8_t* dl = (uint8_t*)ensure(c, "ch_l", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "ch_r", n * 4); uint8_t* dfin = (uint8_t*)ensure(c, "ch_final", n * 4);
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4); uint8_t* dmerged = (uint8_t*)ensure(c, "st_merged", n * 4);
+  // a planned step needs neither a map nor ramp planes of its own
+  uint8_t* dm = plan ? plan->map : (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
+  float* db = plan ? nullptr : (float*)ensure(c, "st_blend", n * 4); float* dmd = plan ? nullptr : (float*)ensure(c, "st_md", n * 4);
+  uint8_t* dmerged = (uint8_t*)ensure(c, "st_merged", n * 4);
   float* f0 = (float*)ensure(c, "nv_flow_l2r", n * 8); float* f1 = (float*)ensure(c, "nv_flow_r2l", n * 8);
-  if (!dl || !dr || !dfin || !dm || !dol || !dor || !db || !dmd || !dmerged || !f0 || !f1) return PF_ERR_NOMEM;
+  if (!dl || !dr || !dfin || !dm || !dol || !dor || (!plan && (!db || !dmd)) || !dmerged || !f0 || !f1) return PF_ERR_NOMEM;
   hipStream_t sm = c->s_main;
   uint8_t* dnext = (uint8_t*)ensure(c, "ch_l_next", n * 4);
   if (!dnext) return PF_ERR_NOMEM;
   const RampGeom g = ramp_geom(cols, rows);
   StitchPtrs p{};
   RampWork w;
-  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
+  if (!plan) if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   // both prefetch records are one-shot: latched and cleared here, whatever this step does with them
   const pf_ctx::HostImage ready = c->ready, hint = c->hint;
   c->ready = pf_ctx::HostImage(); c->hint = pf_ctx::HostImage();
@@ -264,22 +296,44 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
   }
   if (r) { if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e; }
   else {
-    if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "pf_stitch_step: no previous result of this size to chain on");
+    if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "%s: no previous result of this size to chain on", what);
     HIPCHK(c, hipMemcpyAsync(dr, dfin, n * 4, hipMemcpyDeviceToDevice, sm));
   }
   if (!c->s_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
   p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd; p.merged[0] = dmerged; p.out[0] = dfin;
   float* const flows[2] = {f0, f1};
-  if (int e = stitch_step_dev(c, p, 1, flows, cols, rows, max_pct, g, w)) return e;
-  if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  // "ch_final" is rewritten from here on; a frame that fails the plan leaves nothing to chain on.  (So does a planned step that fails for
+  // any other reason, e.g. an allocation inside the solve, where the unplanned step keeps the old chain size: the composite it
+  // would chain on is being overwritten either way, and the planned step says so.)
+  if (plan) { c->chain_cols = c->chain_rows = 0; }
+  if (int e = stitch_step_dev(c, p, 1, flows, cols, rows, max_pct, g, w, plan)) return e;
   // everything of this step is enqueued: upload the NEXT step's left image now (announced with pf_stitch_prefetch); the
   // host-side staging of a pageable source runs while the GPU computes
-  if (hint.src && hint.src != l && hint.cols == cols && hint.rows == rows) {
-    if (hint.step == size_t(cols) * 4) HIPCHK(c, hipMemcpyAsync(dnext, hint.src, n * 4, hipMemcpyHostToDevice, c->s_copy));
-    else HIPCHK(c, hipMemcpy2DAsync(dnext, size_t(cols) * 4, hint.src, hint.step, size_t(cols) * 4, rows, hipMemcpyHostToDevice, c->s_copy));
-    HIPCHK(c, hipStreamSynchronize(c->s_copy));
-    c->ready = hint;
-    c->ready.sig = host_image_sig(hint.src, cols, rows, hint.step);
+  auto prefetch_next = [&]() -> int {
+    if (hint.src && hint.src != l && hint.cols == cols && hint.rows == rows) {
+      if (hint.step == size_t(cols) * 4) HIPCHK(c, hipMemcpyAsync(dnext, hint.src, n * 4, hipMemcpyHostToDevice, c->s_copy));
+      else HIPCHK(c, hipMemcpy2DAsync(dnext, size_t(cols) * 4, hint.src, hint.step, size_t(cols) * 4, rows, hipMemcpyHostToDevice, c->s_copy));
+      HIPCHK(c, hipStreamSynchronize(c->s_copy));
+      c->ready = hint;
+      c->ready.sig = host_image_sig(hint.src, cols, rows, hint.step);
+    }
+    return 0;
+  };
+  if (!plan) {
+    if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+    if (int e = prefetch_next()) return e;
+  } else {
+    // the composite goes to the caller only once the frame is known to match the plan: the step is drained (the prefetch upload ran
+    // beside it), the word read, and only then the download enqueued
+    if (int e = prefetch_next()) return e;
+    HIPCHK(c, hipGetLastError());
+    if (int e = finish(c)) return e;
+    unsigned diff = 0;
+    collect_plan_diff(c, 0, 1, &diff);
+    if (int e = check_sweeps(c)) return e;
+    if (int e = report_plan_diff(c, what, &diff, 1)) return e;
+    c->drained = false;   // the download below is this call's work again
+    if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   }
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
@@ -287,6 +341,16 @@ int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int 
   if (int e = check_sweeps(c)) return e;
   c->vis_step_valid = true;
   return 0;
+}
+
+int pf_stitch_step(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, int max_pct, uint8_t* out, size_t ostep) {
+  return stitch_step_lone(c, nullptr, l, r, cols, rows, step, max_pct, out, ostep);
+}
+int pf_stitch_step_planned(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, int max_pct, uint8_t* out,
+                           size_t ostep) {
+  if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
+  if (!plan) return fail(c, PF_ERR_ARG, "pf_stitch_step_planned: null plan");
+  return stitch_step_lone(c, plan, l, r, cols, rows, step, max_pct, out, ostep);
 }
 
 // Announce the left image of the pf_stitch_step call AFTER the coming one: the coming step uploads it while its own kernels run
@@ -314,33 +378,37 @@ int check_stitch_canvas(pf_ctx* c, int cols, int rows, int max_pct) {
   if (max_pct < 0 || max_pct > 100) return fail(c, PF_ERR_ARG, "max_percentage %d out of range", max_pct);
   return 0;
 }
+// plan != nullptr: a planned group -- every frame on the plan's map and ramp, 12 B/px of StitchTool planes per frame (overlaps 8,
+// novel view 4) instead of 33; diff[first ..] receives the frames' counts of pixels that differ from the plan (the call reports them)
 int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
-                 uint8_t* const* d_out) {
+                 uint8_t* const* d_out, const pf_stitch_plan* plan = nullptr, unsigned* diff = nullptr) {
   if (int e = use(lane)) return e;
   CallGuard guard_(lane);
   const size_t n = size_t(cols) * rows;
   const RampGeom g = ramp_geom(cols, rows);
   // 33 B/px of StitchTool planes per frame (map 1, overlaps 8, ramp + MergedDis 8, box blur 12, novel view 4) + 16 B/px of flows
-  size_t s1, s4, s16;
-  uint8_t* map = frame_planes<uint8_t>(lane, "sb_map", count, n, s1);
+  size_t s1 = 0, s4, s16;
+  uint8_t* map = plan ? plan->map : frame_planes<uint8_t>(lane, "sb_map", count, n, s1);
   uint8_t* ovl = frame_planes<uint8_t>(lane, "sb_ovl", count, n * 4, s4); uint8_t* ovr = frame_planes<uint8_t>(lane, "sb_ovr", count, n * 4, s4);
-  float* blend = frame_planes<float>(lane, "sb_blend", count, n * 4, s4); float* md = frame_planes<float>(lane, "sb_md", count, n * 4, s4);
+  float* blend = plan ? nullptr : frame_planes<float>(lane, "sb_blend", count, n * 4, s4); float* md = plan ? nullptr : frame_planes<float>(lane, "sb_md", count, n * 4, s4);
   uint8_t* merged = frame_planes<uint8_t>(lane, "sb_merged", count, n * 4, s4);
   float* flow = frame_planes<float>(lane, "sb_flow", count, n * 16, s16);
-  if (!map || !ovl || !ovr || !blend || !md || !merged || !flow) return PF_ERR_NOMEM;
+  if (!map || !ovl || !ovr || (!plan && (!blend || !md)) || !merged || !flow) return PF_ERR_NOMEM;
   StitchPtrs sp{};
   RampWork w;
-  if (int e = ramp_planes(lane, kRampBatch, count, cols, rows, g, sp, w)) return e;
+  if (!plan) if (int e = ramp_planes(lane, kRampBatch, count, cols, rows, g, sp, w)) return e;
   float* flows[2 * kMaxBatch];
   for (int p = 0; p < count; ++p) {
     sp.L[p] = d_l[first + p]; sp.R[p] = d_r[first + p]; sp.out[p] = d_out[first + p];
     sp.map[p] = map + p * s1; sp.ovL[p] = ovl + p * s4; sp.ovR[p] = ovr + p * s4;
-    sp.blend[p] = (float*)((char*)blend + p * s4); sp.md[p] = (float*)((char*)md + p * s4); sp.merged[p] = merged + p * s4;
+    if (!plan) { sp.blend[p] = (float*)((char*)blend + p * s4); sp.md[p] = (float*)((char*)md + p * s4); }
+    sp.merged[p] = merged + p * s4;
     flows[2 * p] = (float*)((char*)flow + p * s16); flows[2 * p + 1] = flows[2 * p] + n * 2;
   }
-  if (int e = stitch_step_dev(lane, sp, count, flows, cols, rows, max_pct, g, w)) return e;
+  if (int e = stitch_step_dev(lane, sp, count, flows, cols, rows, max_pct, g, w, plan)) return e;
   HIPCHK(lane, hipGetLastError());
   if (int e = finish(lane)) return e;
+  if (plan) collect_plan_diff(lane, first, count, diff);
   return check_sweeps(lane);
 }
 bool overlaps(const void* a, const void* b, size_t bytes) {
@@ -349,11 +417,12 @@ bool overlaps(const void* a, const void* b, size_t bytes) {
 }
 }  // namespace
 
-int pf_stitch_step_batch_dev(pf_ctx* c, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
-                             uint8_t* const* d_out, int in_flight) {
+static int stitch_batch_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
+                            uint8_t* const* d_out, int in_flight) {
   if (int e = use(c)) return e;
   c->vis_step_valid = false;   // lane 0 solves in this context's arena
   if (n_frames < 0 || !d_l || !d_r || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
+  if (plan) if (int e = check_plan(c, plan, cols, rows, "pf_stitch_step_batch_planned_dev")) return e;
   if (n_frames == 0) return 0;
   if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
   const size_t bytes = size_t(cols) * rows * 4;
@@ -364,18 +433,42 @@ int pf_stitch_step_batch_dev(pf_ctx* c, int n_frames, const uint8_t* const* d_l,
     for (int j = 0; j < n_frames; ++j)
       if (overlaps(d_out[k], d_l[j], bytes) || overlaps(d_out[k], d_r[j], bytes) || (j != k && overlaps(d_out[k], d_out[j], bytes)))
         return fail(c, PF_ERR_ARG, "d_out[%d] overlaps an input or another output of the call (frame %d)", k, j);
-  return run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
-    return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out);
-  });
+  if (!plan)
+    return run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
+      return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out);
+    });
+  std::vector<unsigned> diff(n_frames, 0u);
+  if (int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch_planned", [&](pf_ctx* lane, int first, int count) {
+        return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out, plan, diff.data());
+      })) return e;
+  if (std::all_of(diff.begin(), diff.end(), [](unsigned d) { return d == 0; })) return 0;
+  // the call fails as a whole: no composite is delivered (the gathers have run, so the caller's buffers are cleared)
+  {
+    CallGuard guard_(c);
+    for (int k = 0; k < n_frames; ++k) HIPCHK(c, hipMemsetAsync(d_out[k], 0, bytes, c->s_main));
+    if (int e = finish(c)) return e;
+  }
+  return report_plan_diff(c, "pf_stitch_step_batch_planned_dev", diff.data(), n_frames);
+}
+int pf_stitch_step_batch_dev(pf_ctx* c, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
+                             uint8_t* const* d_out, int in_flight) {
+  return stitch_batch_dev(c, nullptr, n_frames, d_l, d_r, cols, rows, max_pct, d_out, in_flight);
+}
+int pf_stitch_step_batch_planned_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows,
+                                     int max_pct, uint8_t* const* d_out, int in_flight) {
+  if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
+  if (!plan) return fail(c, PF_ERR_ARG, "pf_stitch_step_batch_planned_dev: null plan");
+  return stitch_batch_dev(c, plan, n_frames, d_l, d_r, cols, rows, max_pct, d_out, in_flight);
 }
 
 // Host form: one slot of three planes per frame index (12 B/px: left, right, composite), kept between calls so that frame k may
 // chain on its own previous composite.  The slots are separate from pf_stitch_step's chain ("ch_*") and prefetch records.
-int pf_stitch_step_batch(pf_ctx* c, int n_frames, const uint8_t* const* l, const uint8_t* const* r, int cols, int rows, size_t step, int max_pct,
-                         uint8_t* const* out, size_t ostep, int in_flight) {
+static int stitch_batch_host(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* l, const uint8_t* const* r, int cols, int rows, size_t step,
+                             int max_pct, uint8_t* const* out, size_t ostep, int in_flight) {
   if (int e = use(c)) return e;
   c->vis_step_valid = false;
   if (n_frames < 0 || !l) return fail(c, PF_ERR_ARG, "bad argument");
+  if (plan) if (int e = check_plan(c, plan, cols, rows, "pf_stitch_step_batch_planned")) return e;
   if (n_frames == 0) return 0;
   for (int k = 0; k < n_frames; ++k) if (!l[k]) return fail(c, PF_ERR_ARG, "null pointer (frame %d)", k);
   if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
@@ -402,10 +495,13 @@ int pf_stitch_step_batch(pf_ctx* c, int n_frames, const uint8_t* const* l, const
     }
     if (int e = finish(c)) return e;   // the lanes' streams start from complete inputs
   }
-  const int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
-    return stitch_group(lane, first, count, dl.data(), dr.data(), cols, rows, max_pct, dfin.data());
+  std::vector<unsigned> diff(plan ? n_frames : 0, 0u);
+  const int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, plan ? "pf_stitch_step_batch_planned" : "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
+    return stitch_group(lane, first, count, dl.data(), dr.data(), cols, rows, max_pct, dfin.data(), plan, diff.data());
   });
   if (e) return e;
+  // a frame off the plan fails the call as a whole: nothing is downloaded, and the slots stay invalid (sb_frames = 0 above)
+  if (plan) if (int e2 = report_plan_diff(c, "pf_stitch_step_batch_planned", diff.data(), n_frames)) return e2;
   if (out) {
     CallGuard guard_(c);
     for (int k = 0; k < n_frames; ++k)
@@ -415,4 +511,114 @@ int pf_stitch_step_batch(pf_ctx* c, int n_frames, const uint8_t* const* l, const
   }
   c->sb_cols = cols; c->sb_rows = rows; c->sb_frames = n_frames;
   return 0;
+}
+int pf_stitch_step_batch(pf_ctx* c, int n_frames, const uint8_t* const* l, const uint8_t* const* r, int cols, int rows, size_t step, int max_pct,
+                         uint8_t* const* out, size_t ostep, int in_flight) {
+  return stitch_batch_host(c, nullptr, n_frames, l, r, cols, rows, step, max_pct, out, ostep, in_flight);
+}
+int pf_stitch_step_batch_planned(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* l, const uint8_t* const* r, int cols, int rows, size_t step,
+                                 int max_pct, uint8_t* const* out, size_t ostep, int in_flight) {
+  if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
+  if (!plan) return fail(c, PF_ERR_ARG, "pf_stitch_step_batch_planned: null plan");
+  return stitch_batch_host(c, plan, n_frames, l, r, cols, rows, step, max_pct, out, ostep, in_flight);
+}
+
+// ---- stitch plans ----
+// Creation: MatchImages into the plan's map, then the blend ramp by blend_ramp_dev with ramp_geom()'s geometry and form, finishing in
+// the plan's ramp plane (the box blur's result plane, or the in-place ramp where the canvas has no box blur); the working planes are the
+// lone entry points' ("st_*"), the inputs go through "h_img0/1": the chain ("ch_*"), the prefetch records and the visualiser's inputs stay.
+static int stitch_plan_make(pf_ctx* c, const uint8_t* dl, const uint8_t* dr, int cols, int rows, const RampGeom& g, pf_stitch_plan** plan_out) {
+  const size_t n = size_t(cols) * rows;
+  uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
+  float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
+  unsigned* dcount = (unsigned*)ensure(c, "plan_count", 256);
+  if (!dol || !dor || !db || !dmd || !dcount) return PF_ERR_NOMEM;
+  StitchPtrs p{};
+  RampWork w;
+  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
+  pf_stitch_plan* pl = new pf_stitch_plan();
+  pl->cols = cols; pl->rows = rows;
+  struct Drop { pf_stitch_plan* pl; ~Drop() { if (pl) { hipFree(pl->map); hipFree(pl->ramp); delete pl; } } } drop{pl};
+  if (hipMalloc((void**)&pl->map, (n + 255) & ~size_t(255)) != hipSuccess || hipMalloc((void**)&pl->ramp, (n * 4 + 255) & ~size_t(255)) != hipSuccess)
+    return fail(c, PF_ERR_NOMEM, "hipMalloc of a %dx%d stitch plan (5 B/px) failed", cols, rows);
+  hipStream_t sm = c->s_main;
+  p.L[0] = dl; p.R[0] = dr; p.map[0] = pl->map; p.ovL[0] = dol; p.ovR[0] = dor; p.md[0] = dmd;
+  if (g.k2 > 0) { p.blend[0] = db; p.tmp[0] = pl->ramp; } else p.blend[0] = pl->ramp;
+  { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
+  const float* ramp = nullptr;
+  if (int e = blend_ramp_dev(c, sm, p, 1, cols, rows, g, w, true, &ramp)) return e;
+  HIPCHK(c, hipMemsetAsync(dcount, 0, 4, sm));
+  launch_count_code(sm, pl->map, cols, rows, 150, dcount);
+  unsigned overlap = 0;
+  HIPCHK(c, hipMemcpyAsync(&overlap, dcount, 4, hipMemcpyDeviceToHost, sm));
+  HIPCHK(c, hipGetLastError());
+  if (int e = finish(c)) return e;
+  if (int e = check_sweeps(c)) return e;
+  pl->overlap_px = overlap;
+  c->plans.push_back(pl);
+  drop.pl = nullptr;
+  *plan_out = pl;
+  return 0;
+}
+int pf_stitch_plan_create(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, pf_stitch_plan** plan_out) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!l || !plan_out) return fail(c, PF_ERR_ARG, "null pointer");
+  *plan_out = nullptr;
+  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  if (step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
+  const RampGeom g = ramp_geom(cols, rows);
+  if (int e = check_blend_ramp(c, cols, rows, g)) return e;
+  const size_t n = size_t(cols) * rows;
+  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4);
+  if (!dl) return PF_ERR_NOMEM;
+  const uint8_t* dr = nullptr;
+  if (r) {
+    uint8_t* up = (uint8_t*)ensure(c, "h_img1", n * 4);
+    if (!up) return PF_ERR_NOMEM;
+    if (int e = up2d(c, up, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
+    dr = up;
+  } else {
+    if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "pf_stitch_plan_create: no previous result of this size to take the R mask from");
+    dr = (const uint8_t*)ensure(c, "ch_final", n * 4);   // read in place
+    if (!dr) return PF_ERR_NOMEM;
+  }
+  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
+  return stitch_plan_make(c, dl, dr, cols, rows, g, plan_out);
+}
+int pf_stitch_plan_create_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int cols, int rows, pf_stitch_plan** plan_out) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_l || !d_r || !plan_out) return fail(c, PF_ERR_ARG, "null pointer");
+  *plan_out = nullptr;
+  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  const RampGeom g = ramp_geom(cols, rows);
+  if (int e = check_blend_ramp(c, cols, rows, g)) return e;
+  return stitch_plan_make(c, d_l, d_r, cols, rows, g, plan_out);
+}
+int pf_stitch_plan_destroy(pf_ctx* c, pf_stitch_plan* plan) {
+  if (int e = use(c)) return e;
+  auto it = std::find(c->plans.begin(), c->plans.end(), plan);
+  if (it == c->plans.end()) return fail(c, PF_ERR_ARG, "pf_stitch_plan_destroy: not a live stitch plan of this context");
+  c->plans.erase(it);
+  hipFree(plan->map); hipFree(plan->ramp);   // every call is synchronous on return: nothing in flight reads them
+  delete plan;
+  return 0;
+}
+int pf_stitch_plan_info(const pf_stitch_plan* plan, int* cols, int* rows, long long* overlap_px) {
+  if (!plan) return fail(nullptr, PF_ERR_ARG, "null plan");
+  if (cols) *cols = plan->cols;
+  if (rows) *rows = plan->rows;
+  if (overlap_px) *overlap_px = plan->overlap_px;
+  return 0;
+}
+int pf_stitch_plan_download(pf_ctx* c, const pf_stitch_plan* plan, uint8_t* map_out, size_t mstep, float* blend_out, size_t bstep) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (std::find(c->plans.begin(), c->plans.end(), plan) == c->plans.end()) return fail(c, PF_ERR_ARG, "pf_stitch_plan_download: not a live stitch plan of this context");
+  const int cols = plan->cols, rows = plan->rows;
+  if ((map_out && mstep < size_t(cols)) || (blend_out && bstep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
+  if (map_out) if (int e = down2d(c, map_out, mstep, plan->map, cols, cols, rows)) return e;
+  if (blend_out) if (int e = down2d(c, blend_out, bstep, plan->ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  return finish(c);
 }

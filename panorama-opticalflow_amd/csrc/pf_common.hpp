@@ -182,6 +182,10 @@ struct StitchPtrs {
   uint8_t* merged[kMaxBatch]; uint8_t* out[kMaxBatch];          // novel view, composite
 };
 void launch_match_images(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);   // L, R -> map, ovL, ovR
+// against a stitch plan: p.map = the plan's map (read only); L, R -> ovL, ovR by the plan's code, and per frame the number of pixels whose
+// own code differs from it, added to diff_mapped[frame] (mapped host words, zeroed by the caller)
+void launch_match_verify(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, unsigned* diff_mapped);
+void launch_count_code(hipStream_t st, const uint8_t* map, int cols, int rows, int code, unsigned* count /* device word, zeroed by the caller */);
 void launch_countblend(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
 void launch_tile_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed = false,
                       void* scratch = nullptr);                                                // blend in place, by md

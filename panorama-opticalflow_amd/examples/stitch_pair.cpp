@@ -2,6 +2,8 @@
 // headers, with raw-file I/O: the call sequence is the reference's own.
 //   stitch_pair <cols> <rows> <L.bgra> <R.bgra> <flow_alg> <out_prefix>
 // writes <out_prefix>.final.bgra, .merged.bgra, .blend.f32, .flowLR.f32, .flowRL.f32, .map.u8
+//   stitch_pair ... <out_prefix> plan    also runs the step through a stitch plan of the same pair (StitchPlan + its stitchStep
+//   overload) and writes <out_prefix>.planned.bgra, .plan_map.u8, .plan_blend.f32
 #include <cstdio>
 #include <iostream>
 
@@ -60,6 +62,14 @@ int main(int argc, char** argv) {
     writeRaw(prefix + ".flowRL.f32", novelViewGen->getFlowRtoL());
     writeRaw(prefix + ".map.u8", Stools.getMap());
     delete novelViewGen;
+    if (argc > 7 && std::string(argv[7]) == "plan") {
+      StitchPlan plan(colorImageL, &colorImageR);
+      if (plan.empty() || plan.cols() != cols || plan.rows() != rows) throw VrCamException("StitchPlan: wrong geometry");
+      writeRaw(prefix + ".planned.bgra", stitchStep(plan, colorImageL, &colorImageR, flow_alg));
+      writeRaw(prefix + ".plan_map.u8", plan.getMap());
+      writeRaw(prefix + ".plan_blend.f32", plan.getBlend());
+      std::cout << "plan overlap pixels = " << plan.overlapPixels() << std::endl;
+    }
     std::cout << "Part1 Finished!RUNTIME (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
   } catch (const VrCamException& e) {
     std::cerr << "VrCamException: " << e.what() << std::endl;

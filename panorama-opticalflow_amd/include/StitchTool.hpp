@@ -102,6 +102,64 @@ static inline Mat stitchStep(const Mat& colorImageL, const Mat* colorImageR, con
   return out;
 }
 
+// A stitch plan (pf_stitch_plan): the Map and the blend ramp of one step of a fixed rig, kept in HBM and reused for every frame whose
+// alpha masks are the ones it was made from.  colorImageR == nullptr takes the R mask from the previous stitchStep's result in HBM.
+// Owned by pano::context(); the object frees it (movable, not copyable).
+class StitchPlan {
+ public:
+  StitchPlan() {}
+  StitchPlan(const Mat& colorImageL, const Mat* colorImageR) {
+    if (colorImageL.type() != CV_8UC4 || (colorImageR && (colorImageR->type() != CV_8UC4 || colorImageR->rows != colorImageL.rows ||
+                                                           colorImageR->cols != colorImageL.cols || colorImageR->step != colorImageL.step)))
+      throw util::VrCamException("StitchPlan: inputs must be CV_8UC4 images of equal size");
+    pano::check(pf_stitch_plan_create(pano::context(), colorImageL.data, colorImageR ? colorImageR->data : nullptr, colorImageL.cols, colorImageL.rows,
+                                      colorImageL.step, &plan_));
+  }
+  ~StitchPlan() { reset(); }
+  StitchPlan(const StitchPlan&) = delete;
+  StitchPlan& operator=(const StitchPlan&) = delete;
+  StitchPlan(StitchPlan&& o) noexcept : plan_(o.plan_) { o.plan_ = nullptr; }
+  StitchPlan& operator=(StitchPlan&& o) noexcept {
+    if (this != &o) { reset(); plan_ = o.plan_; o.plan_ = nullptr; }
+    return *this;
+  }
+  void reset() {
+    if (plan_) pf_stitch_plan_destroy(pano::context(), plan_);
+    plan_ = nullptr;
+  }
+  bool empty() const { return plan_ == nullptr; }
+  const pf_stitch_plan* get() const { return plan_; }
+  int cols() const { int v = 0; if (plan_) pf_stitch_plan_info(plan_, &v, nullptr, nullptr); return v; }
+  int rows() const { int v = 0; if (plan_) pf_stitch_plan_info(plan_, nullptr, &v, nullptr); return v; }
+  long long overlapPixels() const { long long v = 0; if (plan_) pf_stitch_plan_info(plan_, nullptr, nullptr, &v); return v; }
+  Mat getMap() const {
+    Mat m(rows(), cols(), CV_8UC1);
+    pano::check(pf_stitch_plan_download(pano::context(), plan_, m.data, m.step, nullptr, 0));
+    return m;
+  }
+  Mat getBlend() const {
+    Mat b(rows(), cols(), CV_32FC1);
+    pano::check(pf_stitch_plan_download(pano::context(), plan_, nullptr, 0, b.ptr<float>(), b.step));
+    return b;
+  }
+
+ private:
+  pf_stitch_plan* plan_ = nullptr;
+};
+
+// stitchStep on a plan: the same bytes without recomputing the map and the ramp; throws if the frame's masks are not the plan's.
+static inline Mat stitchStep(const StitchPlan& plan, const Mat& colorImageL, const Mat* colorImageR, const std::string& flowAlgName) {
+  const int maxPct = pf_max_percentage_by_name(flowAlgName.c_str());
+  if (maxPct < 0) throw util::VrCamException("unrecognized flow algorithm name: " + flowAlgName);
+  if (colorImageL.type() != CV_8UC4 || (colorImageR && (colorImageR->type() != CV_8UC4 || colorImageR->rows != colorImageL.rows ||
+                                                         colorImageR->cols != colorImageL.cols || colorImageR->step != colorImageL.step)))
+    throw util::VrCamException("stitchStep: inputs must be CV_8UC4 images of equal size");
+  Mat out(colorImageL.rows, colorImageL.cols, CV_8UC4);
+  pano::check(pf_stitch_step_planned(pano::context(), plan.get(), colorImageL.data, colorImageR ? colorImageR->data : nullptr, colorImageL.cols,
+                                     colorImageL.rows, colorImageL.step, maxPct, out.data, out.step));
+  return out;
+}
+
 }  // namespace stitch_tools
 
 #endif /* StitchTool_hpp */

@@ -94,6 +94,8 @@ EXPORTS = [
     "pf_solver_params_init", "pf_set_solver_params", "pf_get_solver_params",
     "pf_flow", "pf_flow_bidir", "pf_blend", "pf_novel_view", "pf_stitch_prepare", "pf_stitch_match", "pf_stitch_generate_blend", "pf_stitch_raw_blend", "pf_stitch_gather", "pf_stitch_step", "pf_stitch_prefetch",
     "pf_stitch_step_batch", "pf_stitch_step_batch_dev",
+    "pf_stitch_plan_create", "pf_stitch_plan_create_dev", "pf_stitch_plan_destroy", "pf_stitch_plan_info", "pf_stitch_plan_download",
+    "pf_stitch_step_planned", "pf_stitch_step_batch_planned", "pf_stitch_step_batch_planned_dev",
     "pf_dev_alloc", "pf_dev_free", "pf_host_alloc", "pf_host_free", "pf_upload", "pf_download", "pf_sync", "pf_checksum_dev", "pf_selftest_packed_chains",
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
@@ -177,6 +179,27 @@ class Dist:
         if self.h:
             self.l.pf_dist_destroy(self.h)
             self.h = None
+
+
+class StitchPlan:
+    """pf_stitch_plan: one rig's overlap map and blend ramp in HBM (Context.stitch_plan).  Owned by its context; close() frees it early."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, C.c_void_p(handle)
+        cols, rows, ov = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        ctx._chk(ctx.l.pf_stitch_plan_info(self.h, C.byref(cols), C.byref(rows), C.byref(ov)))
+        self.cols, self.rows, self.overlap_px = cols.value, rows.value, ov.value
+
+    def download(self):
+        """(Map (rows, cols) uint8, finished ramp (rows, cols) float32)"""
+        mp = np.empty((self.rows, self.cols), np.uint8); bl = np.empty((self.rows, self.cols), np.float32)
+        self.ctx._chk(self.ctx.l.pf_stitch_plan_download(self.ctx.h, self.h, _p(mp), C.c_size_t(self.cols), _p(bl), C.c_size_t(self.cols * 4)))
+        return mp, bl
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx._chk(self.ctx.l.pf_stitch_plan_destroy(self.ctx.h, self.h))
+        self.h = None
 
 
 class Context:
@@ -291,22 +314,41 @@ class Context:
         rows, cols, _ = next_L.shape
         self._chk(self.l.pf_stitch_prefetch(self.h, _p(next_L), cols, rows, C.c_size_t(cols * 4)))
 
-    def stitch_step(self, L, R, max_pct, want_out=True, out=None):
+    def stitch_plan(self, L, R):
+        """The plan of a step whose alpha masks are L's and R's (only alpha matters); R=None takes the R mask from the composite the
+        last stitch_step left in HBM."""
+        a = _u8(L); rows, cols, _ = a.shape
+        r = None if R is None else _u8(R)
+        h = C.c_void_p(None)
+        self._chk(self.l.pf_stitch_plan_create(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), C.byref(h)))
+        return StitchPlan(self, h.value)
+
+    def stitch_plan_dev(self, d_l, d_r, cols, rows):
+        h = C.c_void_p(None)
+        self._chk(self.l.pf_stitch_plan_create_dev(self.h, C.c_void_p(d_l), C.c_void_p(d_r), cols, rows, C.byref(h)))
+        return StitchPlan(self, h.value)
+
+    def stitch_step(self, L, R, max_pct, want_out=True, out=None, plan=None):
         """One iteration of main.cpp's loop on the device; R=None chains on the previous result kept in HBM.
         out: optional preallocated (rows, cols, 4) uint8 array for the composite (a caller that reuses its buffer, like
-        the reference's Mat, does not pay a fresh 144 MB allocation + first-touch page faults per call)."""
+        the reference's Mat, does not pay a fresh 144 MB allocation + first-touch page faults per call).
+        plan: a StitchPlan of these masks -- the same bytes without recomputing the map and the ramp; raises if the masks differ."""
         a = _u8(L); rows, cols, _ = a.shape
         r = None if R is None else _u8(R)     # named, so that a converted copy outlives the call
         if out is not None:
             assert out.dtype == np.uint8 and out.shape == (rows, cols, 4) and out.flags["C_CONTIGUOUS"]
         elif want_out:
             out = np.empty((rows, cols, 4), np.uint8)
-        self._chk(self.l.pf_stitch_step(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                        None if out is None else _p(out), C.c_size_t(cols * 4)))
+        if plan is not None:
+            self._chk(self.l.pf_stitch_step_planned(self.h, plan.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
+                                                    None if out is None else _p(out), C.c_size_t(cols * 4)))
+        else:
+            self._chk(self.l.pf_stitch_step(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
+                                            None if out is None else _p(out), C.c_size_t(cols * 4)))
         self._step_shape = (rows, cols)
         return out
 
-    def stitch_step_batch(self, Ls, Rs, max_pct, in_flight=8, want_out=True, out=None):
+    def stitch_step_batch(self, Ls, Rs, max_pct, in_flight=8, want_out=True, out=None, plan=None):
         """n independent stitch steps of one size (frame k = one stitch_step of its own chain).  Rs=None, or a None entry, chains
         frame k on its composite from the previous stitch_step_batch call.  Returns a list of (rows, cols, 4) arrays, or of None.
         out: optional list of preallocated (rows, cols, 4) uint8 arrays for the composites (as stitch_step's `out`)."""
@@ -322,15 +364,22 @@ class Context:
         else:
             outs = [np.empty((rows, cols, 4), np.uint8) for _ in range(n)] if want_out else [None] * n
         arr = lambda v: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in v])
-        self._chk(self.l.pf_stitch_step_batch(self.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                              arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
+        if plan is not None:   # one plan for all frames; the call raises as a whole if any frame's masks differ from it
+            self._chk(self.l.pf_stitch_step_batch_planned(self.h, plan.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4),
+                                                          max_pct, arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
+        else:
+            self._chk(self.l.pf_stitch_step_batch(self.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4), max_pct,
+                                                  arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
         return outs
 
-    def stitch_step_batch_dev(self, d_l, d_r, cols, rows, max_pct, d_out, in_flight=8):
+    def stitch_step_batch_dev(self, d_l, d_r, cols, rows, max_pct, d_out, in_flight=8, plan=None):
         """the device form: lists of device pointers (packed BGRA), every d_r entry non-NULL"""
         n = len(d_l)
         arr = lambda v: (C.c_void_p * max(n, 1))(*[C.c_void_p(int(x)) if x else None for x in v])
-        self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
+        if plan is not None:
+            self._chk(self.l.pf_stitch_step_batch_planned_dev(self.h, plan.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
+        else:
+            self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
 
     # ---- flow visualisation (CPU/OpticalFlow.cpp:147-204, the panel of CPU/main.cpp:20-45) ----
     def vis_grey_disparity(self, flow):

@@ -10,6 +10,10 @@
 //   pano_stitch -test_dirs <dir1>,<dir2>,... -top_img top.tif -flow_alg ... [-steps 5] [-in_flight 8]: the -test_dir flow for every
 //   directory at once through the batched step (pf_stitch_step_batch, one frame per directory); each directory gets the same files as
 //   its own -test_dir run, and one "Part<i> Finished!" line is printed per batched step.
+//   -static_rig 1 (with -test_dirs): the directories are frames of ONE camera rig, i.e. they share their alpha masks.  Before step i a
+//   stitch plan (overlap map + blend ramp) is made from the first directory's <i>.tif and its R of that step (the top image, then its
+//   previous composite), and step i of all directories runs on it (pf_stitch_step_batch_planned): the same files, without recomputing
+//   the map and the ramp per directory.  A directory whose masks differ from the first one's ends the run with an error that names it.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -120,12 +124,14 @@ static std::vector<std::string> splitDirs(const std::string& list) {
     b = e + 1;
   }
 }
-static int runBatchDirs(const std::vector<std::string>& dirs, const std::string& top_img, const std::string& flow_alg, int nsteps, int in_flight) {
+static int runBatchDirs(const std::vector<std::string>& dirs, const std::string& top_img, const std::string& flow_alg, int nsteps, int in_flight,
+                        bool static_rig) {
   const int maxPct = pf_max_percentage_by_name(flow_alg.c_str());
   if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + flow_alg);
   double StartTime = getCurrTimeSec();
   const int n = (int)dirs.size();
   std::vector<Mat> tops(n), Ls(n), outs(n);
+  Mat prev0;   // -static_rig: the first directory's previous composite, the R of its next plan
   for (int k = 0; k < n; ++k) tops[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + top_img);
   for (int i = 1; i <= nsteps; i++) {
     double StepStart = getCurrTimeSec();
@@ -139,8 +145,27 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
       outs[k] = Mat(Ls[0].rows, Ls[0].cols, CV_8UC4);
       l[k] = Ls[k].data; r[k] = tops[k].data; o[k] = outs[k].data;
     }
+    if (static_rig) {
+      // outs[0] was replaced above, prev0 still holds the first directory's composite of step i - 1
+      StitchPlan plan(Ls[0], i == 1 ? &tops[0] : &prev0);
+      const int rc = pf_stitch_step_batch_planned(pano::context(), plan.get(), n, l.data(), i == 1 ? r.data() : nullptr, Ls[0].cols, Ls[0].rows, Ls[0].step,
+                                                  maxPct, o.data(), outs[0].step, in_flight);
+      if (rc != 0) {
+        // the frame index is read out of the library's message: the wording "frame <k> differs from the stitch plan" is
+        // report_plan_diff()'s in csrc/pf_api_stitch.inl (keep the two in step; tests/test_cli_stitch_static_rig.py pins both)
+        const std::string msg = pf_last_error(pano::context());
+        const size_t at = msg.find("frame ");
+        int k = -1;
+        if (at != std::string::npos && msg.find("differs from the stitch plan") != std::string::npos) k = atoi(msg.c_str() + at + 6);
+        if (k >= 0 && k < n)
+          throw VrCamException("-static_rig: step " + std::to_string(i) + ": the alpha masks of directory " + dirs[k] + " are not those of " + dirs[0] +
+                               " (panoflow: " + msg + ")");
+        throw VrCamException("panoflow: " + msg);
+      }
+    } else
     pano::check(pf_stitch_step_batch(pano::context(), n, l.data(), i == 1 ? r.data() : nullptr, Ls[0].cols, Ls[0].rows, Ls[0].step, maxPct,
                                      o.data(), outs[0].step, in_flight));
+    prev0 = outs[0];
     for (int k = 0; k < n; ++k) {
       if (i == nsteps) pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "FinalResult.png", outs[k]);
       else pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", outs[k]);
@@ -156,6 +181,7 @@ int main(int argc, char** argv) {
     auto flags = parseFlags(argc, argv);
     if (flags.count("test_dirs")) {   // every refusal before any device call
       if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
+      const bool static_rig = flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0;
       if (flags.count("fused") && atoi(flags["fused"].c_str()) == 0) throw VrCamException("-test_dirs runs the fused step only (-fused 0 is not supported)");
       if (flags.count("visualize") && atoi(flags["visualize"].c_str()) != 0) throw VrCamException("-test_dirs does not support -visualize 1");
       if (flags.count("inputs")) throw VrCamException("-test_dirs does not support -inputs");
@@ -166,8 +192,9 @@ int main(int argc, char** argv) {
       const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
       const int in_flight = flags.count("in_flight") ? atoi(flags["in_flight"].c_str()) : 8;
       if (in_flight < 1 || in_flight > 32) throw VrCamException("-in_flight must be 1..32");
-      return runBatchDirs(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight);
+      return runBatchDirs(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight, static_rig);
     }
+    if (flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0) throw VrCamException("-static_rig 1 needs -test_dirs (it plans the batched step)");
     const std::string FLAGS_test_dir = flags["test_dir"], FLAGS_top_img = flags["top_img"], FLAGS_flow_alg = flags["flow_alg"];
     const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
     const bool fused = !flags.count("fused") || atoi(flags["fused"].c_str()) != 0;   // -fused 0: the reference's object-by-object sequence
