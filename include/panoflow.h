@@ -317,6 +317,7 @@ int pf_stage_sweep(pf_ctx* ctx, const float* g0xy, const float* g1xy, const floa
                    const float* alpha1, float* flow_inout, int w, int h, int forward);  /* PixFlow.hpp:315-324 / :328-337 */
 int pf_stage_diffusion(pf_ctx* ctx, const float* alpha0, const float* alpha1, float* flow_inout, int w, int h); /* PixFlow.hpp:388-405 */
 int pf_stage_upsample_cubic(pf_ctx* ctx, const float* flow, int sw, int sh, float* out, int dw, int dh, float scale); /* PixFlow.hpp:122-125 */
+                                                                      /* PF_ERR_ARG when sh / dh > 1.1875: the kernel upsamples, as every pyramid does */
 int pf_stage_final(pf_ctx* ctx, const float* flow, int sw, int sh, int pad_cols, int rows, int pad, float scale,
                    float* out /* (pad_cols-2*pad) x rows */);                          /* PixFlow.hpp:128-134 + OpticalFlow.cpp:143-144 */
 int pf_stage_adjust_initial_flow(pf_ctx* ctx, const float* i0, const float* i1, const float* a0, const float* a1, int w, int h,
@@ -329,6 +330,28 @@ int pf_stage_blend_smooth(pf_ctx* ctx, float* blend_inout, const float* merged_d
  * (PF_ERR_ARG if it does not fit), 1 = streamed (any geometry whose window row, step + k - 1 floats, fits that LDS).  PF_ERR_ARG for
  * step < 1, k < 1, step >= min(cols, rows) (no tile), max(k/2, k-1-k/2) >= min(cols, rows), null pointers. */
 int pf_stage_tile_blur(pf_ctx* ctx, float* blend_inout, const float* merged_dis, int cols, int rows, int step, int k, int form);
+/* Every form of the fused Gaussian 15 (PixFlow.hpp:306-311, :389-403) through the launcher a solve uses, on n_batch (1..3) planes laid
+ * out as the slabs of a batched solve are.  Host arrays hold n_batch packed planes one after the other.
+ *   PF_G15_PLAIN:       src w x h float2                                  -> dst = GaussianBlur 15, sigma 8
+ *   PF_G15_MIX:         src w x h float2, alpha0 / alpha1 w x h           -> dst = lowAlphaFlowDiffusion
+ *   PF_G15_UPSAMPLE:    src sw x sh float2 (the coarser level), mul       -> up_out = cubic upsample * mul (w x h), dst = its GaussianBlur
+ *   PF_G15_MEDIAN_MIX:  src w x h float2, alpha0 / alpha1                 -> dst = lowAlphaFlowDiffusion of medianBlur 5 of src
+ * max_blocks > 0 caps the persistent blocks per plane (a block then walks several tiles); 0 = the library's choice.
+ * sw, sh, mul and up_out are only read by PF_G15_UPSAMPLE, the alphas only by the two MIX forms. */
+typedef enum pf_gauss15_form { PF_G15_PLAIN = 0, PF_G15_MIX = 1, PF_G15_UPSAMPLE = 2, PF_G15_MEDIAN_MIX = 3 } pf_gauss15_form;
+int pf_stage_gauss15_form(pf_ctx* ctx, int form, int n_batch, int max_blocks, const float* src, int sw, int sh, float mul,
+                          const float* alpha0, const float* alpha1, int w, int h, float* dst, float* up_out);
+/* Gradients (PixFlow.hpp:281-294) and gate + bounding boxes + level-0 count (PixFlow.hpp:317,330) of a whole level table in one launch
+ * each, as a solve runs them, for n_batch (1..3) pairs.  ws / hs: n_levels level sizes (each at least 2 x 2, at most 96 levels).  The host
+ * inputs hold, per pair, the levels back to back without padding; on the device they lie as in a solve's pyramid plane, level l at
+ * off[l], every offset rounded up to 64 elements.  off_out receives off[0..n_levels-1] and the plane size P.
+ * The gradients cover plane elements [first, total) (multiples of 4; total 0 = P) with at most max_blocks blocks per image (0 = no cap).
+ * Outputs per pair: g0 / g1 = the whole gradient planes (P x float2), gate = the whole gate plane (P bytes) -- what no kernel wrote reads
+ * 0xFF bytes -- boxes = (min x, min y, max x, max y) per level as the kernel published them (max < min: nothing gated), count0 = gated
+ * pixels of level 0.  One pair uses the context's own work area of the gate kernel, several use slab areas as a batched solve does. */
+int pf_stage_level_table(pf_ctx* ctx, int n_levels, const int* ws, const int* hs, int n_batch, const float* img0, const float* img1,
+                         const float* alpha0, const float* alpha1, long long first, long long total, int max_blocks, long long* off_out,
+                         float* g0, float* g1, uint8_t* gate, int* boxes, int* count0);
 
 /* ---- flow visualisation ---------------------------------------------------------------------
  * The reference's debugging views of a flow (CPU/OpticalFlow.cpp:147-204, declared in CPU/OpticalFlow.hpp:72-76), byte for byte,

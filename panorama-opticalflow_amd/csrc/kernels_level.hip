@@ -2,7 +2,8 @@
 // sweeps, plus the inter-level and final upsampling (:122-134).  All stencil/streaming, HBM-bound.
 // One kernel per stage: gradients and gate + boxes + count cover every level of a level table in one launch (the stage entry
 // points and the largest canvases hand them a one-level table), the Gaussian 15 is the fused LDS kernel in all its uses.  The two
-// stages with two forms (median 5, cubic upsample: direct and tiled) pick by level size / scale, and both forms are used.
+// stage with two forms (median 5: direct and LDS-tiled) picks by level size, and both forms are used.  The cubic upsample has the tiled
+// form only: no pyramid reaches the scale at which a direct form would be needed (launch_upsample_cubic).
 #include <stdio.h>
 #include <stdlib.h>
 #include "pf_common.hpp"
@@ -239,7 +240,6 @@ __global__ __launch_bounds__(256) void k_gate_bbox_all(const float* __restrict__
     }
     flush();
   }
-  // padding between levels: keep the gate defined (0) there
   for (int o = 32; o > 0; o >>= 1) cnt0 += __shfl_down(cnt0, o);
   if ((threadIdx.x & 63) == 0 && cnt0) atomicAdd(&scnt, cnt0);
   __syncthreads();
@@ -318,7 +318,7 @@ __device__ __forceinline__ float2 d_median5_px(const float2* __restrict__ src, i
 }
 
 // one output pixel of the inter-level upsample (K9 below: resize INTER_CUBIC on float2, then *= 1/0.9f); shared by
-// k_upsample_cubic and by the Gauss15 kernel that upsamples while it loads (small levels)
+// k_upsample_cubic_tiled's expressions, per pixel: used by the Gauss15 kernel that upsamples while it loads (small levels)
 __device__ __forceinline__ float2 d_upsample_cubic_px(const float2* __restrict__ src, int sw, int sh, int dx, int dy, double scale_x, double scale_y, float mul) {
   int sx, sy; float fx, fy;
   d_src_coord(dx, scale_x, sx, fx);
@@ -371,7 +371,7 @@ constexpr int kG15Pre = kG15Main + kG15Tail;                               // 15
 // A tile whose 78 x 46 footprint lies inside the plane (all but the rim) takes the INTERIOR form of every step: no reflection, no
 // bounds tests, no partial rows -- the same loads, products and sums in the same order, so the same bits.
 // UPS (small levels): the source plane does not exist yet -- it is the bicubic upsample of the coarser level's result
-// (PixFlow.hpp:122-125); the tile loader computes it on the fly (same expressions as k_upsample_cubic) and writes the tile's own
+// (PixFlow.hpp:122-125); the tile loader computes it on the fly (same expressions as k_upsample_cubic_tiled) and writes the tile's own
 // 64 x 32 pixels of it to `up_out`, which saves the separate upsample launch where a launch costs more than its work.
 struct UpsSrc { const float2* src; int sw, sh; double scale_x, scale_y; float mul; float2* up_out; };
 template <bool V> struct G15Flag { static constexpr bool value = V; };
@@ -533,32 +533,34 @@ __global__ __launch_bounds__(256, 3) void k_gauss15_fused(const float2* __restri
     if (tile < ntiles) __syncthreads();   // every read of this tile's LDS is done before the next one is stored
   }
 }
-static inline void gauss15_grid(int w, int h, int& ntx, int& ntiles, unsigned& blocks, int nbatch = 1) {
+// max_blocks > 0 caps the persistent blocks per plane (tests: a walk of several tiles per block on a small plane)
+static inline void gauss15_grid(int w, int h, int& ntx, int& ntiles, unsigned& blocks, int nbatch = 1, int max_blocks = 0) {
   ntx = (w + kG15TX - 1) / kG15TX;
   ntiles = ntx * ((h + kG15TY - 1) / kG15TY);
   static const int cap = [] { int dev = 0; hipDeviceProp_t p; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 768; return 3 * p.multiProcessorCount; }();
   int per = cap / (nbatch > 0 ? nbatch : 1);   // the persistent blocks of all pairs of a batch share the chip
   if (per < 1) per = 1;
   blocks = (unsigned)(ntiles < per ? ntiles : per);
+  if (max_blocks > 0 && blocks > (unsigned)max_blocks) blocks = (unsigned)max_blocks;
 }
-void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt) {
+void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt, int max_blocks) {
   int ntx, ntiles; unsigned blocks;
-  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
+  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n, max_blocks);
   hipLaunchKernelGGL((k_gauss15_fused<false, false, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, reinterpret_cast<const float2*>(src), reinterpret_cast<float2*>(dst), w, h, g15, nullptr, nullptr, ntx, ntiles, UpsSrc{}, bt.stride);
 }
 
 // upsample (coarse sw x sh -> w x h, times mul) + Gauss15 of the upsampled plane in one launch: `up` receives the upsampled flow
-void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh, float mul, float* up, float* dst, int w, int h, const Gauss& g15, Batch bt) {
+void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh, float mul, float* up, float* dst, int w, int h, const Gauss& g15, Batch bt, int max_blocks) {
   int ntx, ntiles; unsigned blocks;
-  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
+  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n, max_blocks);
   const UpsSrc u{reinterpret_cast<const float2*>(coarse), sw, sh, 1. / ((double)w / sw), 1. / ((double)h / sh), mul, reinterpret_cast<float2*>(up)};
   hipLaunchKernelGGL((k_gauss15_fused<false, true, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, nullptr, reinterpret_cast<float2*>(dst), w, h, g15, nullptr, nullptr, ntx, ntiles, u, bt.stride);
 }
 
 // K8 lowAlphaFlowDiffusion (PixFlow.hpp:388-405): the alpha mix is the fused kernel's epilogue (MIX).
-void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt) {
+void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt, int max_blocks) {
   int ntx, ntiles; unsigned blocks;
-  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
+  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n, max_blocks);
   hipLaunchKernelGGL((k_gauss15_fused<true, false, false>), dim3(blocks, 1, bt.n), dim3(256), 0, st, reinterpret_cast<const float2*>(flow), reinterpret_cast<float2*>(out), w, h, g15, a0, a1, ntx, ntiles, UpsSrc{}, bt.stride);
 }
 
@@ -640,9 +642,9 @@ void launch_median5_form(hipStream_t st, const float* src, float* dst, int w, in
 void launch_median5(hipStream_t st, const float* src, float* dst, int w, int h, Batch bt) { launch_median5_form(st, src, dst, w, h, (long)w * h >= kMedTiledMinPx, bt); }
 
 // medianBlur(5) + lowAlphaFlowDiffusion in one launch: `flow` is the backward sweep's output, `out` a different plane
-void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt) {
+void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt, int max_blocks) {
   int ntx, ntiles; unsigned blocks;
-  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n);
+  gauss15_grid(w, h, ntx, ntiles, blocks, bt.n, max_blocks);
   hipLaunchKernelGGL((k_gauss15_fused<true, false, true>), dim3(blocks, 1, bt.n), dim3(256), 0, st, reinterpret_cast<const float2*>(flow), reinterpret_cast<float2*>(out), w, h, g15, a0, a1, ntx, ntiles, UpsSrc{}, bt.stride);
 }
 
@@ -650,14 +652,7 @@ void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a
 // K9 inter-level upsample: resize INTER_CUBIC on float2 then *= 1/0.9f (PixFlow.hpp:122-125).
 // [OpenCV imgwarp.cpp] HResizeCubic (taps clamped to the row) then VResizeCubic (rows clipped).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_upsample_cubic(const float2* __restrict__ src, int sw, int sh, float2* __restrict__ dst, int dw, int dh,
-                                                        double scale_x, double scale_y, float mul, size_t bstride) {
-  const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
-  if (dx >= dw) return;
-  { const size_t bo = size_t(blockIdx.z) * bstride; PF_BOFF(src, bo); PF_BOFF(dst, bo); }
-  dst[size_t(dy) * dw + dx] = d_upsample_cubic_px(src, sw, sh, dx, dy, scale_x, scale_y, mul);
-}
-// Tiled form: a block owns a 64 x 16 output tile.  The horizontal pass (HResizeCubic) of every source row the tile's vertical
+// A block owns a 64 x 16 output tile.  The horizontal pass (HResizeCubic) of every source row the tile's vertical
 // pass touches (at most kUpRows: 16 * 0.9 + 4 at the pyramid's scale) is computed once per output column into LDS, then the
 // vertical pass (VResizeCubic) reads four LDS rows: ~5 global loads per output instead of 16, same expressions.
 constexpr int kUpX = 64, kUpY = 16, kUpRows = 24;
@@ -698,16 +693,14 @@ __global__ __launch_bounds__(256) void k_upsample_cubic_tiled(const float2* __re
     dst[size_t(dy) * dw + x0 + tx] = make_float2(ox * mul + 0.0f, oy2 * mul + 0.0f);
   }
 }
+// The tile's LDS holds the source rows a 16-row output tile can touch: floor(15 * sy) + 4 (+1 for rounding) <= kUpRows, i.e. sh / dh <= 1.1875.
+// Every pyramid upsamples (sh <= dh: make_geometry never grows a level), so a solve always fits; there is no other form.
+bool upsample_cubic_fits(int sh, int dh) { return dh > 0 && kUpY * (1. / ((double)dh / sh)) + 5.0 <= kUpRows; }
 void launch_upsample_cubic(hipStream_t st, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul, Batch bt) {
+  if (!upsample_cubic_fits(sh, dh)) { fprintf(stderr, "[panoflow] launch_upsample_cubic: %d -> %d rows is outside the tiled kernel's range\n", sh, dh); abort(); }
   const double sx = 1. / ((double)dw / sw), sy = 1. / ((double)dh / sh);
-  if (kUpY * sy + 5.0 <= kUpRows) {   // source rows a 16-row output tile can touch: floor(15 * sy) + 4 (+1 for rounding)
-    dim3 grid((dw + kUpX - 1) / kUpX, (dh + kUpY - 1) / kUpY, bt.n);
-    hipLaunchKernelGGL(k_upsample_cubic_tiled, grid, dim3(256), 0, st, reinterpret_cast<const float2*>(src), sw, sh, reinterpret_cast<float2*>(dst), dw, dh, sx, sy, mul, bt.stride);
-    return;
-  }
-  dim3 grid((dw + 255) / 256, dh, bt.n);
-  hipLaunchKernelGGL(k_upsample_cubic, grid, dim3(256), 0, st, reinterpret_cast<const float2*>(src), sw, sh, reinterpret_cast<float2*>(dst), dw, dh, sx,
-                     sy, mul, bt.stride);
+  dim3 grid((dw + kUpX - 1) / kUpX, (dh + kUpY - 1) / kUpY, bt.n);
+  hipLaunchKernelGGL(k_upsample_cubic_tiled, grid, dim3(256), 0, st, reinterpret_cast<const float2*>(src), sw, sh, reinterpret_cast<float2*>(dst), dw, dh, sx, sy, mul, bt.stride);
 }
 
 // ------------------------------------------------------------------------------------------------

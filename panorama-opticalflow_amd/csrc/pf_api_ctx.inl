@@ -59,6 +59,7 @@ struct pf_ctx {
                                         // pairs drives three streams, so that six lanes of the throughput mode fit the hardware queues)
   bool drained = true;                  // false between "work enqueued" and finish(): what CallGuard looks at
   size_t slab_stride = 0, slab_work_off = 0; int slab_pairs = 0;   // layout the "batch_slab" buffer was last initialised for (alloc_solve_batch)
+  const void* tbl_slab = nullptr; size_t tbl_stride = 0; int tbl_pairs = 0;   // ... and the "sg_tbl" slabs of pf_stage_level_table (same self-resetting work areas)
   std::vector<pf_ctx*> lanes;           // throughput mode: further stream/buffer sets on the same device (pf_novel_view_batch_dev)
   int* h_gate = nullptr; int* d_gate = nullptr; int gate_epoch = 0;   // mapped pinned: per-level gate boxes + count + epoch flag (k_gate_bbox_all)
   int* h_status = nullptr;              // mapped pinned host word: bit d set = a sweep band of direction d timed out

@@ -116,6 +116,8 @@ int pf_stage_diffusion(pf_ctx* c, const float* a0, const float* a1, float* flow,
 }
 int pf_stage_upsample_cubic(pf_ctx* c, const float* flow, int sw, int sh, float* out, int dw, int dh, float scale) {
   STAGE_BEGIN(c);
+  if (sw < 1 || sh < 1 || dw < 1 || dh < 1) return fail(c, PF_ERR_ARG, "bad upsample size %dx%d -> %dx%d", sw, sh, dw, dh);
+  if (!upsample_cubic_fits(sh, dh)) return fail(c, PF_ERR_ARG, "upsample %d -> %d rows: the kernel covers source / destination rows <= 1.1875 (a pyramid never shrinks on the way up)", sh, dh);
   float* s = (float*)stage_up(c, "sg_a", flow, size_t(sw) * sh * 8); float* d = (float*)ensure(c, "sg_b", size_t(dw) * dh * 8);
   if (!s || !d) return PF_ERR_NOMEM;
   launch_upsample_cubic(sm, s, sw, sh, d, dw, dh, scale);
@@ -207,6 +209,121 @@ int pf_stage_tile_blur(pf_ctx* c, float* blend, const float* md, int cols, int r
   if (int e = tile_blur_dev(c, sm, db, dmd, cols, rows, step, k, streamed)) return e;
   if (int e = stage_down(c, blend, db, n * 4)) return e;
   return check_sweeps(c);
+}
+
+// ---- every form of the fused Gaussian 15 and a whole level table (tests/test_gpu_stage_forms.py) ----
+// Slabs as a batched solve lays them out: one per pair, `stride` bytes apart, every plane at the same 256-byte-aligned offset inside.
+struct StageSlab {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
+  size_t stride() const { return (off + 4095) & ~size_t(4095); }
+};
+int pf_stage_gauss15_form(pf_ctx* c, int form, int n_batch, int max_blocks, const float* src, int sw, int sh, float mul, const float* a0, const float* a1, int w, int h,
+                          float* dst, float* up_out) {
+  STAGE_BEGIN(c);
+  if (form < PF_G15_PLAIN || form > PF_G15_MEDIAN_MIX) return fail(c, PF_ERR_ARG, "gauss15 form %d (0..3)", form);
+  if (n_batch < 1 || n_batch > 3 || max_blocks < 0) return fail(c, PF_ERR_ARG, "n_batch %d (1..3) / max_blocks %d (>= 0)", n_batch, max_blocks);
+  if (int e = check_image(c, w, h)) return e;
+  const bool ups = form == PF_G15_UPSAMPLE, mix = form == PF_G15_MIX || form == PF_G15_MEDIAN_MIX;
+  if (!src || !dst || (mix && (!a0 || !a1)) || (ups && !up_out)) return fail(c, PF_ERR_ARG, "null pointer");
+  if (ups) { if (int e = check_image(c, sw, sh)) return e; } else { sw = w; sh = h; }
+  const size_t n = size_t(w) * h, ns = size_t(sw) * sh;
+  StageSlab L;
+  const size_t oS = L.take(ns * 8), oA0 = L.take(n * 4), oA1 = L.take(n * 4), oD = L.take(n * 8), oU = L.take(n * 8);
+  const size_t stride = L.stride();
+  char* base = (char*)ensure(c, "sg_g15", stride * size_t(n_batch));
+  if (!base) return PF_ERR_NOMEM;
+  HIPCHK(c, hipMemsetAsync(base, 0xFF, stride * size_t(n_batch), sm));   // whatever a kernel reads outside its planes is a NaN
+  for (int p = 0; p < n_batch; ++p) {
+    char* sl = base + size_t(p) * stride;
+    HIPCHK(c, hipMemcpyAsync(sl + oS, src + size_t(p) * ns * 2, ns * 8, hipMemcpyHostToDevice, sm));
+    if (mix) {
+      HIPCHK(c, hipMemcpyAsync(sl + oA0, a0 + size_t(p) * n, n * 4, hipMemcpyHostToDevice, sm));
+      HIPCHK(c, hipMemcpyAsync(sl + oA1, a1 + size_t(p) * n, n * 4, hipMemcpyHostToDevice, sm));
+    }
+  }
+  Batch bt; bt.n = n_batch; bt.stride = n_batch > 1 ? stride : 0;
+  float* dS = (float*)(base + oS); float* dA0 = (float*)(base + oA0); float* dA1 = (float*)(base + oA1); float* dD = (float*)(base + oD); float* dU = (float*)(base + oU);
+  switch (form) {
+    case PF_G15_PLAIN: launch_gauss15(sm, dS, dD, w, h, c->g15, bt, max_blocks); break;
+    case PF_G15_MIX: launch_gauss15_mix(sm, dS, dA0, dA1, w, h, c->g15, dD, bt, max_blocks); break;
+    case PF_G15_UPSAMPLE: launch_gauss15_upsample(sm, dS, sw, sh, mul, dU, dD, w, h, c->g15, bt, max_blocks); break;
+    default: launch_median_gauss15_mix(sm, dS, dA0, dA1, w, h, c->g15, dD, bt, max_blocks); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  for (int p = 0; p < n_batch; ++p) {
+    const char* sl = base + size_t(p) * stride;
+    HIPCHK(c, hipMemcpyAsync(dst + size_t(p) * n * 2, sl + oD, n * 8, hipMemcpyDeviceToHost, sm));
+    if (ups) HIPCHK(c, hipMemcpyAsync(up_out + size_t(p) * n * 2, sl + oU, n * 8, hipMemcpyDeviceToHost, sm));
+  }
+  return finish(c);
+}
+// Host planes are packed (levels back to back, no padding); the device planes are a solve's pyramid planes: level l at off[l], offsets
+// rounded up to 64 elements (make_geometry).  Device planes are filled with 0xFF bytes before the inputs go in, and gradients / gate come
+// back as whole padded planes: what the kernels did not write still reads 0xFF.
+int pf_stage_level_table(pf_ctx* c, int n_levels, const int* ws, const int* hs, int n_batch, const float* img0, const float* img1, const float* a0, const float* a1,
+                         long long first, long long total, int max_blocks, long long* off_out, float* g0, float* g1, uint8_t* gate, int* boxes, int* count0) {
+  STAGE_BEGIN(c);
+  if (n_levels < 1 || n_levels > kLevelTableMax || !ws || !hs) return fail(c, PF_ERR_ARG, "%d levels (1..%d)", n_levels, kLevelTableMax);
+  if (n_batch < 1 || n_batch > 3 || max_blocks < 0) return fail(c, PF_ERR_ARG, "n_batch %d (1..3) / max_blocks %d (>= 0)", n_batch, max_blocks);
+  if (!img0 || !img1 || !a0 || !a1 || !off_out || !g0 || !g1 || !gate || !boxes || !count0) return fail(c, PF_ERR_ARG, "null pointer");
+  LevelTable t{}; t.n = n_levels;
+  size_t P = 0, Pexact = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    if (ws[l] < 2 || hs[l] < 2) return fail(c, PF_ERR_ARG, "level %d is %dx%d (at least 2x2)", l, ws[l], hs[l]);
+    const size_t px = size_t(ws[l]) * hs[l];
+    if (P + px >= (size_t(1) << 31)) return fail(c, PF_ERR_ARG, "level table too large");
+    t.w[l] = ws[l]; t.h[l] = hs[l]; t.off[l] = (unsigned)P; off_out[l] = (long long)P;
+    Pexact += px; P += (px + 63) & ~size_t(63);
+  }
+  off_out[n_levels] = (long long)P;
+  if (total == 0) total = (long long)P;
+  if (first < 0 || first % 4 || total % 4 || first > total || total > (long long)P) return fail(c, PF_ERR_ARG, "gradient range [%lld, %lld) of %zu elements (multiples of 4)", first, total, P);
+  StageSlab L;
+  const size_t oW = L.take(kGateWords * sizeof(int));   // first: the one area the fill below leaves alone (self-resetting, initialised once per layout)
+  const size_t oI0 = L.take(P * 4), oI1 = L.take(P * 4), oA0 = L.take(P * 4), oA1 = L.take(P * 4), oG0 = L.take(P * 8), oG1 = L.take(P * 8), oGate = L.take(P);
+  const size_t stride = L.stride();
+  char* base = (char*)ensure(c, "sg_tbl", stride * size_t(n_batch));
+  if (!base) return PF_ERR_NOMEM;
+  int* work = nullptr;
+  if (n_batch == 1) work = gate_work(c);   // a lone solve's area
+  else {
+    work = (int*)(base + oW);
+    if (c->tbl_slab != base || c->tbl_stride != stride || c->tbl_pairs < n_batch) {
+      const std::vector<int> init = gate_work_init();
+      for (int p = 0; p < n_batch; ++p) HIPCHK(c, hipMemcpy(base + size_t(p) * stride + oW, init.data(), init.size() * sizeof(int), hipMemcpyHostToDevice));
+      c->tbl_slab = base; c->tbl_stride = stride; c->tbl_pairs = n_batch;
+    }
+  }
+  if (!work) return PF_ERR_NOMEM;
+  for (int p = 0; p < n_batch; ++p) {
+    char* sl = base + size_t(p) * stride;
+    HIPCHK(c, hipMemsetAsync(sl + oI0, 0xFF, stride - oI0, sm));
+    const float* hsrc[4] = {img0, img1, a0, a1}; const size_t ooff[4] = {oI0, oI1, oA0, oA1};
+    for (int k = 0; k < 4; ++k) {
+      size_t e = 0;
+      for (int l = 0; l < n_levels; ++l) {
+        const size_t px = size_t(ws[l]) * hs[l];
+        HIPCHK(c, hipMemcpyAsync(sl + ooff[k] + size_t(t.off[l]) * 4, hsrc[k] + size_t(p) * Pexact + e, px * 4, hipMemcpyHostToDevice, sm));
+        e += px;
+      }
+    }
+  }
+  Batch bt; bt.n = n_batch; bt.stride = n_batch > 1 ? stride : 0;
+  launch_gradients_all(sm, (const float*)(base + oI0), (const float*)(base + oI1), (float*)(base + oG0), (float*)(base + oG1), t, size_t(first), size_t(total), c->g3_05, max_blocks, bt);
+  const int epoch = ++c->gate_epoch;
+  launch_gate_bbox_all(sm, (const float*)(base + oA0), (const float*)(base + oA1), (uint8_t*)(base + oGate), t, P, work, c->d_gate, epoch, bt, kGateWords * sizeof(int));
+  HIPCHK(c, hipGetLastError());
+  for (int p = 0; p < n_batch; ++p) {
+    unsigned cnt = 0;
+    if (int e = wait_gate_boxes(c, sm, epoch, n_levels, boxes + size_t(p) * n_levels * 4, cnt, p)) return e;
+    count0[p] = (int)cnt;
+    const char* sl = base + size_t(p) * stride;
+    HIPCHK(c, hipMemcpyAsync(g0 + size_t(p) * P * 2, sl + oG0, P * 8, hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipMemcpyAsync(g1 + size_t(p) * P * 2, sl + oG1, P * 8, hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipMemcpyAsync(gate + size_t(p) * P, sl + oGate, P, hipMemcpyDeviceToHost, sm));
+  }
+  return finish(c);
 }
 
 // ---- profiling ----

@@ -118,13 +118,14 @@ void launch_gradients_all(hipStream_t st, const float* pyr0, const float* pyr1, 
 // work[4*l..]: min x, min y, max x, max y of level l
 void launch_gate_bbox_all(hipStream_t st, const float* a0, const float* a1, uint8_t* gate, const LevelTable& t, size_t total, int* work, int* host_mapped,
                           int epoch, Batch bt = Batch(), size_t host_stride = 0 /* bytes between the pairs' mapped host areas */);
-void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch());
-void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch());
-void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh, float mul, float* up, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch());
-void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch());
+void launch_gauss15(hipStream_t st, const float* src, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch(), int max_blocks = 0 /* cap on the persistent blocks per plane; 0 = the launcher's choice */);
+void launch_median_gauss15_mix(hipStream_t st, const float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch(), int max_blocks = 0 /* cap on the persistent blocks per plane; 0 = the launcher's choice */);
+void launch_gauss15_upsample(hipStream_t st, const float* coarse, int sw, int sh, float mul, float* up, float* dst, int w, int h, const Gauss& g15, Batch bt = Batch(), int max_blocks = 0 /* cap on the persistent blocks per plane; 0 = the launcher's choice */);
+void launch_gauss15_mix(hipStream_t st, float* flow, const float* a0, const float* a1, int w, int h, const Gauss& g15, float* out, Batch bt = Batch(), int max_blocks = 0 /* cap on the persistent blocks per plane; 0 = the launcher's choice */);
 void launch_median5(hipStream_t st, const float* src, float* dst, int w, int h, Batch bt = Batch());   // direct form below 3 Mpix, LDS-tiled form above
 void launch_median5_form(hipStream_t st, const float* src, float* dst, int w, int h, bool tiled, Batch bt = Batch());   // a given form at any size (tests)
 void launch_upsample_cubic(hipStream_t st, const float* src, int sw, int sh, float* dst, int dw, int dh, float mul, Batch bt = Batch());
+bool upsample_cubic_fits(int sh, int dh);   // the scale launch_upsample_cubic covers: sh / dh <= 1.1875 (every pyramid: sh <= dh); it aborts on any other
 void launch_final_flow(hipStream_t st, const float* flow0, int sw, int sh, int pad_cols, int rows, int pad, float mul, const Gauss& g3,
                        float* out, Batch bt = Batch(), const ExtPtrs* outs = nullptr /* batched: the pairs' output planes instead of out */);
 // sweep

@@ -100,7 +100,7 @@ EXPORTS = [
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
     "pf_stage_diffusion", "pf_stage_upsample_cubic", "pf_stage_final", "pf_stage_adjust_initial_flow", "pf_stage_level",
-    "pf_stage_blend_smooth", "pf_stage_tile_blur",
+    "pf_stage_blend_smooth", "pf_stage_tile_blur", "pf_stage_gauss15_form", "pf_stage_level_table",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
@@ -562,6 +562,52 @@ class Context:
             raise ValueError("blend and merged_dis differ in shape")
         self._chk(self.l.pf_stage_tile_blur(self.h, _p(b), _p(m), cols, rows, int(step), int(k), int(form)))
         return b
+
+    def stage_gauss15_form(self, form, src, a0=None, a1=None, size=None, mul=1.0, max_blocks=0):
+        """One form of the fused Gaussian 15 ("plain", "mix", "ups", "med_mix") on a batch of planes: src (n, h, w, 2), or (h, w, 2) for a lone
+        plane; the MIX forms take alphas of shape src.shape[:-1]; "ups" takes the coarse planes as src and size=(w, h) of the result.
+        Returns dst, or (dst, up) for "ups", shaped like the input batch."""
+        fid = {"plain": 0, "mix": 1, "ups": 2, "med_mix": 3}[form]
+        s = _f32(src); lone = s.ndim == 3
+        if lone:
+            s = s[None]
+        n, sh, sw, _ = s.shape
+        w, h = size if fid == 2 else (sw, sh)
+        al = [None, None]
+        if fid in (1, 3):
+            al = [_f32(a)[None] if lone else _f32(a) for a in (a0, a1)]
+            assert al[0].shape == (n, h, w) and al[1].shape == (n, h, w)
+        dst = np.empty((n, h, w, 2), np.float32); up = np.empty((n, h, w, 2), np.float32) if fid == 2 else None
+        self._chk(self.l.pf_stage_gauss15_form(self.h, fid, n, int(max_blocks), _p(s), sw, sh, C.c_float(mul), None if al[0] is None else _p(al[0]),
+                                               None if al[1] is None else _p(al[1]), w, h, _p(dst), None if up is None else _p(up)))
+        if lone:
+            dst = dst[0]; up = None if up is None else up[0]
+        return (dst, up) if fid == 2 else dst
+
+    def stage_level_table(self, sizes, img0, img1, a0, a1, first=0, total=0, max_blocks=0):
+        """Gradients and gate + boxes + count of a whole level table.  sizes: [(w, h), ...]; img0 / img1 / a0 / a1: per pair a list of
+        (h, w) planes, one per level (a lone pair may pass the list itself instead of a list of lists).  Returns a dict: off (level
+        offsets in the padded plane + its size P), g0 / g1 (n, P, 2) float32 and gate (n, P) uint8 as whole padded planes (unwritten = 0xFF
+        bytes), boxes (n, levels, 4), count0 (n,)."""
+        nl = len(sizes)
+        if nl and isinstance(img0[0], np.ndarray) and img0[0].ndim == 2:
+            img0, img1, a0, a1 = [img0], [img1], [a0], [a1]
+        n = len(img0)
+
+        def pack(planes):
+            for pair in planes:
+                assert len(pair) == nl and all(pl.shape == (hh, ww) for pl, (ww, hh) in zip(pair, sizes))
+            return np.ascontiguousarray(np.concatenate([_f32(pl).ravel() for pair in planes for pl in pair]))
+        ws = (C.c_int * nl)(*[int(s[0]) for s in sizes]); hs = (C.c_int * nl)(*[int(s[1]) for s in sizes])
+        P = sum((int(w) * int(h) + 63) & ~63 for w, h in sizes)
+        off = np.zeros(nl + 1, np.int64)
+        g0 = np.empty((n, P, 2), np.float32); g1 = np.empty((n, P, 2), np.float32); gate = np.empty((n, P), np.uint8)
+        boxes = np.empty((n, nl, 4), np.int32); cnt = np.empty(n, np.int32)
+        pk = [pack(v) for v in (img0, img1, a0, a1)]
+        self._chk(self.l.pf_stage_level_table(self.h, nl, ws, hs, n, _p(pk[0]), _p(pk[1]), _p(pk[2]), _p(pk[3]), C.c_longlong(int(first)), C.c_longlong(int(total)),
+                                              int(max_blocks), _p(off), _p(g0), _p(g1), _p(gate), _p(boxes), _p(cnt)))
+        assert int(off[nl]) == P
+        return {"off": off, "g0": g0, "g1": g1, "gate": gate, "boxes": boxes, "count0": cnt}
 
     def set_solver_params(self, **kw):
         """PixFlow's constructor arguments for every later solve on this context (pf_set_solver_params); no arguments = the factory's presets.
