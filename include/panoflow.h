@@ -330,6 +330,13 @@ int pf_stage_blend_smooth(pf_ctx* ctx, float* blend_inout, const float* merged_d
  * (PF_ERR_ARG if it does not fit), 1 = streamed (any geometry whose window row, step + k - 1 floats, fits that LDS).  PF_ERR_ARG for
  * step < 1, k < 1, step >= min(cols, rows) (no tile), max(k/2, k-1-k/2) >= min(cols, rows), null pointers. */
 int pf_stage_tile_blur(pf_ctx* ctx, float* blend_inout, const float* merged_dis, int cols, int rows, int step, int k, int form);
+/* The final box blur of that smoothing alone (StitchTool.cpp:142-143: blur(blend, blend, Size(k, k)) with k = rows / 400) with the
+ * kernel width k given explicitly, through the launcher the stitch entry points use, on n_batch (1..3) planes laid out as the frames of a
+ * batched stitch step are.  src / dst hold n_batch packed cols x rows planes one after the other.  k <= 32 runs the row pass staged
+ * through LDS, k > 32 the one that reads straight from memory; k may exceed cols or rows (BORDER_REFLECT_101, reflected as often as
+ * needed).  The device planes are filled with 0xFF bytes first: a value read outside a plane comes back as a NaN.
+ * PF_ERR_ARG for k < 1, n_batch outside 1..3, cols or rows < 1, null pointers. */
+int pf_stage_box_blur(pf_ctx* ctx, int n_batch, const float* src, int cols, int rows, int k, float* dst);
 /* Every form of the fused Gaussian 15 (PixFlow.hpp:306-311, :389-403) through the launcher a solve uses, on n_batch (1..3) planes laid
  * out as the slabs of a batched solve are.  Host arrays hold n_batch packed planes one after the other.
  *   PF_G15_PLAIN:       src w x h float2                                  -> dst = GaussianBlur 15, sigma 8

@@ -210,6 +210,36 @@ int pf_stage_tile_blur(pf_ctx* c, float* blend, const float* md, int cols, int r
   if (int e = stage_down(c, blend, db, n * 4)) return e;
   return check_sweeps(c);
 }
+// The rows/400 box blur of the ramp smoothing alone (StitchTool.cpp:142-143) with the kernel width given explicitly, through the
+// launcher blend_ramp_dev uses (tests/test_gpu_stitch_forms.py).  n_batch frames as a batched stitch step lays them out: the ramps as
+// stitch_group's, the fp64 row sums and the result planes as ramp_planes', all 256-byte-aligned frame strides.  The three areas are
+// filled with 0xFF bytes before the ramps go in: whatever a kernel reads outside a plane is a NaN.
+int pf_stage_box_blur(pf_ctx* c, int n_batch, const float* src, int cols, int rows, int k, float* dst) {
+  STAGE_BEGIN(c);
+  if (!src || !dst) return fail(c, PF_ERR_ARG, "null pointer");
+  if (n_batch < 1 || n_batch > 3 || k < 1) return fail(c, PF_ERR_ARG, "n_batch %d (1..3) / k %d (>= 1)", n_batch, k);
+  if (int e = check_image(c, cols, rows)) return e;
+  const size_t n = size_t(cols) * rows;
+  RampGeom g; g.k2 = k;   // no tile pass: ramp_planes sets up the box blur's planes only
+  StitchPtrs p{};
+  RampWork w;
+  if (int e = ramp_planes(c, kRampBatch, n_batch, cols, rows, g, p, w)) return e;
+  size_t s4;
+  float* blend = frame_planes<float>(c, "sb_blend", n_batch, n * 4, s4);
+  if (!blend) return PF_ERR_NOMEM;
+  const size_t s8 = (n * 8 + 255) & ~size_t(255);   // frame_planes' strides of p.rs (p.tmp: s4)
+  HIPCHK(c, hipMemsetAsync(blend, 0xFF, s4 * n_batch, sm));
+  HIPCHK(c, hipMemsetAsync(p.rs[0], 0xFF, s8 * n_batch, sm));
+  HIPCHK(c, hipMemsetAsync(p.tmp[0], 0xFF, s4 * n_batch, sm));
+  for (int f = 0; f < n_batch; ++f) {
+    p.blend[f] = (float*)((char*)blend + f * s4);
+    HIPCHK(c, hipMemcpyAsync(p.blend[f], src + size_t(f) * n, n * 4, hipMemcpyHostToDevice, sm));
+  }
+  { PROF(c, sm, "box_blur"); launch_box_blur(sm, p, n_batch, cols, rows, k); }
+  HIPCHK(c, hipGetLastError());
+  for (int f = 0; f < n_batch; ++f) HIPCHK(c, hipMemcpyAsync(dst + size_t(f) * n, p.tmp[f], n * 4, hipMemcpyDeviceToHost, sm));
+  return finish(c);
+}
 
 // ---- every form of the fused Gaussian 15 and a whole level table (tests/test_gpu_stage_forms.py) ----
 // Slabs as a batched solve lays them out: one per pair, `stride` bytes apart, every plane at the same 256-byte-aligned offset inside.

@@ -100,7 +100,7 @@ EXPORTS = [
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
     "pf_stage_diffusion", "pf_stage_upsample_cubic", "pf_stage_final", "pf_stage_adjust_initial_flow", "pf_stage_level",
-    "pf_stage_blend_smooth", "pf_stage_tile_blur", "pf_stage_gauss15_form", "pf_stage_level_table",
+    "pf_stage_blend_smooth", "pf_stage_tile_blur", "pf_stage_box_blur", "pf_stage_gauss15_form", "pf_stage_level_table",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
@@ -562,6 +562,17 @@ class Context:
             raise ValueError("blend and merged_dis differ in shape")
         self._chk(self.l.pf_stage_tile_blur(self.h, _p(b), _p(m), cols, rows, int(step), int(k), int(form)))
         return b
+
+    def stage_box_blur(self, src, k):
+        """the final box blur of the ramp smoothing alone with an explicit kernel width: src (rows, cols), or (n, rows, cols) for a batch
+        of 1..3 planes; returns the blurred planes in the input's shape"""
+        s = _f32(src); lone = s.ndim == 2
+        if lone:
+            s = s[None]
+        n, rows, cols = s.shape
+        d = np.empty_like(s)
+        self._chk(self.l.pf_stage_box_blur(self.h, n, _p(s), cols, rows, int(k), _p(d)))
+        return d[0] if lone else d
 
     def stage_gauss15_form(self, form, src, a0=None, a1=None, size=None, mul=1.0, max_blocks=0):
         """One form of the fused Gaussian 15 ("plain", "mix", "ups", "med_mix") on a batch of planes: src (n, h, w, 2), or (h, w, 2) for a lone
