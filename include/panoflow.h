@@ -360,6 +360,27 @@ int pf_stage_level_table(pf_ctx* ctx, int n_levels, const int* ws, const int* hs
                          const float* alpha0, const float* alpha1, long long first, long long total, int max_blocks, long long* off_out,
                          float* g0, float* g1, uint8_t* gate, int* boxes, int* count0);
 
+/* The head of the pipeline in the forms a solve runs it (tests/test_gpu_front_forms.py): n_batch (1..3) pairs in slabs as a batched solve
+ * lays them out (n_batch = 1: the lone form), the slabs filled with 0xFF bytes before the inputs go in.  Host arrays hold the pairs one
+ * after the other.  pf_stage_preprocess and pf_stage_preprocess_batch return PF_ERR_ARG for pad < 0 or pad > cols (the kernel wraps a tap
+ * of the virtually padded image once) before anything is launched.
+ *   preprocess_batch: n_batch BGRA images of one size, each in a device buffer of its own (a caller's, to the kernel) -> per pair the grey
+ *     and the alpha half-resolution plane, each as ((w0 * h0 + 63) & ~63) floats: the plane and its padding inside the slab.
+ *   pyramid: level0 = per pair the four level-0 planes I0, I1, alpha0, alpha1 (w0 x h0 each) -> the solver's own pyramid loop.
+ *     mode 0: one level per launch; 1: the product's rule (by level size); 2 / 3: two / three levels per launch wherever that many are left.
+ *     Out: n_levels, ws / hs [n_levels], off [n_levels + 1] (level offsets in a plane and the plane size P, elements), ks [n_launches] =
+ *     levels written by each launch, planes = per pair four whole planes of P floats.  cap_levels / cap_plane: what ws / hs / off / ks
+ *     and a plane of `planes` hold (PF_ERR_ARG if the pyramid needs more).
+ *   adjust_initial_flow_batch: per pair the four planes of one w x h level, flows zero-filled, the ratio scratch in the slab ->
+ *     per pair the flow plane as ((2 * w * h + 63) & ~63) floats.
+ *   intensity_ratio: k_intensity_ratio (PixFlow.hpp:190-205) on n elements per pair -> one ratio per pair. */
+int pf_stage_preprocess_batch(pf_ctx* ctx, int n_batch, const uint8_t* bgra, int cols, int rows, int pad, float* gray_half, float* alpha_half);
+int pf_stage_pyramid(pf_ctx* ctx, int n_batch, int mode, const float* level0, int w0, int h0, int cap_levels, long long cap_plane,
+                     int* n_levels, int* ws, int* hs, long long* off, int* ks, int* n_launches, float* planes);
+int pf_stage_adjust_initial_flow_batch(pf_ctx* ctx, int n_batch, const float* i0, const float* i1, const float* a0, const float* a1,
+                                       int w, int h, int hint, int max_percentage, float* flow_out);
+int pf_stage_intensity_ratio(pf_ctx* ctx, int n_batch, const float* i0, const float* i1, const float* a0, const float* a1, int n, float* ratio_out);
+
 /* ---- flow visualisation ---------------------------------------------------------------------
  * The reference's debugging views of a flow (CPU/OpticalFlow.cpp:147-204, declared in CPU/OpticalFlow.hpp:72-76), byte for byte,
  * on the device.  The reference computes them with OpenCV 3.2 on the host; here they are restated kernels:

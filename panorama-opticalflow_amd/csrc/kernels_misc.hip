@@ -139,6 +139,11 @@ __global__ __launch_bounds__(kSegW) void k_adjust_initial_flow(const float* __re
   flow[size_t(i0y) * w + i0x] = make_float2(float(i1xBest - i0x), float(i1yBest - i0y));
 }
 
+// the ratio of n elements alone: what the search launches in front of itself above 4096 pixels (and a stage test, at any n)
+void launch_intensity_ratio(hipStream_t st, const float* i0, const float* i1, const float* a0, const float* a1, int n, float* ratio, Batch bt) {
+  hipLaunchKernelGGL(k_intensity_ratio, dim3(1, 1, bt.n), dim3(256), 0, st, i0, i1, a0, a1, n, ratio, bt.stride);
+}
+
 // `flow` must be zero-filled by the caller (PixFlow.hpp:298).  i1eq_tmp: >= 1 float of scratch (the ratio).
 void launch_adjust_initial_flow(hipStream_t st, const float* i0, const float* i1, const float* a0, const float* a1, int w, int h, int hint,
                                 int max_pct, float* ratio_tmp, float* flow, Batch bt) {
@@ -155,7 +160,7 @@ void launch_adjust_initial_flow(hipStream_t st, const float* i0, const float* i1
   // levels up to 4096 pixels (every coarsest level of a pyramid whose images are not extreme strips): the search kernel sums the
   // intensity ratio itself, one launch instead of two (0.13 -> 0.09 ms per stitch step on the 5-step chain)
   const bool fused = w * h <= 4096;
-  if (!fused) hipLaunchKernelGGL(k_intensity_ratio, dim3(1, 1, bt.n), dim3(256), 0, st, i0, i1, a0, a1, w * h, ratio_tmp, bt.stride);
+  if (!fused) launch_intensity_ratio(st, i0, i1, a0, a1, w * h, ratio_tmp, bt);
   dim3 grid((w + kSegW - 1) / kSegW, h, bt.n);
   size_t lds = (size_t(2) * 5 * (kSegW + 4) + size_t(2) * (5 + bh - 1) * (kSegW + 4 + bw - 1)) * sizeof(float);   // <= ~14 KB at max_percentage 100
   if (fused && lds < 2 * 1024 * sizeof(float)) lds = 2 * 1024 * sizeof(float);

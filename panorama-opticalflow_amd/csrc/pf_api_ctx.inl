@@ -172,9 +172,8 @@ struct Geometry {
   size_t P;                 // total level pixels (padded to 64 per level)
   size_t Pexact;
 };
-Geometry make_geometry(int cols, int rows, int pad, float pyrScale = kPyrScaleFactor) {
-  Geometry g; g.cols = cols; g.rows = rows; g.pad = pad; g.ce = cols + 2 * pad;
-  g.w0 = int(g.ce * kDownscaleFactor); g.h0 = int(rows * kDownscaleFactor);
+// the levels below level 0 (g.w0 x g.h0), their offsets inside a pyramid plane and the totals
+void fill_levels(Geometry& g, float pyrScale) {
   g.ws = {g.w0}; g.hs = {g.h0};
   while ((int)g.ws.size() < kPyrMaxLevels) {
     const int nw = int(g.ws.back() * pyrScale + 0.5f), nh = int(g.hs.back() * pyrScale + 0.5f);
@@ -183,9 +182,21 @@ Geometry make_geometry(int cols, int rows, int pad, float pyrScale = kPyrScaleFa
     g.ws.push_back(nw); g.hs.push_back(nh);
   }
   g.n = (int)g.ws.size();
+  g.off.clear();
   size_t o = 0, pe = 0;
   for (int l = 0; l < g.n; ++l) { g.off.push_back(o); const size_t px = size_t(g.ws[l]) * g.hs[l]; pe += px; o += (px + 63) & ~size_t(63); }
   g.P = o; g.Pexact = pe;
+}
+Geometry make_geometry(int cols, int rows, int pad, float pyrScale = kPyrScaleFactor) {
+  Geometry g; g.cols = cols; g.rows = rows; g.pad = pad; g.ce = cols + 2 * pad;
+  g.w0 = int(g.ce * kDownscaleFactor); g.h0 = int(rows * kDownscaleFactor);
+  fill_levels(g, pyrScale);
+  return g;
+}
+// the pyramid under a given half-resolution plane (a stage test hands in level 0 itself)
+Geometry make_geometry_level0(int w0, int h0, float pyrScale = kPyrScaleFactor) {
+  Geometry g; g.cols = g.rows = g.pad = g.ce = 0; g.w0 = w0; g.h0 = h0;
+  fill_levels(g, pyrScale);
   return g;
 }
 

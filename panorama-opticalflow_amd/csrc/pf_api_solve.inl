@@ -207,6 +207,27 @@ int gate_level(pf_ctx* c, hipStream_t st, const float* a0, const float* a1, uint
   return 0;
 }
 
+// The pyramids of the four planes (both greys, both alphas), level 0 given: one launch per level while the levels are large, then two
+// and three levels per launch (the chain of dependent ~5 us launches is otherwise ~0.2 ms in front of everything; kernels_pre.hip:
+// k_pyr_chain).  mode 0: one level per launch; 1: the rule above (a solve, unless pf_config::pyramid_chaining is 0); 2 / 3 (stage tests): two /
+// three levels per launch whatever their size, fewer where fewer are left.  ks: the levels each launch wrote, in order.
+void launch_pyramids(pf_ctx* c, hipStream_t sm, float* const* pyrI, float* const* pyrA, const Geometry& g, int mode, Batch bt, std::vector<int>* ks = nullptr) {
+  for (int l = 1; l < g.n;) {
+    PROF(c, sm, "pyr_down");
+    const size_t px = size_t(g.ws[l]) * g.hs[l];
+    int k = 1;
+    if (mode == 1) { if (px <= 40000 && l + 2 < g.n) k = 3; else if (px <= 160000 && l + 1 < g.n) k = 2; }
+    else if (mode >= 2) k = std::min(mode, g.n - l);
+    if (k == 1)
+      launch_pyr_down4(sm, pyrI[0] + g.off[l - 1], pyrI[1] + g.off[l - 1], pyrA[0] + g.off[l - 1], pyrA[1] + g.off[l - 1], g.ws[l - 1], g.hs[l - 1],
+                       pyrI[0] + g.off[l], pyrI[1] + g.off[l], pyrA[0] + g.off[l], pyrA[1] + g.off[l], g.ws[l], g.hs[l], bt);
+    else
+      launch_pyr_chain4(sm, pyrI[0], pyrI[1], pyrA[0], pyrA[1], g.ws.data(), g.hs.data(), g.off.data(), l - 1, k, bt);
+    if (ks) ks->push_back(k);
+    l += k;
+  }
+}
+
 // The whole solver for 1 or 2 directions on device-resident packed BGRA images, for nb same-size pairs at once.
 // dir 0: I0 = img0, I1 = img1, hint0;  dir 1: I0 = img1, I1 = img0, hint1.  out[p * 2 + d]: cols x rows float2 (pad cropped).
 // nb == 1: the context's arena.  nb > 1 (throughput mode): the pairs' buffers are slabs of one layout, every kernel covers all pairs
@@ -246,21 +267,7 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
     { PROF(c, sm, "downscale_gray"); launch_downscale_gray(sm, nullptr, cols, rows, pad, half_tmp, pyrA[i], g.w0, g.h0, bt, &imgs); }
     { PROF(c, sm, "preblur5"); launch_gauss_small(sm, half_tmp, pyrI[i], g.w0, g.h0, 1, c->g5, bt); }
   }
-  // pyramids: one launch per level while the levels are large, then two and three levels per launch (the chain of dependent
-  // ~5 us launches is otherwise ~0.2 ms in front of everything; kernels_pre.hip: k_pyr_chain)
-  const int chainMode = c->cfg.pyramid_chaining;
-  for (int l = 1; l < g.n;) {
-    PROF(c, sm, "pyr_down");
-    const size_t px = size_t(g.ws[l]) * g.hs[l];
-    int k = 1;
-    if (chainMode) { if (px <= 40000 && l + 2 < g.n) k = 3; else if (px <= 160000 && l + 1 < g.n) k = 2; }
-    if (k == 1)
-      launch_pyr_down4(sm, pyrI[0] + g.off[l - 1], pyrI[1] + g.off[l - 1], pyrA[0] + g.off[l - 1], pyrA[1] + g.off[l - 1], g.ws[l - 1], g.hs[l - 1],
-                       pyrI[0] + g.off[l], pyrI[1] + g.off[l], pyrA[0] + g.off[l], pyrA[1] + g.off[l], g.ws[l], g.hs[l], bt);
-    else
-      launch_pyr_chain4(sm, pyrI[0], pyrI[1], pyrA[0], pyrA[1], g.ws.data(), g.hs.data(), g.off.data(), l - 1, k, bt);
-    l += k;
-  }
+  launch_pyramids(c, sm, pyrI, pyrA, g, c->cfg.pyramid_chaining ? 1 : 0, bt);
   // The host needs the per-level bounding boxes of the gate (they size the sweep launches) and the level-0 gate count (dense
   // or sparse sweep variant; full-canvas inputs, CPU/StitchTool.cpp:17-33): one fused kernel computes gate, boxes and count
   // and publishes them into mapped pinned memory; the host polls its epoch flag (microseconds, no blocking sync, no pageable

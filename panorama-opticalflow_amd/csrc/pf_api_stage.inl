@@ -12,8 +12,15 @@ static int stage_down(pf_ctx* c, void* host, const void* dev, size_t bytes) {
   return finish(c);
 }
 
+// k_downscale_gray wraps a tap of the virtually padded image [last pad columns | image | first pad columns] back into the image ONCE
+// (+- cols): that covers pad <= cols.  The product passes cols / 20; anything else is refused before a launch.
+static int check_pad(pf_ctx* c, int cols, int pad) {
+  if (pad < 0 || pad > cols) return fail(c, PF_ERR_ARG, "pad %d outside 0..cols (%d): the wrap padding repeats the image at most once per side", pad, cols);
+  return 0;
+}
 int pf_stage_preprocess(pf_ctx* c, const uint8_t* bgra, int cols, int rows, int pad, float* gray_half, float* alpha_half) {
   STAGE_BEGIN(c);
+  if (int e = check_pad(c, cols, pad)) return e;
   if (int e = check_dims(c, cols, rows, pad)) return e;
   const int dw = int((cols + 2 * pad) * kDownscaleFactor), dh = int(rows * kDownscaleFactor);
   uint8_t* d = (uint8_t*)stage_up(c, "sg_a", bgra, size_t(cols) * rows * 4);
@@ -353,6 +360,135 @@ int pf_stage_level_table(pf_ctx* c, int n_levels, const int* ws, const int* hs, 
     HIPCHK(c, hipMemcpyAsync(g1 + size_t(p) * P * 2, sl + oG1, P * 8, hipMemcpyDeviceToHost, sm));
     HIPCHK(c, hipMemcpyAsync(gate + size_t(p) * P, sl + oGate, P, hipMemcpyDeviceToHost, sm));
   }
+  return finish(c);
+}
+
+
+// ---- the head of the pipeline in the forms a solve runs (tests/test_gpu_front_forms.py) ----
+// As above: slabs laid out as a batched solve lays them, filled with 0xFF bytes before the inputs go in, outputs returned as whole planes
+// up to their 256-byte padding, so that a write outside its place shows.  n_batch = 1 runs the lone form (stride 0), as solve_n does.
+static int check_batch3(pf_ctx* c, int n_batch) {
+  if (n_batch < 1 || n_batch > 3) return fail(c, PF_ERR_ARG, "n_batch %d (1..3)", n_batch);
+  return 0;
+}
+int pf_stage_preprocess_batch(pf_ctx* c, int n_batch, const uint8_t* bgra, int cols, int rows, int pad, float* gray_half, float* alpha_half) {
+  STAGE_BEGIN(c);
+  if (int e = check_batch3(c, n_batch)) return e;
+  if (!bgra || !gray_half || !alpha_half) return fail(c, PF_ERR_ARG, "null pointer");
+  if (int e = check_pad(c, cols, pad)) return e;
+  if (int e = check_dims(c, cols, rows, pad)) return e;
+  const Geometry g = make_geometry(cols, rows, pad);
+  const size_t npad = (size_t(g.w0) * g.h0 + 63) & ~size_t(63), nimg = size_t(cols) * rows * 4;
+  StageSlab L;
+  const size_t oT = L.take(npad * 4), oG = L.take(npad * 4), oA = L.take(npad * 4);
+  const size_t stride = L.stride();
+  char* base = (char*)ensure(c, "sg_pre", stride * size_t(n_batch));
+  if (!base) return PF_ERR_NOMEM;
+  static const char* const names[3] = {"sg_img0", "sg_img1", "sg_img2"};   // one caller-style buffer per pair
+  ExtPtrs imgs{};
+  for (int p = 0; p < n_batch; ++p) {
+    void* d = stage_up(c, names[p], bgra + size_t(p) * nimg, nimg);
+    if (!d) return PF_ERR_NOMEM;
+    imgs.p[p] = d;
+  }
+  HIPCHK(c, hipMemsetAsync(base, 0xFF, stride * size_t(n_batch), sm));
+  Batch bt; bt.n = n_batch; bt.stride = n_batch > 1 ? stride : 0;
+  float* half_tmp = (float*)(base + oT); float* gray = (float*)(base + oG); float* alpha = (float*)(base + oA);
+  launch_downscale_gray(sm, nullptr, cols, rows, pad, half_tmp, alpha, g.w0, g.h0, bt, &imgs);   // as solve_n
+  launch_gauss_small(sm, half_tmp, gray, g.w0, g.h0, 1, c->g5, bt);
+  HIPCHK(c, hipGetLastError());
+  for (int p = 0; p < n_batch; ++p) {
+    const char* sl = base + size_t(p) * stride;
+    HIPCHK(c, hipMemcpyAsync(gray_half + size_t(p) * npad, sl + oG, npad * 4, hipMemcpyDeviceToHost, sm));
+    HIPCHK(c, hipMemcpyAsync(alpha_half + size_t(p) * npad, sl + oA, npad * 4, hipMemcpyDeviceToHost, sm));
+  }
+  return finish(c);
+}
+int pf_stage_pyramid(pf_ctx* c, int n_batch, int mode, const float* level0, int w0, int h0, int cap_levels, long long cap_plane, int* n_levels, int* ws, int* hs,
+                     long long* off, int* ks, int* n_launches, float* planes) {
+  STAGE_BEGIN(c);
+  if (int e = check_batch3(c, n_batch)) return e;
+  if (mode < 0 || mode > 3) return fail(c, PF_ERR_ARG, "chaining mode %d (0..3)", mode);
+  if (!level0 || !n_levels || !ws || !hs || !off || !ks || !n_launches || !planes) return fail(c, PF_ERR_ARG, "null pointer");
+  if (w0 < 2 || h0 < 2) return fail(c, PF_ERR_ARG, "level 0 is %dx%d (at least 2x2)", w0, h0);
+  if ((double)w0 * h0 > 5.0e8) return fail(c, PF_ERR_ARG, "level 0 too large");
+  const Geometry g = make_geometry_level0(w0, h0);
+  if (g.n > cap_levels || (long long)g.P > cap_plane) return fail(c, PF_ERR_ARG, "%d levels, planes of %zu elements: the caller's arrays hold %d and %lld", g.n, g.P, cap_levels, cap_plane);
+  StageSlab L;
+  size_t o[4];
+  for (int k = 0; k < 4; ++k) o[k] = L.take(g.P * 4);   // I0, I1, A0, A1
+  const size_t stride = L.stride(), n0 = size_t(w0) * h0;
+  char* base = (char*)ensure(c, "sg_pyr", stride * size_t(n_batch));
+  if (!base) return PF_ERR_NOMEM;
+  HIPCHK(c, hipMemsetAsync(base, 0xFF, stride * size_t(n_batch), sm));
+  for (int p = 0; p < n_batch; ++p)
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(base + size_t(p) * stride + o[k], level0 + (size_t(p) * 4 + k) * n0, n0 * 4, hipMemcpyHostToDevice, sm));
+  Batch bt; bt.n = n_batch; bt.stride = n_batch > 1 ? stride : 0;
+  float* pyrI[2] = {(float*)(base + o[0]), (float*)(base + o[1])}; float* pyrA[2] = {(float*)(base + o[2]), (float*)(base + o[3])};
+  std::vector<int> launched;
+  launch_pyramids(c, sm, pyrI, pyrA, g, mode, bt, &launched);
+  HIPCHK(c, hipGetLastError());
+  *n_levels = g.n; *n_launches = (int)launched.size();
+  for (int l = 0; l < g.n; ++l) { ws[l] = g.ws[l]; hs[l] = g.hs[l]; off[l] = (long long)g.off[l]; }
+  off[g.n] = (long long)g.P;
+  std::copy(launched.begin(), launched.end(), ks);   // at most g.n - 1
+  for (int p = 0; p < n_batch; ++p)
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(planes + (size_t(p) * 4 + k) * g.P, base + size_t(p) * stride + o[k], g.P * 4, hipMemcpyDeviceToHost, sm));
+  return finish(c);
+}
+// The slabs of the search entries: per pair the four planes of one level (I0, I1, A0, A1), the flow plane (flow_bytes, may be 0) and the ratio
+// scratch (SolveBufs::ratio).  up() lays them out, fills everything with 0xFF bytes -- the ratio scratch too: a NaN where it is read before it
+// is written -- and copies the inputs in.
+struct SearchSlabs {
+  char* base = nullptr; size_t stride = 0, o[4] = {0, 0, 0, 0}, oFlow = 0, oRatio = 0;
+  Batch bt;
+  const float* plane(int k) const { return (const float*)(base + o[k]); }
+  float* flow() const { return (float*)(base + oFlow); }
+  float* ratio() const { return (float*)(base + oRatio); }
+  int up(pf_ctx* c, hipStream_t sm, int n_batch, const float* const src[4], size_t n, size_t flow_bytes) {
+    StageSlab L;
+    const size_t npad = (n + 63) & ~size_t(63);
+    for (int k = 0; k < 4; ++k) o[k] = L.take(npad * 4);
+    oFlow = flow_bytes ? L.take(flow_bytes) : 0;
+    oRatio = L.take(256);
+    stride = L.stride();
+    base = (char*)ensure(c, "sg_search", stride * size_t(n_batch));
+    if (!base) return PF_ERR_NOMEM;
+    HIPCHK(c, hipMemsetAsync(base, 0xFF, stride * size_t(n_batch), sm));
+    for (int p = 0; p < n_batch; ++p)
+      for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(base + size_t(p) * stride + o[k], src[k] + size_t(p) * n, n * 4, hipMemcpyHostToDevice, sm));
+    bt.n = n_batch; bt.stride = n_batch > 1 ? stride : 0;
+    return 0;
+  }
+};
+int pf_stage_adjust_initial_flow_batch(pf_ctx* c, int n_batch, const float* i0, const float* i1, const float* a0, const float* a1, int w, int h, int hint, int max_pct,
+                                       float* flow_out) {
+  STAGE_BEGIN(c);
+  if (int e = check_batch3(c, n_batch)) return e;
+  if (!i0 || !i1 || !a0 || !a1 || !flow_out) return fail(c, PF_ERR_ARG, "null pointer");
+  if (int e = check_image(c, w, h)) return e;
+  if (hint < PF_HINT_RIGHT || hint > PF_HINT_UP || max_pct < 1 || max_pct > 100) return fail(c, PF_ERR_ARG, "hint %d (1..4) / max_percentage %d (1..100)", hint, max_pct);
+  const size_t n = size_t(w) * h, fpad = (n * 2 + 63) & ~size_t(63);
+  const float* const src[4] = {i0, i1, a0, a1};
+  SearchSlabs s;
+  if (int e = s.up(c, sm, n_batch, src, n, fpad * 4)) return e;
+  launch_fill_u32(sm, reinterpret_cast<unsigned*>(s.flow()), n * 2, 0u, s.bt);   // PixFlow.hpp:298, as solve_n
+  launch_adjust_initial_flow(sm, s.plane(0), s.plane(1), s.plane(2), s.plane(3), w, h, hint, max_pct, s.ratio(), s.flow(), s.bt);
+  HIPCHK(c, hipGetLastError());
+  for (int p = 0; p < n_batch; ++p) HIPCHK(c, hipMemcpyAsync(flow_out + size_t(p) * fpad, (char*)s.flow() + size_t(p) * s.stride, fpad * 4, hipMemcpyDeviceToHost, sm));
+  return finish(c);
+}
+int pf_stage_intensity_ratio(pf_ctx* c, int n_batch, const float* i0, const float* i1, const float* a0, const float* a1, int n, float* ratio_out) {
+  STAGE_BEGIN(c);
+  if (int e = check_batch3(c, n_batch)) return e;
+  if (!i0 || !i1 || !a0 || !a1 || !ratio_out) return fail(c, PF_ERR_ARG, "null pointer");
+  if (n < 1) return fail(c, PF_ERR_ARG, "%d elements", n);
+  const float* const src[4] = {i0, i1, a0, a1};
+  SearchSlabs s;
+  if (int e = s.up(c, sm, n_batch, src, size_t(n), 0)) return e;
+  launch_intensity_ratio(sm, s.plane(0), s.plane(1), s.plane(2), s.plane(3), n, s.ratio(), s.bt);
+  HIPCHK(c, hipGetLastError());
+  for (int p = 0; p < n_batch; ++p) HIPCHK(c, hipMemcpyAsync(ratio_out + p, (char*)s.ratio() + size_t(p) * s.stride, 4, hipMemcpyDeviceToHost, sm));
   return finish(c);
 }
 

@@ -101,6 +101,7 @@ EXPORTS = [
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
     "pf_stage_diffusion", "pf_stage_upsample_cubic", "pf_stage_final", "pf_stage_adjust_initial_flow", "pf_stage_level",
     "pf_stage_blend_smooth", "pf_stage_tile_blur", "pf_stage_box_blur", "pf_stage_gauss15_form", "pf_stage_level_table",
+    "pf_stage_preprocess_batch", "pf_stage_pyramid", "pf_stage_adjust_initial_flow_batch", "pf_stage_intensity_ratio",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
@@ -619,6 +620,49 @@ class Context:
                                               int(max_blocks), _p(off), _p(g0), _p(g1), _p(gate), _p(boxes), _p(cnt)))
         assert int(off[nl]) == P
         return {"off": off, "g0": g0, "g1": g1, "gate": gate, "boxes": boxes, "count0": cnt}
+
+    def stage_preprocess_batch(self, images, pad=0):
+        """1..3 BGRA images of one size, (n, rows, cols, 4), each in a device buffer of its own, through the batched form of the downscale and
+        the pre-blur (one image: the lone form).  Returns gray, alpha as (n, padded) float32: each pair's w0 * h0 plane and the padding behind
+        it inside the slab (unwritten = 0xFF bytes), and (w0, h0)."""
+        a = _u8(images); n, rows, cols, _ = a.shape
+        dw = int(np.float32(cols + 2 * pad) * np.float32(0.5)); dh = int(np.float32(rows) * np.float32(0.5))
+        npad = (max(dw * dh, 0) + 63) & ~63
+        g = np.empty((n, npad), np.float32); al = np.empty((n, npad), np.float32)
+        self._chk(self.l.pf_stage_preprocess_batch(self.h, n, _p(a), cols, rows, int(pad), _p(g), _p(al)))
+        return g, al, (dw, dh)
+
+    def stage_pyramid(self, level0, mode=1):
+        """The solver's pyramid loop on 1..3 pairs.  level0: (n, 4, h0, w0) = I0, I1, alpha0, alpha1 of each pair.  mode 0 = one level per
+        launch, 1 = the product's rule, 2 / 3 = that many levels per launch wherever that many are left.  Returns a dict: sizes [(w, h)],
+        off (level offsets + the plane size P), ks (levels written per launch), planes (n, 4, P) float32 whole padded planes."""
+        s = _f32(level0); n, four, h0, w0 = s.shape
+        assert four == 4
+        cap_l = 128; cap_p = 6 * w0 * h0 + 64 * cap_l   # a 0.9x pyramid holds 1 / (1 - 0.81) = 5.3 times level 0, plus 64 elements of padding per level
+        ws = (C.c_int * cap_l)(); hs = (C.c_int * cap_l)(); ks = (C.c_int * cap_l)(); nlev = C.c_int(0); nk = C.c_int(0)
+        off = np.zeros(cap_l + 1, np.int64)
+        buf = np.empty(n * 4 * cap_p, np.float32)
+        self._chk(self.l.pf_stage_pyramid(self.h, n, int(mode), _p(s), w0, h0, cap_l, C.c_longlong(cap_p), C.byref(nlev), ws, hs, _p(off), ks, C.byref(nk), _p(buf)))
+        nl = nlev.value; P = int(off[nl])
+        return {"sizes": [(ws[i], hs[i]) for i in range(nl)], "off": off[:nl + 1].copy(), "ks": [ks[i] for i in range(nk.value)],
+                "planes": buf[:n * 4 * P].reshape(n, 4, P).copy()}
+
+    def stage_adjust_initial_flow_batch(self, i0, i1, a0, a1, hint, max_pct):
+        """The coarsest-level search on 1..3 pairs of one level size in slabs, (n, h, w) each.  Returns (n, padded) float32: each pair's
+        h x w x 2 flow plane and the padding behind it (unwritten = 0xFF bytes)."""
+        s = [_f32(v) for v in (i0, i1, a0, a1)]; n, h, w = s[0].shape
+        assert all(v.shape == (n, h, w) for v in s)
+        f = np.empty((n, (2 * w * h + 63) & ~63), np.float32)
+        self._chk(self.l.pf_stage_adjust_initial_flow_batch(self.h, n, _p(s[0]), _p(s[1]), _p(s[2]), _p(s[3]), w, h, int(hint), int(max_pct), _p(f)))
+        return f
+
+    def stage_intensity_ratio(self, i0, i1, a0, a1):
+        """k_intensity_ratio on 1..3 pairs of n elements, (pairs, n) each; returns (pairs,) float32"""
+        s = [_f32(v) for v in (i0, i1, a0, a1)]; m, n = s[0].shape
+        assert all(v.shape == (m, n) for v in s)
+        r = np.empty(m, np.float32)
+        self._chk(self.l.pf_stage_intensity_ratio(self.h, m, _p(s[0]), _p(s[1]), _p(s[2]), _p(s[3]), n, _p(r)))
+        return r
 
     def set_solver_params(self, **kw):
         """PixFlow's constructor arguments for every later solve on this context (pf_set_solver_params); no arguments = the factory's presets.
