@@ -250,6 +250,58 @@ int pf_stitch_step_batch_planned_dev(pf_ctx* ctx, const pf_stitch_plan* plan, in
                                      const uint8_t* const* d_r, int cols, int rows, int max_percentage, uint8_t* const* d_out,
                                      int in_flight);
 
+/* ---- rig plans: the plans of a whole stitch chain from its input masks, and the chain in one call ----
+ * The composite of a step has alpha > 0 exactly where its L or its R has, so the R mask of step i of the chain of CPU/main.cpp:60-101 is
+ * top | L_1 | .. | L_{i-1}: every step's Map and ramp follow from the n + 1 input masks before a single flow is solved.  A rig plan makes
+ * them all at once: ONE kernel pass over the n + 1 images writes the n maps and counts their overlaps, and the n ramps are smoothed as
+ * one group (one countblend, one tile-smoothing and one box-blur launch).  n_steps is 1..16; l_bgra holds the n_steps left images in
+ * chain order; only alphas are read.  The canvases accepted and refused are pf_stitch_plan_create's, as is everything said there about
+ * contexts, handles after destroy (PF_ERR_ARG, looked up before they are dereferenced) and the state creation leaves alone.  A step
+ * whose masks do not overlap gets the plan pf_stitch_plan_create makes for those masks (overlap count 0).  5 B/px per step.
+ * pf_rig_plan_step hands out step `step` (0-based) as an ordinary pf_stitch_plan for pf_stitch_step_planned, pf_stitch_step_batch_planned*,
+ * pf_stitch_plan_info and pf_stitch_plan_download; the rig owns it: pf_stitch_plan_destroy on it is PF_ERR_ARG, pf_rig_plan_destroy (or
+ * pf_destroy) frees it.  NULL, with pf_last_error set, for a handle that is not a live rig plan of the context or a step outside it. */
+typedef struct pf_rig_plan pf_rig_plan;
+int pf_rig_plan_create(pf_ctx* ctx, int n_steps, const uint8_t* top_bgra, const uint8_t* const* l_bgra, int cols, int rows,
+                       size_t step_bytes, pf_rig_plan** rig_out);
+int pf_rig_plan_create_dev(pf_ctx* ctx, int n_steps, const uint8_t* d_top, const uint8_t* const* d_l, int cols, int rows,
+                           pf_rig_plan** rig_out);
+int pf_rig_plan_destroy(pf_ctx* ctx, pf_rig_plan* rig);
+/* geometry of a LIVE rig plan (outputs may be NULL) */
+int pf_rig_plan_info(const pf_rig_plan* rig, int* n_steps, int* cols, int* rows);
+const pf_stitch_plan* pf_rig_plan_step(pf_ctx* ctx, const pf_rig_plan* rig, int step);
+/* The whole chain of n_frames frames of the rig in one call.  top_bgra[k] and l_bgra[k * n_steps + i] are frame k's inputs (frame-major);
+ * out_bgra[k * n_steps + i] receives the bytes pf_stitch_step gives for step i + 1 of frame k's own chain.  out_bgra == NULL or a NULL
+ * entry skips that download.
+ * Verification first: before any solve every frame's region codes of every step are derived from its n_steps + 1 alphas and compared
+ * with the rig's maps.  If any frame is off the rig the call fails with PF_ERR_ARG, pf_last_error names the first such frame, its first
+ * differing step (1-based) and the pixel count, nothing is solved, the host form downloads nothing and the device form zero-fills its
+ * non-NULL d_out entries.  (The device form verifies all frames in one launch; the host form, whose images pass through the slots of
+ * the frames in flight, in one launch per wave.  It keeps two waves' images, so a call of up to 2 x in_flight frames uploads every
+ * image once; a longer call uploads the images of its third and later waves twice, the second time on the copy stream while the wave
+ * before computes -- pf_rig_set_upload_overlap(ctx, 0) issues that upload between the waves instead; results never depend on it.)
+ * Execution: frames go through in waves of `in_flight` (clamped as in pf_stitch_step_batch); a wave runs its steps one after the other
+ * as planned batched steps (the launches, lanes and groups of pf_stitch_step_batch_planned).  Synchronous on return.  The call leaves
+ * pf_stitch_step's chain state, pf_stitch_prefetch's records and the frame slots of pf_stitch_step_batch alone (pf_stitch_visualize's
+ * inputs are invalidated, as by any batched call).
+ * HBM is bounded by in_flight, not by n_frames.  Per frame in flight: two composites (8 B/px) + the planned step's 12 B/px of StitchTool
+ * planes + 16 B/px of flows + the solver slab; the host form adds the frame's n_steps + 1 inputs (4 (n_steps + 1) B/px), twice that
+ * where the call has more than in_flight frames.
+ * Device form: only a frame's LAST d_out entry must be non-NULL; a NULL entry keeps that composite in an internal plane (two per frame in
+ * flight, ping-ponged: a composite is never written over an input of its own step).  A non-NULL d_out that overlaps any input of the
+ * call or another d_out is PF_ERR_ARG; repeated input pointers are allowed.
+ * pf_rig_stitch / pf_rig_stitch_dev are these calls with one frame (l and out hold n_steps entries). */
+int pf_rig_stitch_batch(pf_ctx* ctx, const pf_rig_plan* rig, int n_frames, const uint8_t* const* top_bgra, const uint8_t* const* l_bgra,
+                        int cols, int rows, size_t step_bytes, int max_percentage, uint8_t* const* out_bgra, size_t out_step_bytes,
+                        int in_flight);
+int pf_rig_stitch_batch_dev(pf_ctx* ctx, const pf_rig_plan* rig, int n_frames, const uint8_t* const* d_top, const uint8_t* const* d_l,
+                            int cols, int rows, int max_percentage, uint8_t* const* d_out, int in_flight);
+int pf_rig_set_upload_overlap(pf_ctx* ctx, int on);   /* default 1 */
+int pf_rig_stitch(pf_ctx* ctx, const pf_rig_plan* rig, const uint8_t* top_bgra, const uint8_t* const* l_bgra, int cols, int rows,
+                  size_t step_bytes, int max_percentage, uint8_t* const* out_bgra, size_t out_step_bytes);
+int pf_rig_stitch_dev(pf_ctx* ctx, const pf_rig_plan* rig, const uint8_t* d_top, const uint8_t* const* d_l, int cols, int rows,
+                      int max_percentage, uint8_t* const* d_out);
+
 /* ---- device-resident entry points (packed buffers already in this context's HBM) -----------
  * Same semantics as above; used by bench.py (inputs resident when the clock starts) and by the
  * multi-GPU driver.  Pointers are device pointers on the context's device.  The calls are synchronous on

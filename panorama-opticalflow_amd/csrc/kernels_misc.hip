@@ -347,6 +347,73 @@ void launch_count_code(hipStream_t st, const uint8_t* map, int cols, int rows, i
   int blocks = (n / 16 + 255) / 256; if (blocks > 1024) blocks = 1024; if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_count_code, dim3(blocks), dim3(256), 0, st, map, n, (unsigned)code, count);
 }
+// K12 for a whole chain of a rig (rig plans): the region codes of ALL n_steps steps in one pass over the n_steps + 1 input images.  The R
+// mask of step i is the union of top's and L_1 .. L_{i-1}'s (a composite's alpha is > 0 exactly where one of its inputs' is), so a thread
+// keeps the union of its 4 pixels in a register: u = top.a > 0; per step code = (L_i.a > 0 ? 100 : 0) + (u ? 50 : 0), then u |= L_i.a > 0.
+// img: device table of the launch's image pointers, frame z at img + z * (n_steps + 1); maps.m[i]: the rig's map of step i.
+//   kMake:  stores the codes and adds each step's overlap pixels (code 150) to cnt[i], a device word (copied back with the plan: no mapped word needed);
+//   verify: stores nothing, compares with the rig's maps and adds the differing pixels to cnt[z * n_steps + i], words of mapped host
+//           memory read after the call's sync -- a matching frame issues no atomic at all.
+// Streams 4 (n_steps + 1) B/px and a 4-byte map access per step: 16-byte image loads where `vec` (every image pointer of the launch is
+// 16-byte aligned: caller-owned ones need not be), the last n % 4 pixels one by one; no early return in front of the wave votes.
+template <bool kMake>
+__global__ __launch_bounds__(256) void k_rig_maps(const uint8_t* const* __restrict__ img, RigMaps maps, int n_steps, int n, int vec, unsigned* __restrict__ cnt) {
+  const int z = blockIdx.z;
+  const uint8_t* const* __restrict__ f = img + (size_t)z * (n_steps + 1);
+  const long long i0 = (long long)(blockIdx.x * 256u + threadIdx.x) * 4;
+  const bool quad = i0 + 3 < n;
+  const int left = i0 < n ? (int)(n - i0) : 0;   // pixels of the tail thread (quad: unused)
+  // bit k = alpha of pixel i0 + k is > 0 (alpha is the top byte of a little-endian BGRA word); pixels past the end read as 0
+  auto alpha4 = [&](const uint8_t* p) -> unsigned {
+    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(p);
+    unsigned a = 0;
+    if (quad) {
+      uint4 v;
+      if (vec) v = *reinterpret_cast<const uint4*>(w + i0);
+      else v = make_uint4(w[i0], w[i0 + 1], w[i0 + 2], w[i0 + 3]);
+      a = (v.x >> 24 ? 1u : 0u) | (v.y >> 24 ? 2u : 0u) | (v.z >> 24 ? 4u : 0u) | (v.w >> 24 ? 8u : 0u);
+    } else {
+      for (int k = 0; k < left; ++k) a |= (w[i0 + k] >> 24 ? 1u : 0u) << k;
+    }
+    return a;
+  };
+  unsigned u = alpha4(f[0]);
+  for (int s = 0; s < n_steps; ++s) {
+    const unsigned l = alpha4(f[s + 1]);
+    uint32_t code4 = 0;
+    for (int k = 0; k < 4; ++k) code4 |= (((l >> k) & 1u) * 100u + ((u >> k) & 1u) * 50u) << (8 * k);
+    uint8_t* __restrict__ m = maps.m[s];
+    unsigned d = 0;
+    if (kMake) {
+      if (quad) *reinterpret_cast<uint32_t*>(m + i0) = code4;
+      else for (int k = 0; k < left; ++k) m[i0 + k] = (uint8_t)(code4 >> (8 * k));
+      d = __popc(l & u);
+    } else {
+      if (quad) {
+        const uint32_t x = code4 ^ *reinterpret_cast<const uint32_t*>(m + i0);
+        d = ((x & 0xffu) != 0) + ((x & 0xff00u) != 0) + ((x & 0xff0000u) != 0) + ((x >> 24) != 0);
+      } else for (int k = 0; k < left; ++k) d += m[i0 + k] != (uint8_t)(code4 >> (8 * k));
+    }
+    u |= l;
+    // every thread arrives here for every step: the vote and the shuffles see whole waves
+    if (__any(d != 0)) {
+      for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o);
+      if ((threadIdx.x & 63) == 0) {
+        if (kMake) __hip_atomic_fetch_add(cnt + s, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else __hip_atomic_fetch_add(cnt + (size_t)z * n_steps + s, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+  }
+}
+void launch_rig_maps_make(hipStream_t st, const uint8_t* const* img, bool aligned16, const RigMaps& maps, int n_steps, int cols, int rows, unsigned* count) {
+  const int n = cols * rows;
+  hipLaunchKernelGGL(k_rig_maps<true>, dim3((n + 1023) / 1024, 1, 1), dim3(256), 0, st, img, maps, n_steps, n, aligned16 ? 1 : 0, count);
+}
+void launch_rig_maps_verify(hipStream_t st, const uint8_t* const* img, bool aligned16, const RigMaps& maps, int n_steps, int nf, int cols, int rows,
+                            unsigned* diff_mapped) {
+  const int n = cols * rows;
+  hipLaunchKernelGGL(k_rig_maps<false>, dim3((n + 1023) / 1024, 1, nf), dim3(256), 0, st, img, maps, n_steps, n, aligned16 ? 1 : 0, diff_mapped);
+}
 
 // ------------------------------------------------------------------------------------------------
 // K13 GenerateBlend's per-pixel part + countblend (StitchTool.cpp:98-128, :148-191).  The map extended

@@ -21,6 +21,13 @@ struct pf_stitch_plan {
   long long overlap_px = 0;   // pixels of code 150
   uint8_t* map = nullptr;     // Map, 1 B/px
   float* ramp = nullptr;      // the finished blend ramp, 4 B/px
+  bool rig_owned = false;     // a step of a rig plan: pf_rig_plan_destroy frees it, pf_stitch_plan_destroy refuses it
+};
+// A rig plan (pf_rig_plan_create): the stitch plans of every step of one chain, made from the n + 1 input masks.  The step plans are
+// ordinary entries of the context's `plans` list; the rig itself is valid while the context's `rigs` list holds it.
+struct pf_rig_plan {
+  int n_steps = 0, cols = 0, rows = 0;
+  std::vector<pf_stitch_plan*> steps;
 };
 
 struct pf_ctx {
@@ -67,6 +74,11 @@ struct pf_ctx {
   unsigned* h_plan_diff = nullptr;      // mapped pinned, kMaxBatch words: pixels of frame f of a planned group whose region code differs from the plan's
   unsigned* d_plan_diff = nullptr;      // (k_match_verify adds, the host reads after the group's final sync and zeroes)
   std::vector<pf_stitch_plan*> plans;   // the stitch plans this context owns (pf_stitch_plan_create .. _destroy / pf_destroy)
+  std::vector<pf_rig_plan*> rigs;       // the rig plans this context owns (their step plans are in `plans`)
+  unsigned* h_rig_diff = nullptr;       // mapped pinned, rig_diff_cap words (grown on demand): frames x steps of a pf_rig_stitch_batch call,
+  unsigned* d_rig_diff = nullptr;       // pixels whose region code differs from the rig's (k_rig_maps adds, the host reads after a sync)
+  size_t rig_diff_cap = 0;
+  bool rig_overlap_uploads = true;   // pf_rig_stitch_batch: later waves' second upload beside the compute (pf_rig_set_upload_overlap)
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;
   std::vector<ProfPending> prof_pending;

@@ -215,6 +215,7 @@ void pf_destroy(pf_ctx* c) {
   hipDeviceSynchronize();
   for (auto& kv : c->bufs) if (kv.second.p) hipFree(kv.second.p);
   for (pf_stitch_plan* pl : c->plans) { hipFree(pl->map); hipFree(pl->ramp); delete pl; }
+  for (pf_rig_plan* rg : c->rigs) delete rg;   // (its step plans went with the list above)
   for (auto e : c->ev_pool) hipEventDestroy(e);
   for (auto& p : c->prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   if (c->ev_pre) hipEventDestroy(c->ev_pre);
@@ -232,6 +233,7 @@ void pf_destroy(pf_ctx* c) {
   if (c->h_status) hipHostFree(c->h_status);
   if (c->h_gate) hipHostFree(c->h_gate);
   if (c->h_plan_diff) hipHostFree(c->h_plan_diff);
+  if (c->h_rig_diff) hipHostFree(c->h_rig_diff);
   delete c;
 }
 

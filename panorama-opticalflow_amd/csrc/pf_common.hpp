@@ -189,6 +189,14 @@ void launch_match_images(hipStream_t st, const StitchPtrs& p, int nf, int cols, 
 void launch_match_verify(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, unsigned* diff_mapped);
 void launch_count_code(hipStream_t st, const uint8_t* map, int cols, int rows, int code, unsigned* count /* device word, zeroed by the caller */);
 void launch_countblend(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows);     // map -> blend, md
+// K12 for a whole chain (rig plans): img = a DEVICE table of nf x (n_steps + 1) image pointers, frame-major (top, L_1 .. L_n); the region
+// code of step i is derived from L_i's alpha and the running union of top's and L_1 .. L_{i-1}'s.  make: nf = 1, the codes are stored into
+// maps.m[i] and each step's overlap pixels (code 150) are added to count[i] (device words, zeroed by the caller).  verify: nothing is stored,
+// pixels whose code differs from maps.m[i] are added to diff_mapped[frame * n_steps + i] (mapped host words, zeroed by the caller).
+struct RigMaps { uint8_t* m[kMaxBatch]; };
+void launch_rig_maps_make(hipStream_t st, const uint8_t* const* img, bool aligned16, const RigMaps& maps, int n_steps, int cols, int rows, unsigned* count);
+void launch_rig_maps_verify(hipStream_t st, const uint8_t* const* img, bool aligned16, const RigMaps& maps, int n_steps, int nf, int cols, int rows,
+                            unsigned* diff_mapped);
 void launch_tile_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int step, int k, void* work, bool streamed = false,
                       void* scratch = nullptr);                                                // blend in place, by md
 void launch_box_blur(hipStream_t st, const StitchPtrs& p, int nf, int cols, int rows, int k); // blend -> tmp (rs: scratch)

@@ -4,6 +4,7 @@
 #define StitchTool_hpp
 
 #include <string>
+#include <vector>
 
 #include "util.hpp"
 
@@ -145,6 +146,49 @@ class StitchPlan {
 
  private:
   pf_stitch_plan* plan_ = nullptr;
+};
+
+// A rig plan (pf_rig_plan): the StitchPlans of every step of one rig's chain, made from the top image and the chain's left images before
+// any flow is solved (only alphas are read).  Owned by pano::context(); the object frees it (movable, not copyable).  step(i) is step
+// i + 1's plan for stitchStep-like calls on the C interface; the rig owns it.
+class RigPlan {
+ public:
+  RigPlan() {}
+  RigPlan(const Mat& colorImageT, const std::vector<Mat>& colorImagesL) {
+    std::vector<const uint8_t*> l;
+    for (const Mat& m : colorImagesL) {
+      if (colorImageT.type() != CV_8UC4 || m.type() != CV_8UC4 || m.rows != colorImageT.rows || m.cols != colorImageT.cols || m.step != colorImageT.step)
+        throw util::VrCamException("RigPlan: inputs must be CV_8UC4 images of equal size");
+      l.push_back(m.data);
+    }
+    pano::check(pf_rig_plan_create(pano::context(), (int)l.size(), colorImageT.data, l.data(), colorImageT.cols, colorImageT.rows, colorImageT.step, &rig_));
+  }
+  ~RigPlan() { reset(); }
+  RigPlan(const RigPlan&) = delete;
+  RigPlan& operator=(const RigPlan&) = delete;
+  RigPlan(RigPlan&& o) noexcept : rig_(o.rig_) { o.rig_ = nullptr; }
+  RigPlan& operator=(RigPlan&& o) noexcept {
+    if (this != &o) { reset(); rig_ = o.rig_; o.rig_ = nullptr; }
+    return *this;
+  }
+  void reset() {
+    if (rig_) pf_rig_plan_destroy(pano::context(), rig_);
+    rig_ = nullptr;
+  }
+  bool empty() const { return rig_ == nullptr; }
+  const pf_rig_plan* get() const { return rig_; }
+  int steps() const { int v = 0; if (rig_) pf_rig_plan_info(rig_, &v, nullptr, nullptr); return v; }
+  int cols() const { int v = 0; if (rig_) pf_rig_plan_info(rig_, nullptr, &v, nullptr); return v; }
+  int rows() const { int v = 0; if (rig_) pf_rig_plan_info(rig_, nullptr, nullptr, &v); return v; }
+  const pf_stitch_plan* step(int i) const {
+    const pf_stitch_plan* p = pf_rig_plan_step(pano::context(), rig_, i);
+    if (!p) throw util::VrCamException(std::string("panoflow: ") + pf_last_error(pano::context()));
+    return p;
+  }
+  long long overlapPixels(int i) const { long long v = 0; pf_stitch_plan_info(step(i), nullptr, nullptr, &v); return v; }
+
+ private:
+  pf_rig_plan* rig_ = nullptr;
 };
 
 // stitchStep on a plan: the same bytes without recomputing the map and the ramp; throws if the frame's masks are not the plan's.

@@ -86,6 +86,8 @@ def lib(exp=False):
         _lib.pf_dist_barrier.argtypes = [C.c_void_p]
         _lib.pf_last_swept_steps.restype = C.c_longlong
         _lib.pf_last_swept_steps.argtypes = [C.c_void_p]
+        _lib.pf_rig_plan_step.restype = C.c_void_p
+        _lib.pf_rig_plan_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -96,6 +98,8 @@ EXPORTS = [
     "pf_stitch_step_batch", "pf_stitch_step_batch_dev",
     "pf_stitch_plan_create", "pf_stitch_plan_create_dev", "pf_stitch_plan_destroy", "pf_stitch_plan_info", "pf_stitch_plan_download",
     "pf_stitch_step_planned", "pf_stitch_step_batch_planned", "pf_stitch_step_batch_planned_dev",
+    "pf_rig_plan_create", "pf_rig_plan_create_dev", "pf_rig_plan_destroy", "pf_rig_plan_info", "pf_rig_plan_step",
+    "pf_rig_stitch_batch", "pf_rig_stitch_batch_dev", "pf_rig_stitch", "pf_rig_stitch_dev", "pf_rig_set_upload_overlap",
     "pf_dev_alloc", "pf_dev_free", "pf_host_alloc", "pf_host_free", "pf_upload", "pf_download", "pf_sync", "pf_checksum_dev", "pf_selftest_packed_chains",
     "pf_flow_bidir_dev", "pf_blend_dev", "pf_novel_view_dev", "pf_novel_view_batch_dev",
     "pf_stage_preprocess", "pf_stage_pyr_down", "pf_stage_gradients", "pf_stage_gauss", "pf_stage_median5", "pf_stage_sweep",
@@ -200,6 +204,30 @@ class StitchPlan:
     def close(self):
         if self.h and self.ctx.h:
             self.ctx._chk(self.ctx.l.pf_stitch_plan_destroy(self.ctx.h, self.h))
+        self.h = None
+
+
+class RigPlan:
+    """pf_rig_plan: the stitch plans of every step of one rig's chain (Context.rig_plan).  .steps are StitchPlan objects the rig owns
+    (usable wherever a plan is; closing one raises); close() frees the rig and its steps early."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, C.c_void_p(handle)
+        n, cols, rows = C.c_int(0), C.c_int(0), C.c_int(0)
+        ctx._chk(ctx.l.pf_rig_plan_info(self.h, C.byref(n), C.byref(cols), C.byref(rows)))
+        self.n_steps, self.cols, self.rows = n.value, cols.value, rows.value
+        self.steps = []
+        for i in range(self.n_steps):
+            h = ctx.l.pf_rig_plan_step(ctx.h, self.h, i)
+            if not h:
+                ctx._chk(-1)
+            self.steps.append(StitchPlan(ctx, h))
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx._chk(self.ctx.l.pf_rig_plan_destroy(self.ctx.h, self.h))
+            for p in self.steps:
+                p.h = None
         self.h = None
 
 
@@ -328,6 +356,52 @@ class Context:
         h = C.c_void_p(None)
         self._chk(self.l.pf_stitch_plan_create_dev(self.h, C.c_void_p(d_l), C.c_void_p(d_r), cols, rows, C.byref(h)))
         return StitchPlan(self, h.value)
+
+    def rig_plan(self, top, Ls):
+        """The plans of the whole chain top, Ls[0], Ls[1], ... (only alphas matter): RigPlan"""
+        t = _u8(top); rows, cols, _ = t.shape
+        ls = [_u8(a) for a in Ls]
+        assert all(a.shape == (rows, cols, 4) for a in ls)
+        arr = (C.c_void_p * max(len(ls), 1))(*[a.ctypes.data for a in ls])
+        h = C.c_void_p(None)
+        self._chk(self.l.pf_rig_plan_create(self.h, len(ls), _p(t), arr, cols, rows, C.c_size_t(cols * 4), C.byref(h)))
+        return RigPlan(self, h.value)
+
+    def rig_plan_dev(self, d_top, d_ls, cols, rows):
+        arr = (C.c_void_p * max(len(d_ls), 1))(*[C.c_void_p(int(x)) if x else None for x in d_ls])
+        h = C.c_void_p(None)
+        self._chk(self.l.pf_rig_plan_create_dev(self.h, len(d_ls), C.c_void_p(d_top), arr, cols, rows, C.byref(h)))
+        return RigPlan(self, h.value)
+
+    def rig_stitch_batch(self, rig, tops, Ls, max_pct, in_flight=8, want=None, out=None):
+        """The whole chain of len(tops) frames of the rig: Ls[k] = frame k's left images in chain order.  Returns outs[k][i], the
+        composite after step i + 1 of frame k; want(k, i) -> bool selects what is downloaded (default all; None where not), out[k][i]
+        are optional preallocated (rows, cols, 4) uint8 arrays (None entries skip).  Raises as a whole if any frame is off the rig."""
+        n, ns = len(tops), rig.n_steps
+        ts = [_u8(a) for a in tops]
+        ls = [[_u8(a) for a in row] for row in Ls]
+        rows, cols = rig.rows, rig.cols
+        assert all(a.shape == (rows, cols, 4) for a in ts) and len(ls) == n and all(len(r) == ns and all(a.shape == (rows, cols, 4) for a in r) for r in ls)
+        if out is not None:
+            outs = [list(r) for r in out]
+            assert all(o is None or (o.dtype == np.uint8 and o.shape == (rows, cols, 4) and o.flags["C_CONTIGUOUS"]) for r in outs for o in r)
+        else:
+            outs = [[np.empty((rows, cols, 4), np.uint8) if want is None or want(k, i) else None for i in range(ns)] for k in range(n)]
+        ptrs = lambda v: (C.c_void_p * max(len(v), 1))(*[a.ctypes.data if a is not None else None for a in v])
+        self._chk(self.l.pf_rig_stitch_batch(self.h, rig.h, n, ptrs(ts), ptrs([a for r in ls for a in r]), cols, rows, C.c_size_t(cols * 4), max_pct,
+                                             ptrs([o for r in outs for o in r]), C.c_size_t(cols * 4), in_flight))
+        return outs
+
+    def rig_set_upload_overlap(self, on):
+        """rig_stitch_batch, calls of more than two waves: the later waves' second upload beside the compute (default) or between the waves"""
+        self._chk(self.l.pf_rig_set_upload_overlap(self.h, int(bool(on))))
+
+    def rig_stitch_batch_dev(self, rig, d_tops, d_ls, max_pct, d_outs, in_flight=8):
+        """the device form: d_tops[k], d_ls[k][i], d_outs[k][i] device pointers (packed BGRA); only d_outs[k][-1] must be given"""
+        n = len(d_tops)
+        ptrs = lambda v: (C.c_void_p * max(len(v), 1))(*[C.c_void_p(int(x)) if x else None for x in v])
+        self._chk(self.l.pf_rig_stitch_batch_dev(self.h, rig.h, n, ptrs(d_tops), ptrs([x for r in d_ls for x in r]), rig.cols, rig.rows, max_pct,
+                                                 ptrs([x for r in d_outs for x in r]), in_flight))
 
     def stitch_step(self, L, R, max_pct, want_out=True, out=None, plan=None):
         """One iteration of main.cpp's loop on the device; R=None chains on the previous result kept in HBM.

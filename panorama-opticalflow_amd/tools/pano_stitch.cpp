@@ -14,6 +14,12 @@
 //   stitch plan (overlap map + blend ramp) is made from the first directory's <i>.tif and its R of that step (the top image, then its
 //   previous composite), and step i of all directories runs on it (pf_stitch_step_batch_planned): the same files, without recomputing
 //   the map and the ramp per directory.  A directory whose masks differ from the first one's ends the run with an error that names it.
+//   -rig_chain 1 (with -test_dirs ... -static_rig 1): ONE rig plan is made from the first directory's top image and <1..steps>.tif before
+//   anything is solved, and all directories run their whole chains through one pf_rig_stitch_batch call: the same files; a directory off
+//   the rig ends the run before any solve, with an error that names it and the step.  Host memory: the call takes all inputs and gives all
+//   composites at once, so the run holds steps + 1 images per directory until the call returns and steps composites until they are
+//   written: 4 (2 steps + 1) B/px per directory (25 GB for 16 directories of 9000x4000 x 5 steps), where -static_rig 1 alone holds one
+//   step's images at a time.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -176,12 +182,68 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
   return EXIT_SUCCESS;
 }
 
+// -rig_chain 1: the whole chain of every directory in one call on one rig plan
+static int runRigChain(const std::vector<std::string>& dirs, const std::string& top_img, const std::string& flow_alg, int nsteps, int in_flight) {
+  const int maxPct = pf_max_percentage_by_name(flow_alg.c_str());
+  if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + flow_alg);
+  if (nsteps < 1 || nsteps > 9) throw VrCamException("-rig_chain: -steps must be 1..9");
+  double StartTime = getCurrTimeSec();
+  const int n = (int)dirs.size();
+  std::vector<Mat> tops(n), Ls(size_t(n) * nsteps), outs(size_t(n) * nsteps);
+  std::vector<const uint8_t*> t(n), l(size_t(n) * nsteps);
+  std::vector<uint8_t*> o(size_t(n) * nsteps);
+  for (int k = 0; k < n; ++k) {
+    tops[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + top_img);
+    for (int i = 0; i < nsteps; ++i) Ls[size_t(k) * nsteps + i] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + char(i + 49) + ".tif");
+  }
+  auto same = [&](const Mat& m) { return m.type() == CV_8UC4 && m.rows == tops[0].rows && m.cols == tops[0].cols && m.step == tops[0].step; };
+  for (int k = 0; k < n; ++k) {
+    if (!same(tops[k])) throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
+    t[k] = tops[k].data;
+    for (int i = 0; i < nsteps; ++i) {
+      const size_t at = size_t(k) * nsteps + i;
+      if (!same(Ls[at])) throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
+      outs[at] = Mat(tops[0].rows, tops[0].cols, CV_8UC4);
+      l[at] = Ls[at].data; o[at] = outs[at].data;
+    }
+  }
+  RigPlan rig(tops[0], std::vector<Mat>(Ls.begin(), Ls.begin() + nsteps));
+  std::cout << "Rig plan of " << nsteps << " steps made!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
+  const int rc = pf_rig_stitch_batch(pano::context(), rig.get(), n, t.data(), l.data(), tops[0].cols, tops[0].rows, tops[0].step, maxPct, o.data(),
+                                     outs[0].step, in_flight);
+  if (rc != 0) {
+    // the frame and the step are read out of the library's message: the wording "frame <k> differs from the rig plan at step <i>" is
+    // report_rig_diff()'s in csrc/pf_api_stitch.inl (keep the two in step; tests/test_cli_rig_chain.py pins both)
+    const std::string msg = pf_last_error(pano::context());
+    const size_t at = msg.find("frame "), st = msg.find("differs from the rig plan at step ");
+    if (at != std::string::npos && st != std::string::npos) {
+      const int k = atoi(msg.c_str() + at + 6), i = atoi(msg.c_str() + st + 34);
+      if (k >= 0 && k < n)
+        throw VrCamException("-rig_chain: step " + std::to_string(i) + ": the alpha masks of directory " + dirs[k] + " are not those of " + dirs[0] +
+                             " (panoflow: " + msg + ")");
+    }
+    throw VrCamException("panoflow: " + msg);
+  }
+  tops.clear(); Ls.clear();   // the inputs are done with; every composite is released as soon as it is written
+  for (int k = 0; k < n; ++k)
+    for (int i = 1; i <= nsteps; ++i) {
+      Mat& o_ki = outs[size_t(k) * nsteps + i - 1];
+      if (i == nsteps) pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "FinalResult.png", o_ki);
+      else pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", o_ki);
+      o_ki = Mat();
+    }
+  std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
+  return EXIT_SUCCESS;
+}
+
 int main(int argc, char** argv) {
   try {
     auto flags = parseFlags(argc, argv);
     if (flags.count("test_dirs")) {   // every refusal before any device call
       if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
       const bool static_rig = flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0;
+      const bool rig_chain = flags.count("rig_chain") && atoi(flags["rig_chain"].c_str()) != 0;
+      if (rig_chain && !static_rig) throw VrCamException("-rig_chain 1 needs -static_rig 1 (it plans the whole chain of one rig)");
       if (flags.count("fused") && atoi(flags["fused"].c_str()) == 0) throw VrCamException("-test_dirs runs the fused step only (-fused 0 is not supported)");
       if (flags.count("visualize") && atoi(flags["visualize"].c_str()) != 0) throw VrCamException("-test_dirs does not support -visualize 1");
       if (flags.count("inputs")) throw VrCamException("-test_dirs does not support -inputs");
@@ -192,9 +254,11 @@ int main(int argc, char** argv) {
       const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
       const int in_flight = flags.count("in_flight") ? atoi(flags["in_flight"].c_str()) : 8;
       if (in_flight < 1 || in_flight > 32) throw VrCamException("-in_flight must be 1..32");
+      if (rig_chain) return runRigChain(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight);
       return runBatchDirs(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight, static_rig);
     }
     if (flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0) throw VrCamException("-static_rig 1 needs -test_dirs (it plans the batched step)");
+    if (flags.count("rig_chain") && atoi(flags["rig_chain"].c_str()) != 0) throw VrCamException("-rig_chain 1 needs -test_dirs ... -static_rig 1");
     const std::string FLAGS_test_dir = flags["test_dir"], FLAGS_top_img = flags["top_img"], FLAGS_flow_alg = flags["flow_alg"];
     const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
     const bool fused = !flags.count("fused") || atoi(flags["fused"].c_str()) != 0;   // -fused 0: the reference's object-by-object sequence
