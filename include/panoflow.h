@@ -75,10 +75,9 @@ typedef struct pf_config {
                                throughput form too (1: +17 % on 16 strips in flight; 0 keeps them in the latency form) */
   int full_width_batch_gradients; /* 1: in a batched solve the finest levels' gradients are one full-width launch (nothing to hide them
                                behind: the batch keeps every CU busy anyway), 0: the narrow launch of a lone pair (1) */
-  /* Cross-check implementations -- only in libpanoflow_exp.so (the -DPF_EXPERIMENTS build used by the test-suite);
-   * libpanoflow.so rejects anything but the defaults with PF_ERR_ARG. */
-  int sweep_impl;           /* 2: wavefront sweep (k_sweep_prep + k_sweep2); 1: the independent 64-rows-per-wave kernel; 3: LDS-tile relaxation */
-  int record_path;          /* 0: k_sweep_prep in front of the sweep; 1: loader waves compute the records; 2: prepass blocks inside the sweep launch */
+  /* Cross-check implementation -- only in libpanoflow_exp.so (the -DPF_EXPERIMENTS build used by the test-suite);
+   * libpanoflow.so rejects anything but the default with PF_ERR_ARG. */
+  int sweep_impl;           /* 2: wavefront sweep (k_sweep_prep + k_sweep2); 1: the independent 64-rows-per-wave kernel; any other value: PF_ERR_ARG in every build */
 } pf_config;
 void pf_config_init(pf_config* cfg);
 /* Self-test that pf_create already ran once for the context's device: the sweep's asm-block packed-fp32 chains against the

@@ -790,7 +790,7 @@ __device__ __forceinline__ bool compute_band(SmemT<G>& sm, const float2* __restr
         e = d_error2(g1, W, wm2, hm2, fW, cf, int(posv.x), int(posv.y), ra.x, ra.y, ra.z, ra.w, cand.x + addx, cand.y + addy);
         fin = select_step<false, TR>(e, eC, eCL, rC, cnd, okL, okT, rEps, cf.step, emin, vmax);
       }
-      // (a pixel that is not updated keeps C through its record: kKeepEnergy, see d_make_record)
+      // (a pixel that is not updated keeps C through its record: kKeepEnergy, see d_make_record_at)
       } else {
       { // Only what the step uses is loaded: a loaded register nothing reads is handed out again by the register allocator at once,
         // and the hardware must then wait for the load in flight before the new value may be written (s_waitcnt right behind the
@@ -842,8 +842,7 @@ __device__ __forceinline__ float2 own_gradient_step(float2 f, float e0, float ex
   return make_float2(f.x - step * gx, f.y - step * gy);
 }
 
-// One record of the prepass (slot = linear index in wavefront order, see k_sweep_prep): shared by the prepass kernel and by
-// the prepass blocks that ride inside the sweep launch (k_sweep2, MODE 2).
+// One record of the prepass (see k_sweep_prep).
 // ROWS = rows per band (8: latency / wide form, 32: throughput form).  RC: the record carries rC, the current flow after its own gradient
 // step (three energies per pixel: what the 8-lane step needs); !RC (throughput form): it carries C itself and E(C) only -- that step
 // takes the winner's gradient step itself, the current flow's included (one energy per pixel here instead of three).
@@ -884,22 +883,9 @@ __device__ __forceinline__ void d_make_record_at(int band, int s, int r, bool in
     }
   }
 }
-// the same from a linear slot index (row fastest, then step, then band): two 64-bit divisions -- only the lab build's prepass blocks
-// inside the sweep launch (MODE 2) still address their records this way
-template <int ROWS = kRows, bool RC = true>
-__device__ __forceinline__ void d_make_record(size_t tid, size_t total, const float2* __restrict__ g0, const float2* __restrict__ g1,
-                                              const float2* __restrict__ blurred, const uint8_t* __restrict__ gate, const float2* __restrict__ flow, int W,
-                                              int H, int forward, int transposed, int nstepsPad, float rW, const SolverCoef& cf, int uLo, int uHi, int bandLo, float4& a,
-                                              float4& b, float4& c) {
-  const int r = int(tid % ROWS);
-  const int s = int((tid / ROWS) % nstepsPad);
-  const int band = int(tid / (size_t(ROWS) * nstepsPad));
-  d_make_record_at<ROWS, RC>(band, s, r, tid < total, g0, g1, blurred, gate, flow, W, H, forward, transposed, rW, cf, uLo, uHi, bandLo, a, b, c);
-}
-
 // ------------------------------------------------------------------------------------------------
 // prepass: records in wavefront order for the ACTIVE window of the sweep -- the product's latency form (SOA): per band and chunk of 8 steps
-// [64 first quads][64 second quads], record (s % 8) * 8 + r; the lab forms: rec[((band*nstepsPad + s)*8 + r)*3 + j] with the third quad (x, y, -, -):
+// [64 first quads][64 second quads], record (s % 8) * 8 + r; the wide form (SwWide, AoS): rec[((band*nstepsPad + s)*8 + r)*3 + j] with the third quad (x, y, -, -):
 // band counts from bandLo, step s handles sweep-order column uLo + s - r (columns [uLo, uHi)).
 //   j=0: (I0x, I0y, blurred.x, blurred.y)   j=1: (E(C), rC.x, rC.y, Ea)   j=2: (x, y, -, -)     (the step reads 16 + 16 + 8 bytes)
 //   rC = C after its own gradient step, C - 0.5 * ((E(C+dx), E(C+dy)) - E(C)) / eps (IEEE operations: what the sweep's exact fast
@@ -1108,59 +1094,18 @@ __device__ __forceinline__ void sweep_loader_pair(SmemT<G>& sm, const float4* __
 // SwWide, 960 threads: waves 0-7 compute (two per SIMD), waves 8-11 load for a PAIR of adjacent bands each (their records,
 // and the one 33-row window the two share), waves 12 / 13 / 14 publish, poll, drain: four waves per SIMD, 128 VGPRs.
 // ------------------------------------------------------------------------------------------------
-// MODE 0: records come from k_sweep_prep (launched in front).  MODE 1: the loader waves compute them (experiment, slower).
-// MODE 2: the prepass rides INSIDE this launch -- blocks [nwgSweep, gridDim.x) compute the records in wavefront order (sweep
-// workgroup 0's first) and hand them over with the write-through + counter + acquire protocol of cdna_hip_programming.md G16/R1;
-// the first bands start a few microseconds after the launch instead of after a whole prepass kernel.
-template <class G, bool TR, bool FWD, bool SPARSE, int MODE>
+// The records come from k_sweep_prep, launched in front.
+template <class G, bool TR, bool FWD, bool SPARSE>
 __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict__ rec, const float2* __restrict__ g1, float2* __restrict__ flow,
                                                 unsigned long long* __restrict__ boundary, int* __restrict__ ctrl, int W, int H,
                                                 int nstepsPad, int nbands, float rW, float rEps, int uLo, int LSv, int bandLo, long long budgetTicks,
-                                                const float2* __restrict__ g0, const float2* __restrict__ blurred, const uint8_t* __restrict__ gate,
-                                                int nwgSweep, int* __restrict__ prepcnt, size_t bstride, SolverCoef cf) {
+                                                const float2* __restrict__ blurred, size_t bstride, SolverCoef cf) {
   {   // blockIdx.z = pair of a batched launch: an independent sweep with its own ticket, granules and records
     const size_t bo = size_t(blockIdx.z) * bstride;
-    PF_BOFF(rec, bo); PF_BOFF(g1, bo); PF_BOFF(flow, bo); PF_BOFF(boundary, bo); PF_BOFF(ctrl, bo); PF_BOFF(g0, bo); PF_BOFF(blurred, bo); PF_BOFF(gate, bo);
-    if (prepcnt != nullptr) PF_BOFF(prepcnt, bo);
+    PF_BOFF(rec, bo); PF_BOFF(g1, bo); PF_BOFF(flow, bo); PF_BOFF(boundary, bo); PF_BOFF(ctrl, bo); PF_BOFF(blurred, bo);
   }
   constexpr int kWaves = G::kWaves, kRS = G::kRS, kOS = G::kOS, kLoadAhead = G::kLoadAhead, kLoaders = G::kLoaders;
-  static_assert(MODE == 0 || G::kBPW == 1, "the experimental record paths exist in the latency form only");
   using Smem = SmemT<G>;
-  if (MODE == 2 && int(blockIdx.x) >= nwgSweep) {
-    // ======================= prepass block (MODE 2): 704 records, written through to memory, then counted in =======================
-    const int slotsPerWG = kWaves * nstepsPad * kRows;
-    const size_t total = size_t(nwgSweep) * slotsPerWG;
-    const size_t first = size_t(int(blockIdx.x) - nwgSweep) * blockDim.x, slot = first + threadIdx.x;
-    float4 a, b, c;
-    d_make_record(slot, total, g0, g1, blurred, gate, flow, W, H, FWD ? 1 : 0, TR ? 1 : 0, nstepsPad, rW, cf, uLo, uLo + LSv, bandLo, a, b, c);
-    if (slot < total) {
-      // sc1 (write-through) 16-byte stores through a buffer descriptor built from wave-uniform values (G16 R1)
-      typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-      const unsigned long long base = reinterpret_cast<unsigned long long>(rec);
-      const unsigned lo = __builtin_amdgcn_readfirstlane(unsigned(base)), hi = __builtin_amdgcn_readfirstlane(unsigned(base >> 32));
-      void* ubase = reinterpret_cast<void*>((unsigned long long)lo | ((unsigned long long)hi << 32));
-      const unsigned nbytes = __builtin_amdgcn_readfirstlane(unsigned(total * 48));
-      auto rsrc = __builtin_amdgcn_make_buffer_rsrc(ubase, 0, int(nbytes), 0x00020000);
-      const unsigned off = unsigned(slot) * 48u;
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(a.x), __float_as_uint(a.y), __float_as_uint(a.z), __float_as_uint(a.w)}, rsrc, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(b.x), __float_as_uint(b.y), __float_as_uint(b.z), __float_as_uint(b.w)}, rsrc, off + 16u, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b128(u4v{__float_as_uint(c.x), __float_as_uint(c.y), __float_as_uint(c.z), __float_as_uint(c.w)}, rsrc, off + 32u, 0, 16);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // EVERY storing wave drains its write-through stores ...
-    __syncthreads();                                    // ... before ONE lane counts the block in
-    if (threadIdx.x == 0 && first < total) {
-      const size_t last = (first + blockDim.x < total ? first + blockDim.x : total) - 1;
-      const int k0 = int(first / slotsPerWG), k1 = int(last / slotsPerWG);
-      const int n = int(last - first + 1), n0 = k0 == k1 ? n : int(size_t(k0 + 1) * slotsPerWG - first);
-      __hip_atomic_fetch_add(&prepcnt[k0], n0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (k1 != k0) __hip_atomic_fetch_add(&prepcnt[k1], n - n0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return;
-  }
-  // FUSED (MODE 1): FUSED PREPASS -- the loader waves compute the records themselves (same expressions as k_sweep_prep) while they
-  // run ahead of the wavefront: no prepass launch in front of the sweep, and the 2 x 48 B per level-pixel of record traffic
-  // through HBM (written by the prepass, read back here) disappears.  A pixel's own flow C is read before its step is
-  // computed and overwritten (by the drainer) only afterwards, so reading it from the plane being updated is safe.
   // Active window of this sweep (everything outside it holds pixels that are not updated and keeps its flow):
   // nbands bands starting at band bandLo, sweep-order columns [uLo, uLo + LSv) along the step axis.  Steps, ring
   // indices and granule columns are relative to uLo; image coordinates are formed from uLo + relative column.
@@ -1309,31 +1254,13 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
       const int sx = TR ? ov : ou, sy = TR ? ou : ov;   // back to image axes
       ox = FWD ? sx : -sx; oy = FWD ? sy : -sy;
     };
-    constexpr bool fused = MODE == 1;
-    constexpr bool soa = MODE == 0;   // the product's record stream: 32-byte records, [64 first quads][64 second quads] per chunk (k_sweep_prep<.., SOA>)
-    const float4* recw = fused ? nullptr : rec + size_t(band0 + w) * nstepsPad * (kRows * (soa ? 2 : 3));
+    // the product's record stream: 32-byte records, [64 first quads][64 second quads] per chunk (k_sweep_prep<.., SOA>)
+    const float4* recw = rec + size_t(band0 + w) * nstepsPad * (kRows * 2);
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float wm2 = float(W) - 2.0f, hm2 = float(H) - 2.0f, fW = float(W);
-    // fused prepass: this lane's slot inside a chunk is (step offset lane >> 3, row lane & 7)
+    // this lane's slot inside a chunk is (step offset lane >> 3, row lane & 7)
     const int lj = lane >> 3, lr = lane & 7;
     const int lib = (bandLo + band0 + w) * kRows + lr;       // position across the bands (absolute)
-    // record stream: lane i of a chunk's three loads holds quads i, i + 64, i + 128 of its 192; quad q is part q % 3 of record q / 3 -- the
-    // third part (x, y, -, -) gets the window OFFSET (ox, oy) in z / w
-    bool isC[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) isC[k] = (lane + 64 * k) % 3 == 2;
     int rh = 0, idle = 0;
-    if (MODE == 2) {
-      // the records of this workgroup's four bands are complete when its counter has reached their number: ONE word polled
-      // relaxed, ONE agent acquire after the match (drops this CU's stale L1 lines), then plain loads (G16 R1)
-      const int need = kWaves * nstepsPad * kRows;
-      int spins = 0;
-      while (__hip_atomic_load(&prepcnt[wg], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != need) {
-        __builtin_amdgcn_s_sleep(2);
-        if (spin_expired(spins, sm) || ld_cnt(&sm.abort)) { sm.abort = 1; __hip_atomic_store(&ctrl[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
     // ---- chunk 0's whole rectangle (31 columns x 24 rows, four blocks in one round trip) ----
     int pox, poy; int front, pov;
     {
@@ -1373,39 +1300,23 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
       float cox[kLoadAhead], coy[kLoadAhead]; bool cdupc[kLoadAhead], cdupr[kLoadAhead], cwhole[kLoadAhead];
       // window work of a chunk: the block of new columns (3 texels per lane), a ninth column (lanes 0-23), one new row (one texel per lane)
       float2 wv[kLoadAhead][5]; int wu[kLoadAhead][5], wvv[kLoadAhead][5]; bool wok[kLoadAhead][5];
-      // fused prepass, phase 1: the inputs of up to kLoadAhead chunks are requested together (one round trip)
-      float2 qf[kLoadAhead], qg[kLoadAhead], qb[kLoadAhead]; int qgate[kLoadAhead], qx[kLoadAhead], qy[kLoadAhead], ia_of[kLoadAhead]; bool qvalid[kLoadAhead];
 #pragma unroll
       for (int c = 0; c < kLoadAhead; ++c) {
         const int r0 = rh + c * kChunk;
         va[c] = z4; vb4[c] = z4; vc[c] = z4; cox[c] = 0.f; coy[c] = 0.f; cdupc[c] = true; cdupr[c] = true; cwhole[c] = false;
         ld[c] = r0 < nsteps && (r0 + kChunk - oh <= kRS);
-        qf[c] = make_float2(0.f, 0.f); qg[c] = qf[c]; qb[c] = qf[c]; qgate[c] = 0; qx[c] = 0; qy[c] = 0; ia_of[c] = 0; qvalid[c] = false;
 #pragma unroll
         for (int k = 0; k < 5; ++k) { wv[c][k] = make_float2(0.f, 0.f); wu[c][k] = 0; wvv[c][k] = 0; wok[c][k] = false; }
         if (ld[c]) {
-          if (!fused) {
-            if (soa) {
-              const float4* src = recw + size_t(r0) * (kRows * 2);   // chunk r0 / 8: 128 quads
-              va[c] = src[lane]; vb4[c] = src[lane + 64];            // this lane's own record (step r0 + lane / 8, row lane % 8)
-              // its third quad: the pixel's coordinates (0, 0 for a slot without a pixel, as the prepass wrote them until round 5)
-              const int sstep = r0 + lj, ia = uLo + sstep - lr;
-              const bool inside = sstep - lr >= 0 && ia < uLo + LSv && ia < LS && lib < LB;
-              const int cxs = TR ? lib : ia, cys = TR ? ia : lib;   // position in sweep order
-              const int px = FWD ? cxs : W - 1 - cxs, py = FWD ? cys : H - 1 - cys;
-              vc[c] = make_float4(inside ? float(px) : 0.f, inside ? float(py) : 0.f, 0.f, 0.f);
-            } else {
-              const float4* src = recw + size_t(r0) * (kRows * 3);
-              va[c] = src[lane]; vb4[c] = src[lane + 64]; vc[c] = src[lane + 128];
-            }
-          } else {
+          {   // ---- the chunk's records ----
+            const float4* src = recw + size_t(r0) * (kRows * 2);   // chunk r0 / 8: 128 quads
+            va[c] = src[lane]; vb4[c] = src[lane + 64];            // this lane's own record (step r0 + lane / 8, row lane % 8)
+            // its third quad: the pixel's coordinates (0, 0 for a slot without a pixel, as the prepass wrote them until round 5)
             const int sstep = r0 + lj, ia = uLo + sstep - lr;
-            ia_of[c] = ia;
-            qvalid[c] = sstep - lr >= 0 && ia < uLo + LSv && ia < LS && lib < LB;
+            const bool inside = sstep - lr >= 0 && ia < uLo + LSv && ia < LS && lib < LB;
             const int cxs = TR ? lib : ia, cys = TR ? ia : lib;   // position in sweep order
-            qx[c] = qvalid[c] ? (FWD ? cxs : W - 1 - cxs) : 0; qy[c] = qvalid[c] ? (FWD ? cys : H - 1 - cys) : 0;
-            const int idx = qy[c] * W + qx[c];
-            qf[c] = flow[idx]; qgate[c] = gate[idx]; qg[c] = g0[idx]; qb[c] = blurred[idx];
+            const int px = FWD ? cxs : W - 1 - cxs, py = FWD ? cys : H - 1 - cys;
+            vc[c] = make_float4(inside ? float(px) : 0.f, inside ? float(py) : 0.f, 0.f, 0.f);
           }
           // ---- the chunk's window: offset (at most one texel from the previous chunk's), new columns, new row ----
           const int j = r0 / kChunk;
@@ -1460,43 +1371,16 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
           front = need_front > front ? need_front : front; pov = ov; pox = tx; poy = ty; cox[c] = float(tx); coy[c] = float(ty);
         }
       }
-      // fused prepass, phase 2: own-flow terms E(C), E(C+dx), E(C+dy) -- the expressions of k_sweep_prep -- straight into the record
-      // ring (the slots are free: ld[c] checked the ring room; they are published further down)
-      if (fused) {
-#pragma unroll
-        for (int c = 0; c < kLoadAhead; ++c) {
-          if (ld[c]) {
-            const float2 f = qf[c], g = qg[c], bl = qb[c];
-            const bool on = qvalid[c] && qgate[c] != 0;
-            const float e0 = d_error2g(g1, W, wm2, hm2, fW, rW, cf, qx[c], qy[c], g.x, g.y, bl.x, bl.y, f.x, f.y);
-            const float e1 = d_error2g(g1, W, wm2, hm2, fW, rW, cf, qx[c], qy[c], g.x, g.y, bl.x, bl.y, f.x + kGradEpsilon, f.y + 0.0f);
-            const float e2 = d_error2g(g1, W, wm2, hm2, fW, rW, cf, qx[c], qy[c], g.x, g.y, bl.x, bl.y, f.x + 0.0f, f.y + kGradEpsilon);
-            float4* dst = &sm.rec[w][(rh + c * kChunk) % kRS][0][0] + lane * 3;   // slot (lane >> 3, lane & 7) = linear slot `lane`
-            dst[0] = on ? make_float4(g.x, g.y, bl.x, bl.y) : z4;
-            const float2 fv = make_float2(qvalid[c] ? f.x : 0.f, qvalid[c] ? f.y : 0.f);
-            const float2 rc0 = on ? own_gradient_step(f, e0, e1, e2, cf.step) : fv;
-            dst[1] = make_float4(on ? e0 : kKeepEnergy, rc0.x, rc0.y, (on && ia_of[c] > 0) ? e0 : kKeepEnergy);
-            dst[2] = make_float4(float(qx[c]), float(qy[c]), on ? cox[c] : __builtin_nanf(""), on ? coy[c] : __builtin_nanf(""));
-          }
-        }
-      }
       bool progress = false;
 #pragma unroll
       for (int c = 0; c < kLoadAhead; ++c) {
         if (ld[c]) {
           float4* dst = &sm.rec[w][rh % kRS][0][0];
-          if (!fused && soa) {
-            // "updated" is E(C) != kKeepEnergy (d_make_record_at): the window offset for such a pixel, NaN ("never leaves the window") otherwise
-            const bool on = vb4[c].x != kKeepEnergy;
-            float4 q2 = vc[c];
-            q2.z = on ? cox[c] : __builtin_nanf(""); q2.w = on ? coy[c] : __builtin_nanf("");
-            dst[3 * lane] = va[c]; dst[3 * lane + 1] = vb4[c]; dst[3 * lane + 2] = q2;
-          } else if (!fused) {
-            float4 v3[3] = {va[c], vb4[c], vc[c]};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) if (isC[k]) { v3[k].z = cox[c] + v3[k].z; v3[k].w = coy[c] + v3[k].w; }   // the chunk's window offset (+ 0, or + NaN where the pixel is not updated)
-            dst[lane] = v3[0]; dst[lane + 64] = v3[1]; dst[lane + 128] = v3[2];
-          }
+          // "updated" is E(C) != kKeepEnergy (d_make_record_at): the window offset for such a pixel, NaN ("never leaves the window") otherwise
+          const bool on = vb4[c].x != kKeepEnergy;
+          float4 q2 = vc[c];
+          q2.z = on ? cox[c] : __builtin_nanf(""); q2.w = on ? coy[c] : __builtin_nanf("");
+          dst[3 * lane] = va[c]; dst[3 * lane + 1] = vb4[c]; dst[3 * lane + 2] = q2;
 #pragma unroll
           for (int k = 0; k < 3; ++k) if (cwhole[c] || wok[c][k]) win_store_block(wu[c][k], wvv[c][k], wv[c][k], cdupc[c], cdupr[c]);
           if (__any(wok[c][3])) { if (wok[c][3]) win_store(wu[c][3], wvv[c][3], wv[c][3]); }
@@ -1588,23 +1472,12 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
   {
     if ((wg == 0 && !staticTop) || wave != kWaves + kLoaders + 1) return;
     const unsigned long long* bnd_in = boundary + size_t(wg) * LSv;
-    const bool topFromPlane = MODE != 0 && wg == 0;   // (wg == 0 only gets here with a static top row)
     int bh = 0, idle = 0;
     while (bh < LSv) {
       const int oh0 = ld_cnt(&sm.outHead[0]);
       if (bh + 64 - oh0 <= kBS) {
         unsigned long long g = kNotReady;
-        if (bh + lane < LSv) {
-          if (topFromPlane) {
-            // fused prepass: the row above the window never changes during this sweep -- read it from the flow plane itself
-            const int ia = uLo + bh + lane, ib = bandLo * kRows - 1;
-            const int cxs = TR ? ib : ia, cys = TR ? ia : ib;
-            const int x = FWD ? cxs : W - 1 - cxs, y = FWD ? cys : H - 1 - cys;
-            g = pack2(flow[y * W + x]);
-          } else {
-            g = __hip_atomic_load(bnd_in + bh + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
+        if (bh + lane < LSv) g = __hip_atomic_load(bnd_in + bh + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const bool ready = (g != kNotReady) || (bh + lane >= LSv);
         const unsigned long long m = __ballot(ready);
         const int n = (m == ~0ull) ? 64 : __builtin_ctzll(~m);
@@ -1738,7 +1611,6 @@ namespace pf {
 static inline int wgs_for(int LB, int waves = SwLatency::kWaves) { const int nbands = (LB + kRows - 1) / kRows; return (nbands + waves - 1) / waves; }
 static inline int steps_pad(int LS) { return ((LS + kRows - 1) + kChunk - 1) / kChunk * kChunk; }
 int sweep2_num_wgs(int H) { return wgs_for(H); }
-int sweep2_num_wgs_max(int W, int H) { const int a = wgs_for(W), b = wgs_for(H); return a > b ? a : b; }
 size_t sweep2_boundary_elems(int W, int H) {   // hand-off granules of one sweep launch, either orientation (+1 row: the static row above the window)
   const size_t a = size_t(wgs_for(H) + 1) * W, b = size_t(wgs_for(W) + 1) * H;
   return a > b ? a : b;
@@ -1746,9 +1618,8 @@ size_t sweep2_boundary_elems(int W, int H) {   // hand-off granules of one sweep
 size_t sweep_boundary_elems(int W, int H) {   // hand-off granules a sweep launch on a W x H level may need (every sweep implementation of this build)
   size_t v = sweep2_boundary_elems(W, H);
 #ifdef PF_EXPERIMENTS
-  const size_t v1 = sweep1_boundary_elems(W, H), v3 = sweep_relax_boundary_elems(W, H);
+  const size_t v1 = sweep1_boundary_elems(W, H);
   if (v1 > v) v = v1;
-  if (v3 > v) v = v3;
 #endif
   return v;
 }
@@ -1768,42 +1639,25 @@ static bool launch_sweep2_form(hipStream_t st, const SweepArgs& a, float* rec) {
   if (win.empty) return false;   // nothing to update: the sweep is the identity
   const int tr = win.tr, uLo = win.uLo, uHi = win.uHi, LSv = win.LSv, bandLo = win.bandLo, nbands = win.nbands;
   const int nwg = win.nwg, nbandsPad = nwg * kWaves, nstepsPad = win.nstepsPad;
-  const size_t total = size_t(nbandsPad) * nstepsPad * kRows;
   const float rW = (float)(1.0 / (double)(float)a.W), rEps = (float)(1.0 / (double)kGradEpsilon);
-  // How the records reach the sweep.  0 (the product): k_sweep_prep in front of the sweep.  Two measured and rejected alternatives
-  // exist in the lab build only (-DPF_EXPERIMENTS, SweepArgs::prep_mode; latency form only), both bit-identical: 1 = the loader waves
-  // compute them (no record traffic through HBM, but 8 % slower: profiles/r02_fused_prepass_ab.txt); 2 = prepass blocks inside the
-  // sweep launch with a write-through + counter + acquire hand-off (the first bands start microseconds after the launch, yet the
-  // launch as a whole is not shorter: same file).
-#ifdef PF_EXPERIMENTS
-  const int mode = (G::kBPW != 1 || (a.prep_mode == 2 && (a.prepcnt == nullptr || total * 48 >= (size_t(1) << 31)))) ? 0 : a.prep_mode;
-#else
-  constexpr int mode = 0;
-#endif
-  if (mode == 0 && G::kBPW == 1)
+  // the records reach the sweep through k_sweep_prep, launched in front of it: the latency form's 32-byte SOA stream, the wide form's AoS three-quad stream
+  if (G::kBPW == 1)
     hipExtLaunchKernelGGL((k_sweep_prep<kRows, true, true>), dim3((unsigned)((nstepsPad + 256 / kRows - 1) / (256 / kRows)), (unsigned)nbandsPad, a.bt.n), dim3(256), 0, st, a.ev_start, nullptr, 0, a.g0, a.g1, a.blurred, a.gate, a.flow,
                           a.W, a.H, a.forward, tr, nstepsPad, nbandsPad, rW, reinterpret_cast<float4*>(rec), uLo, uHi, bandLo,
                           bandLo > 0 ? a.boundary : (unsigned long long*)nullptr, a.bt.stride, a.cf);
-  else if (mode == 0)
+  else
     hipExtLaunchKernelGGL((k_sweep_prep<kRows, true>), dim3((unsigned)((nstepsPad + 256 / kRows - 1) / (256 / kRows)), (unsigned)nbandsPad, a.bt.n), dim3(256), 0, st, a.ev_start, nullptr, 0, a.g0, a.g1, a.blurred, a.gate, a.flow,
                           a.W, a.H, a.forward, tr, nstepsPad, nbandsPad, rW, reinterpret_cast<float4*>(rec), uLo, uHi, bandLo,
                           bandLo > 0 ? a.boundary : (unsigned long long*)nullptr, a.bt.stride, a.cf);
-  hipEvent_t evs = mode == 0 ? nullptr : a.ev_start;   // without a prepass kernel the sweep launch carries both events
   // wall-clock budget of every wait inside the launch, in 100 MHz ticks: 2 s + 1000 x the expected duration (~0.5 us per step)
   const long long budget = 200000000ll + 1000ll * 50ll * (long long)(nstepsPad + 9 * nbands);
   const unsigned nthreads = G::kThreads;
-  const dim3 grid(mode == 2 ? nwg + (unsigned)((total + nthreads - 1) / nthreads) : nwg, 1, a.bt.n), block(nthreads);
-  const float4* r4 = mode == 1 ? nullptr : reinterpret_cast<const float4*>(rec);
-#define PF_LAUNCH_SWEEP2_(TRV, FWV, SPV, MDV) hipExtLaunchKernelGGL((k_sweep2<G, TRV, FWV, SPV, MDV>), grid, block, 0, st, evs, a.ev_stop, 0, r4, a.g1, a.flow, a.boundary, a.ctrl, a.W, a.H, nstepsPad, nbands, rW, rEps, uLo, LSv, bandLo, budget, a.g0, a.blurred, a.gate, nwg, a.prepcnt, a.bt.stride, a.cf)
-#ifdef PF_EXPERIMENTS
-#define PF_LAUNCH_SWEEP2__(TRV, FWV, SPV) do { if constexpr (G::kBPW == 1) { if (mode == 2) { PF_LAUNCH_SWEEP2_(TRV, FWV, SPV, 2); break; } if (mode == 1) { PF_LAUNCH_SWEEP2_(TRV, FWV, SPV, 1); break; } } PF_LAUNCH_SWEEP2_(TRV, FWV, SPV, 0); } while (0)
-#else
-#define PF_LAUNCH_SWEEP2__(TRV, FWV, SPV) PF_LAUNCH_SWEEP2_(TRV, FWV, SPV, 0)   /* the product library ships the MODE-0 variants only: 8 per workgroup shape */
-#endif
-#define PF_LAUNCH_SWEEP2(TRV, FWV) do { if (a.sparse) PF_LAUNCH_SWEEP2__(TRV, FWV, true); else PF_LAUNCH_SWEEP2__(TRV, FWV, false); } while (0)
+  const dim3 grid(nwg, 1, a.bt.n), block(nthreads);
+  const float4* r4 = reinterpret_cast<const float4*>(rec);
+#define PF_LAUNCH_SWEEP2_(TRV, FWV, SPV) hipExtLaunchKernelGGL((k_sweep2<G, TRV, FWV, SPV>), grid, block, 0, st, nullptr, a.ev_stop, 0, r4, a.g1, a.flow, a.boundary, a.ctrl, a.W, a.H, nstepsPad, nbands, rW, rEps, uLo, LSv, bandLo, budget, a.blurred, a.bt.stride, a.cf)
+#define PF_LAUNCH_SWEEP2(TRV, FWV) do { if (a.sparse) PF_LAUNCH_SWEEP2_(TRV, FWV, true); else PF_LAUNCH_SWEEP2_(TRV, FWV, false); } while (0)
   if (tr) { if (a.forward) PF_LAUNCH_SWEEP2(true, true); else PF_LAUNCH_SWEEP2(true, false); }
   else { if (a.forward) PF_LAUNCH_SWEEP2(false, true); else PF_LAUNCH_SWEEP2(false, false); }
-#undef PF_LAUNCH_SWEEP2__
   return true;
 #undef PF_LAUNCH_SWEEP2_
 #undef PF_LAUNCH_SWEEP2
@@ -1829,9 +1683,5 @@ bool launch_sweep2(hipStream_t st, const SweepArgs& a, float* rec) {
 #endif
   return launch_sweep2_form<SwLatency>(st, a, rec);
 }
-
-#ifdef PF_EXPERIMENTS
-#include "kernels_relax.inl"   // rejected experiment (41 % slower), kept bit-exact under test in the lab build only
-#endif
 
 }  // namespace pf

@@ -74,7 +74,7 @@ void pf_config_init(pf_config* cfg) {
   memset(cfg, 0, sizeof *cfg);
   cfg->struct_size = (int)sizeof *cfg;
   cfg->stagger_levels = -1; cfg->fuse_small_level_px = -1; cfg->fine_gradient_blocks = 64; cfg->pyramid_chaining = 1;
-  cfg->sweep_window = 1; cfg->sparse_sweep = -1; cfg->sweep_impl = 2; cfg->record_path = 0; cfg->batch_pairs = -1;
+  cfg->sweep_window = 1; cfg->sparse_sweep = -1; cfg->sweep_impl = 2; cfg->batch_pairs = -1;
   cfg->sweep_wide = -1; cfg->sweep_wide_threshold = 512; cfg->sweep_throughput_transposed = 1; cfg->full_width_batch_gradients = 1;
 }
 
@@ -184,23 +184,21 @@ pf_ctx* pf_create_cfg(const pf_config* user) {
 #ifdef PF_EXPERIMENTS
   // lab build only: the diagnostics under tests/micro select variants per process through the environment
   auto env_int = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
-  env_int("PANOFLOW_SWEEP", cfg.sweep_impl); env_int("PANOFLOW_PREP", cfg.record_path); env_int("PANOFLOW_STAGGER", cfg.stagger_levels);
+  env_int("PANOFLOW_SWEEP", cfg.sweep_impl); env_int("PANOFLOW_STAGGER", cfg.stagger_levels);
   env_int("PANOFLOW_PYR_CHAIN", cfg.pyramid_chaining); env_int("PANOFLOW_FINE_GRAD_BLOCKS", cfg.fine_gradient_blocks);
   env_int("PANOFLOW_SPARSE", cfg.sparse_sweep); env_int("PANOFLOW_WIDE", cfg.sweep_wide); env_int("PANOFLOW_WIDE_THRESHOLD", cfg.sweep_wide_threshold);
   env_int("PANOFLOW_BATCH_GRAD_FULL", cfg.full_width_batch_gradients);
   if (getenv("PANOFLOW_NO_WINDOW")) cfg.sweep_window = 0;
   if (const char* e = getenv("PANOFLOW_FUSE_UPS_PX")) cfg.fuse_small_level_px = atol(e);
-  if (cfg.sweep_impl != 1 && cfg.sweep_impl != 3) cfg.sweep_impl = 2;
-  if (cfg.record_path < 0 || cfg.record_path > 2) cfg.record_path = 0;
 #else
-  if (cfg.sweep_impl != 2 || cfg.record_path != 0 || cfg.sweep_wide == 1) {
-    fail(nullptr, PF_ERR_ARG, "sweep_impl / record_path / sweep_wide 1 select cross-check implementations that only the -DPF_EXPERIMENTS build (libpanoflow_exp.so) contains");
+  if (cfg.sweep_impl == 1 || cfg.sweep_wide == 1) {
+    fail(nullptr, PF_ERR_ARG, "sweep_impl / sweep_wide 1 select cross-check implementations that only the -DPF_EXPERIMENTS build (libpanoflow_exp.so) contains");
     return nullptr;
   }
 #endif
   if (cfg.batch_pairs == 0 || cfg.batch_pairs < -1 || cfg.batch_pairs > kMaxBatch) { fail(nullptr, PF_ERR_ARG, "pf_create_cfg: batch_pairs must be -1 or 1..%d", kMaxBatch); return nullptr; }
   if (cfg.fine_gradient_blocks < 1 || cfg.stagger_levels < -1 || cfg.fuse_small_level_px < -1 || cfg.sparse_sweep < -1 || cfg.sparse_sweep > 1 ||
-      cfg.sweep_wide < -1 || cfg.sweep_wide > 2 || cfg.sweep_wide_threshold < 0) {
+      cfg.sweep_impl < 1 || cfg.sweep_impl > 2 || cfg.sweep_wide < -1 || cfg.sweep_wide > 2 || cfg.sweep_wide_threshold < 0) {
     fail(nullptr, PF_ERR_ARG, "pf_create_cfg: knob out of range");
     return nullptr;
   }
@@ -258,12 +256,6 @@ int pf_set_solver_params(pf_ctx* c, const pf_solver_params* p) {
     return fail(c, PF_ERR_ARG, "smoothnessCoef / verticalRegularizationCoef / horizontalRegularizationCoef must be finite and >= 0");
   if (!coef_ok(q.gradient_step_size)) return fail(c, PF_ERR_ARG, "gradientStepSize must be finite and >= 0");
   if (q.downscale_factor != kDownscaleFactor) return fail(c, PF_ERR_ARG, "downscaleFactor %g: only 0.5 is supported (the 8-bit half-resolution path)", (double)q.downscale_factor);
-#ifdef PF_EXPERIMENTS
-  if (c->cfg.sweep_impl == 3 && p && memcmp(&q, &c->sp, sizeof q) != 0) {   // the relaxation experiment (kernels_relax.inl) is compiled for the presets
-    pf_solver_params d; pf_solver_params_init(&d);
-    if (memcmp(&q, &d, sizeof q) != 0) return fail(c, PF_ERR_ARG, "sweep_impl 3 (lab build) supports the preset parameters only");
-  }
-#endif
   c->sp = q;
   SolverCoef cf;
   cf.smooth = q.smoothness_coef; cf.vreg = q.vertical_regularization_coef; cf.hreg = q.horizontal_regularization_coef; cf.step = q.gradient_step_size;

@@ -2,23 +2,13 @@
 // diffusion): 0 for a lone pair, set by the throughput mode for its lanes; pf_config::fuse_small_level_px overrides both.
 int64_t fuse_small_px(const pf_ctx* c) { return c->cfg.fuse_small_level_px >= 0 ? c->cfg.fuse_small_level_px : c->fuse_ups_px; }
 
-// the product library ships ONE sweep (k_sweep_prep + k_sweep2); the lab build (-DPF_EXPERIMENTS, libpanoflow_exp.so) adds the
-// cross-check implementations the test-suite holds it against
-inline bool launch_sweep_any(hipStream_t st, const SweepArgs& a, float* rec, bool relax) {
-#ifdef PF_EXPERIMENTS
-  if (relax) return launch_sweep_relax(st, a);
-#endif
-  (void)relax;
-  return launch_sweep2(st, a, rec);
-}
-
 // One level of one direction (PixFlow.hpp:272-340, gradients excluded: they are precomputed for all levels).
 // flow_a holds the incoming flow and receives the level's result (flow_b, blurred, tmp are scratch).
 struct LevelBufs { float *flow_a, *flow_b, *blurred, *tmp, *rec; };
 // box = bounding box (min x, min y, max x, max y) of the gated pixels of this level, or nullptr for "everything"
 void run_level(pf_ctx* c, hipStream_t st, const float* g0, const float* g1, const float* a0, const float* a1, const uint8_t* gate, int w, int h, int sparse,
                const int* box, const LevelBufs& b, unsigned long long* bnd_fwd, unsigned long long* bnd_bwd, int* ctrl_fwd, int* ctrl_bwd, float** result,
-               int* pc_fwd = nullptr, int* pc_bwd = nullptr, const float* ups_src = nullptr, int ups_w = 0, int ups_h = 0, Batch bt = Batch()) {
+               const float* ups_src = nullptr, int ups_w = 0, int ups_h = 0, Batch bt = Batch()) {
   // ups_src: flow_a does not hold this level's incoming flow yet -- it is the upsample of the coarser level's result (ups_w x ups_h),
   // computed by the Gaussian's tile loader on the way (small levels: one launch instead of two)
   if (ups_src) { PROF(c, st, "gauss15_blurredFlow"); launch_gauss15_upsample(st, ups_src, ups_w, ups_h, 1.0f / c->sp.pyr_scale_factor, b.flow_a, b.blurred, w, h, c->g15, bt); }
@@ -38,24 +28,22 @@ void run_level(pf_ctx* c, hipStream_t st, const float* g0, const float* g1, cons
   // roofline needs per-launch HIP events inside its timed region, so ~0.2 ms of every timed step is the measurement itself.
   auto sweep = [&](SweepArgs& a) {
 #ifdef PF_EXPERIMENTS
+    // the product library ships ONE sweep (k_sweep_prep + k_sweep2); the lab build (-DPF_EXPERIMENTS, libpanoflow_exp.so) adds the
+    // independent v1 kernel the test-suite holds it against
     if (c->cfg.sweep_impl == 1) { PROF(c, st, "sweep"); launch_sweep(st, a); return; }
-    const bool relax = c->cfg.sweep_impl == 3;
-    a.prep_mode = c->cfg.record_path;
-#else
-    const bool relax = false;
 #endif
-    if (!c->prof) { launch_sweep_any(st, a, b.rec, relax); return; }
+    if (!c->prof) { launch_sweep2(st, a, b.rec); return; }
     ProfPending p;
     { std::lock_guard<std::mutex> lk(c->prof_mu); p.id = prof_id(c, "sweep"); p.a = prof_event(c); p.b = prof_event(c); }
     a.ev_start = p.a; a.ev_stop = p.b;
-    const bool launched = launch_sweep_any(st, a, b.rec, relax);
+    const bool launched = launch_sweep2(st, a, b.rec);
     a.ev_start = nullptr; a.ev_stop = nullptr;
     std::lock_guard<std::mutex> lk(c->prof_mu);
     if (launched) c->prof_pending.push_back(p); else { c->ev_pool.push_back(p.a); c->ev_pool.push_back(p.b); }
   };
-  { sa.flow = reinterpret_cast<float2*>(b.flow_a); sa.boundary = bnd_fwd; sa.ctrl = ctrl_fwd; sa.prepcnt = pc_fwd; sa.forward = 1; sweep(sa); }
+  { sa.flow = reinterpret_cast<float2*>(b.flow_a); sa.boundary = bnd_fwd; sa.ctrl = ctrl_fwd; sa.forward = 1; sweep(sa); }
   { PROF(c, st, "median5"); launch_median5(st, b.flow_a, b.flow_b, w, h, bt); }
-  { sa.flow = reinterpret_cast<float2*>(b.flow_b); sa.boundary = bnd_bwd; sa.ctrl = ctrl_bwd; sa.prepcnt = pc_bwd; sa.forward = 0; sweep(sa); }
+  { sa.flow = reinterpret_cast<float2*>(b.flow_b); sa.boundary = bnd_bwd; sa.ctrl = ctrl_bwd; sa.forward = 0; sweep(sa); }
   if ((long)w * h <= fuse_small_px(c)) {
     // throughput mode, small levels: the second median rides in the diffusion's tile loader (one launch fewer; result in b.tmp,
     // which nothing else uses: it must not be flow_a, the plane the next level's incoming flow is written to)
@@ -75,7 +63,6 @@ struct SolveBufs {
   uint8_t* gate; float* half_tmp;
   std::vector<size_t> bnd_off; size_t bnd_total;
   LevelBufs lb[2]; unsigned long long* bnd[2]; int* ctrl[2]; float* ratio[2];
-  int* prepcnt[2]; std::vector<size_t> pc_off; size_t pc_total;   // per sweep launch: one "records ready" counter per sweep workgroup
   int* gate_work = nullptr;     // batch slabs only: this pair's work area of k_gate_bbox_all (a lone solve uses the context's "gate_work")
   float* nv_flow[2] = {nullptr, nullptr};   // batch slabs only: internal flow planes for pairs whose caller does not want the flows
 };
@@ -106,9 +93,6 @@ int alloc_solve(Carver& cv, const Geometry& g, int ndirs, SolveBufs& b) {
   b.bnd_off.assign(g.n, 0);
   b.bnd_total = 0;
   for (int l = 0; l < g.n; ++l) { b.bnd_off[l] = b.bnd_total; b.bnd_total += sweep_boundary_elems(g.ws[l], g.hs[l]); }
-  b.pc_off.assign(g.n, 0);
-  b.pc_total = 0;
-  for (int l = 0; l < g.n; ++l) { b.pc_off[l] = b.pc_total; b.pc_total += 2 * size_t(sweep2_num_wgs_max(g.ws[l], g.hs[l])); }   // forward + backward sweep
   const char* nb[2][8] = {{"d0_flow_a", "d0_flow_b", "d0_blurred", "d0_tmp", "d0_bnd", "d0_ctrl", "d0_ratio", "d0_rec"},
                           {"d1_flow_a", "d1_flow_b", "d1_blurred", "d1_tmp", "d1_bnd", "d1_ctrl", "d1_ratio", "d1_rec"}};
   for (int d = 0; d < ndirs; ++d) {
@@ -117,8 +101,6 @@ int alloc_solve(Carver& cv, const Geometry& g, int ndirs, SolveBufs& b) {
     b.bnd[d] = (unsigned long long*)cv.get(nb[d][4], b.bnd_total * 2 * 8);
     b.ctrl[d] = (int*)cv.get(nb[d][5], size_t(g.n) * 2 * 2 * sizeof(int));
     b.ratio[d] = (float*)cv.get(nb[d][6], 256);
-    b.prepcnt[d] = (int*)cv.get(d == 0 ? "d0_prepcnt" : "d1_prepcnt", b.pc_total * sizeof(int));
-    if (!b.prepcnt[d]) return PF_ERR_NOMEM;
     b.lb[d].rec = (float*)cv.get(nb[d][7], sweep2_rec_bytes(g.w0, g.h0));
     if (!b.lb[d].rec) return PF_ERR_NOMEM;
     if (!b.lb[d].flow_a || !b.lb[d].flow_b || !b.lb[d].blurred || !b.lb[d].tmp || !b.bnd[d] || !b.ctrl[d] || !b.ratio[d]) return PF_ERR_NOMEM;
@@ -305,7 +287,6 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
     PROF(c, sm, "init_handoff");
     launch_fill_u64(sm, bnd[d], bnd_total * 2, kNotReady, bt);
     launch_fill_u32(sm, reinterpret_cast<unsigned*>(ctrl[d]), size_t(g.n) * 2 * 2, 0u, bt);
-    launch_fill_u32(sm, reinterpret_cast<unsigned*>(sb.prepcnt[d]), sb.pc_total, 0u, bt);
   }
   HIPCHK(c, hipEventRecord(c->ev_pre, sm));
   // Fine levels in two launches behind the coarse ones: levels [split2, split) (needed first, a quarter of the fine pixels), then the
@@ -381,7 +362,6 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
     run_level(c, st, grad[i0] + 2 * o, grad[i1] + 2 * o, pyrA[i0] + o, pyrA[i1] + o, gate + o, w, h, sparse, boxes.empty() ? nullptr : &boxes[4 * level], b,
               bnd[d] + bnd_off[level],
               bnd[d] + bnd_total + bnd_off[level], ctrl[d] + level * 4, ctrl[d] + level * 4 + 2, &res,
-              sb.prepcnt[d] + sb.pc_off[level], sb.prepcnt[d] + sb.pc_off[level] + sweep2_num_wgs_max(w, h),
               upsHere ? prev_res[d] : nullptr, upsHere ? g.ws[level + 1] : 0, upsHere ? g.hs[level + 1] : 0, bt);
     prev_res[d] = res;
     if (level > 0) {

@@ -84,10 +84,7 @@ int pf_stage_sweep(pf_ctx* c, const float* g0, const float* g1, const float* blu
   if (!dg0 || !dg1 || !dbl || !da0 || !da1 || !df || !gate || !bnd || !ctrl) return PF_ERR_NOMEM;
   launch_fill_u64(sm, bnd, nb, kNotReady);
   HIPCHK(c, hipMemsetAsync(ctrl, 0, 16, sm));
-  int* pcnt = (int*)ensure(c, "sg_pc", 2 * size_t(sweep2_num_wgs_max(w, h)) * sizeof(int));
-  if (!pcnt) return PF_ERR_NOMEM;
-  HIPCHK(c, hipMemsetAsync(pcnt, 0, 2 * size_t(sweep2_num_wgs_max(w, h)) * sizeof(int), sm));
-  SweepArgs sa; sa.cf = c->cf; sa.prepcnt = pcnt; sa.g0 = (const float2*)dg0; sa.g1 = (const float2*)dg1; sa.blurred = (const float2*)dbl; sa.gate = gate; sa.flow = (float2*)df;
+  SweepArgs sa; sa.cf = c->cf; sa.g0 = (const float2*)dg0; sa.g1 = (const float2*)dg1; sa.blurred = (const float2*)dbl; sa.gate = gate; sa.flow = (float2*)df;
   sa.boundary = bnd; sa.ctrl = ctrl; sa.W = w; sa.H = h; sa.forward = forward; sa.sparse = (w * h) % 2;   // stage test: exercise both variants
   sa.wide = c->cfg.sweep_wide > 0 ? c->cfg.sweep_wide : 0;   // the sweep form the context was created for (auto = latency form: one pair)
   if (sa.wide == 2) sa.sparse = 0;            // (the throughput form has no sparse variant)
@@ -99,10 +96,9 @@ int pf_stage_sweep(pf_ctx* c, const float* g0, const float* g1, const float* blu
   float* rec = (float*)ensure(c, "sg_rec", sweep2_rec_bytes(w, h));
   if (!rec) return PF_ERR_NOMEM;
 #ifdef PF_EXPERIMENTS
-  sa.prep_mode = c->cfg.record_path;
   if (c->cfg.sweep_impl == 1) { PROF(c, sm, "sweep"); launch_sweep(sm, sa); } else
 #endif
-  { PROF(c, sm, "sweep"); (void)launch_sweep_any(sm, sa, rec, c->cfg.sweep_impl == 3); }
+  { PROF(c, sm, "sweep"); (void)launch_sweep2(sm, sa, rec); }
   int hc[4] = {0, 0, 0, 0};
   HIPCHK(c, hipMemcpyAsync(hc, ctrl, 16, hipMemcpyDeviceToHost, sm));
   if (int e = stage_down(c, flow, df, n * 8)) return e;
@@ -171,11 +167,7 @@ int pf_stage_level(pf_ctx* c, const float* i0, const float* i1, const float* a0,
   float* res = nullptr;
   int box[4];
   if (int e = gate_level(c, sm, da0, da1, gate, w, h, box, nullptr)) return e;
-  const size_t npc = size_t(sweep2_num_wgs_max(w, h));
-  int* pcnt = (int*)ensure(c, "sg_pc", 2 * npc * sizeof(int));
-  if (!pcnt) return PF_ERR_NOMEM;
-  HIPCHK(c, hipMemsetAsync(pcnt, 0, 2 * npc * sizeof(int), sm));
-  run_level(c, sm, g0, g1, da0, da1, gate, w, h, (w + h) % 2, box, b, bnd, bnd + nb, ctrl, ctrl + 2, &res, pcnt, pcnt + npc);
+  run_level(c, sm, g0, g1, da0, da1, gate, w, h, (w + h) % 2, box, b, bnd, bnd + nb, ctrl, ctrl + 2, &res);
   int hc[4] = {0, 0, 0, 0};
   HIPCHK(c, hipMemcpyAsync(hc, ctrl, 16, hipMemcpyDeviceToHost, sm));
   if (int e = stage_down(c, flow_out, res, n * 8)) return e;

@@ -142,9 +142,7 @@ struct SweepArgs {
   // optional timing events (v2 sweep): attached to the launches themselves (hipExtLaunchKernel: start of the prepass / end of the
   // sweep kernel come from the dispatch packets' own timestamps), so that timing a sweep puts no marker packets on its stream
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  int* prepcnt = nullptr; // v2 sweep, prepass inside the launch: one counter per sweep workgroup (sweep2_num_wgs_max ints), ZEROED before the launch
   Batch bt;               // v2 sweep: bt.n same-size pairs in one launch (every pointer above is pair 0's; pair z's lies z * bt.stride bytes on)
-  int prep_mode = 0;      // lab build only (-DPF_EXPERIMENTS): 1 / 2 = the two rejected record paths (pf_config::record_path)
   int ax0 = 0, ay0 = 0, ax1 = 1 << 30, ay1 = 1 << 30;   // bounding box [ax0,ax1) x [ay0,ay1) of the gated pixels (default: everything); v2 sweep only
   int wide = 0;           // v2 sweep form: 0 = latency form (8 lanes per pixel, 4 bands of 8 rows per workgroup, one compute wave per SIMD), 1 = the same step
                           // with 8 bands per workgroup (two compute waves per SIMD), 2 = throughput form (2 lanes per pixel, bands of 32 rows,
@@ -158,13 +156,10 @@ size_t sweep_boundary_elems(int W, int H);   // hand-off granules needed per swe
 size_t sweep1_boundary_elems(int W, int H);                     // lab build only (-DPF_EXPERIMENTS)
 void launch_sweep(hipStream_t st, const SweepArgs& a);          // lab build only: v1, 64 rows per wave, the independent cross-check (pf_config::sweep_impl = 1)
 int sweep2_num_wgs(int H);
-int sweep2_num_wgs_max(int W, int H);          // workgroups a sweep launch on a W x H level can have (either band orientation)
 size_t sweep2_boundary_elems(int W, int H);   // granules one sweep launch may need (either band orientation)
 size_t sweep2_rec_bytes(int W, int H);
 int sweep_pk_probe(hipStream_t st, unsigned* d_scratch);   // 0 = the sweep's asm-block packed chains give the compiler forms' bits on this device; > 0 mismatching threads; < 0 HIP error
 bool launch_sweep2(hipStream_t st, const SweepArgs& a, float* rec);  // v2: prepass + 8 lanes/pixel + helper waves; false = empty window, nothing launched
-size_t sweep_relax_boundary_elems(int W, int H);
-bool launch_sweep_relax(hipStream_t st, const SweepArgs& a);   // lab build only (pf_config::sweep_impl = 3): event-driven relaxation on LDS-resident tiles, kernels_relax.inl
 // coarsest-level search
 void launch_adjust_initial_flow(hipStream_t st, const float* i0, const float* i1, const float* a0, const float* a1, int w, int h, int hint,
                                 int max_pct, float* i1eq_tmp, float* flow, Batch bt = Batch());

@@ -36,7 +36,7 @@ class Config(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("device", C.c_int), ("max_cols", C.c_int), ("max_rows", C.c_int), ("stagger_levels", C.c_int),
                 ("fuse_small_level_px", C.c_int64), ("fine_gradient_blocks", C.c_int), ("pyramid_chaining", C.c_int), ("sweep_window", C.c_int),
                 ("sparse_sweep", C.c_int), ("batch_pairs", C.c_int), ("sweep_wide", C.c_int), ("sweep_wide_threshold", C.c_int), ("sweep_throughput_transposed", C.c_int),
-                ("full_width_batch_gradients", C.c_int), ("sweep_impl", C.c_int), ("record_path", C.c_int)]
+                ("full_width_batch_gradients", C.c_int), ("sweep_impl", C.c_int)]
 
 
 class SolverParams(C.Structure):
@@ -233,8 +233,8 @@ class RigPlan:
 
 class Context:
     def __init__(self, device=0, max_cols=0, max_rows=0, exp=False, **knobs):
-        """knobs: fields of pf_config (stagger_levels, fuse_small_level_px, sweep_window, sparse_sweep, sweep_impl, record_path, ...);
-        exp=True loads the lab build, the only one that accepts sweep_impl / record_path other than the defaults."""
+        """knobs: fields of pf_config (stagger_levels, fuse_small_level_px, sweep_window, sparse_sweep, sweep_impl, ...);
+        exp=True loads the lab build, the only one that accepts sweep_impl 1 (the v1 cross-check kernel) and sweep_wide 1."""
         self.l = lib(exp)
         if knobs:
             cfg = Config()

@@ -2,7 +2,7 @@
 """Hardware-side floor of ONE step of the exact wavefront sweep (k_sweep2, compute_band): runs in the build container, no GPU.
 
   1. compiles csrc/kernels_sweep2.hip to gfx950 assembly with the product's flags (or takes --asm FILE),
-  2. cuts the three steady-state loops of compute_band<TOP = 0 / 1 / 2> out of k_sweep2<TR=0, FWD=1, SPARSE=0, MODE=0> (each is the
+  2. cuts the three steady-state loops of compute_band<TOP = 0 / 1 / 2> out of k_sweep2<TR=0, FWD=1, SPARSE=0> (each is the
      8-step unrolled chunk; a step starts at its first `row_newbcast:0` DPP move = the hand-over of the previous step's result),
   3. builds the register dependency graph of the not-taken (steady-state) path and prices it two ways:
        * recurrence  = the loop-carried dependency cycle alone: longest latency-weighted path through two copies of the chunk
@@ -27,7 +27,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(ROOT, "panorama-opticalflow_amd", "csrc", "kernels_sweep2.hip")
-KERNEL = os.environ.get("ISA_KERNEL") or "_ZN2pf8k_sweep2INS_12_GLOBAL__N_16SwGeomILi4ELi1EEELb0ELb1ELb0ELi0EEE"      # k_sweep2<SwLatency, TR = false, FWD = true, SPARSE = false, MODE = 0> (ISA_KERNEL=... overrides: ...SwGeomILi8ELi2EEE... is the wide form)
+KERNEL = os.environ.get("ISA_KERNEL") or "_ZN2pf8k_sweep2INS_12_GLOBAL__N_16SwGeomILi4ELi1EEELb0ELb1ELb0EEE"      # k_sweep2<SwLatency, TR = false, FWD = true, SPARSE = false> (ISA_KERNEL=... overrides: ...SwGeomILi8ELi2EEE... is the wide form)
 
 # Two pricings.  "lone" (the default, = hw_floor_us): what ONE wave alone on a SIMD gets on MI355X, measured with
 # tests/micro/lat_probe.hip (profiles/r03_lat_probe.txt): a wave is offered an issue slot only every ~5.5 cycles, whether or not the
@@ -300,7 +300,7 @@ def main():
     lone = analyse(body, loops, lat, issue, a.clock_ghz)
     guide = analyse(body, loops, LAT_GUIDE, ISSUE_GUIDE, a.clock_ghz)
     pick = lambda rs, key: max((e[key] for e, _, _ in rs if e["reads_top_neighbour_from_lds"]), default=max(e[key] for e, _, _ in rs))
-    result = {"kernel": "pf::k_sweep2<false, true, false, 0> (normal orientation, forward, dense, records from k_sweep_prep)", "clock_ghz": a.clock_ghz,
+    result = {"kernel": "pf::k_sweep2<false, true, false> (normal orientation, forward, dense, records from k_sweep_prep)", "clock_ghz": a.clock_ghz,
               "lone_wave": {"latencies_cycles": lat, "issue_cycles": issue, "lds_issue_extra_cycles": LDS_ISSUE_EXTRA, "source": "tests/micro/slot_model.py on MI355X (profiles/r06_slot_model.txt)", "loops": [e for e, _, _ in lone]},
               "guide_pipeline": {"latencies_cycles": LAT_GUIDE, "issue_cycles": ISSUE_GUIDE, "source": "MI355X_MICROARCH.md (2-cycle wave64 VALU, ~4-cycle dependent VALU, ~50-cycle ds_read; DPP / cmp / sqrt from tests/micro/issue_rate.hip)",
                                  "loops": [e for e, _, _ in guide]},
@@ -312,7 +312,7 @@ def main():
               "how_to_recompute": "python tests/micro/isa_chain.py [--lat name=cycles ...] [--issue name=cycles ...]   (compiles csrc/kernels_sweep2.hip with the product's flags; no GPU needed)"}
     json.dump(result, open(a.out + ".json", "w"), indent=1)
     with open(a.out + ".txt", "w") as f:
-        f.write("Steady-state step of the exact wavefront sweep -- k_sweep2<TR=0, FWD=1, SPARSE=0, MODE=0>, compute_band (CPU/PixFlow.hpp:315-324,\n"
+        f.write("Steady-state step of the exact wavefront sweep -- k_sweep2<TR=0, FWD=1, SPARSE=0>, compute_band (CPU/PixFlow.hpp:315-324,\n"
                 "342-386, 427-456: gate, proposeFlowUpdate from L and T, errorGradient, flow -= 0.5 * grad; six errorFunction evaluations in six lanes).\n"
                 "Generated by tests/micro/isa_chain.py from `hipcc -S` of csrc/kernels_sweep2.hip with the product's flags; recompute with\n"
                 "`python tests/micro/isa_chain.py [--lat name=cycles] [--issue name=cycles]`.\n\n"

@@ -38,7 +38,7 @@ def kernels(asm):
     return out
 
 
-FAMILIES = [("k_sweep_t", "k_sweep_t<true>"), ("k_median5_tiled", "k_median5_tiled"), ("8k_sweep2INS_12_GLOBAL__N_16SwGeomILi4ELi1EEELb0ELb1ELb0ELi0", "k_sweep2<pf::>"), ("k_gauss15_fused", "k_gauss15_fused"),
+FAMILIES = [("k_sweep_t", "k_sweep_t<true>"), ("k_median5_tiled", "k_median5_tiled"), ("8k_sweep2INS_12_GLOBAL__N_16SwGeomILi4ELi1EEELb0ELb1ELb0EE", "k_sweep2<pf::>"), ("k_gauss15_fused", "k_gauss15_fused"),
             ("k_sweep_prepILi32", "k_sweep_prep<32>"), ("k_sweep_prepILi8", "k_sweep_prep<8>"), ("k_upsample_cubic_tiled", "k_upsample_cubic_tiled"), ("k_final_flow", "k_final_flow"),
             ("k_gradients_all", "k_gradients_all"), ("k_pyr_down4", "k_pyr_down4"), ("7k_blendE", "k_blend_batch"), ("k_downscale_gray", "k_downscale_gray")]
 

@@ -1,6 +1,8 @@
 """GPU parity, stage by stage: every HIP kernel family vs the oracle's restatement of the same
 reference step on the same seeded inputs, through the C ABI.  Bar: bit-exact (np.array_equal treats
 +0 == -0) for everything except the blend's libm transcendentals."""
+import re
+
 import numpy as np
 import pytest
 
@@ -346,21 +348,10 @@ def test_level_fuzz_alpha_patterns(ctx, orc):
         assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), "case %d (%dx%d): %d mismatches" % (case, w, h, (got.view(np.uint32) != ref.view(np.uint32)).sum())
 
 
-@pytest.mark.parametrize("mode", ["1", "2", "relax", "fuse"])
-def test_sweep_record_experiment_paths_are_bit_identical(pf, orc, synth, mode):
-    """Rejected-on-measurement alternatives must stay exact.  They live in the lab build (libpanoflow_exp.so, -DPF_EXPERIMENTS), not
-    in the product library.  Mode relax = pf_config::sweep_impl 3, the event-driven relaxation sweep on LDS-resident tiles
-    (kernels_relax.inl: same fixed point reached in any evaluation order; slower than the wavefront because the longest dependency
-    chain, not the anti-diagonal count, still sets its time: profiles/r02_relaxation_sweep.txt).  record_path 1 (loader waves compute
-    the records) and 2 (prepass blocks inside the sweep launch, G16/R1 hand-off) are the two record-path experiments.  Mode fuse = the
-    throughput mode's launch fusion (upsample inside the next level's Gaussian, second median inside the diffusion kernel) forced on
-    for every level -- product code, product library."""
-    if mode == "relax":
-        c = pf.Context(0, exp=True, sweep_impl=3)
-    elif mode == "fuse":
-        c = pf.Context(0, fuse_small_level_px=100000000)
-    else:
-        c = pf.Context(0, exp=True, record_path=int(mode))
+def test_forced_launch_fusion_is_bit_identical(pf, orc, synth):
+    """The throughput mode's launch fusion (upsample inside the next level's Gaussian, second median inside the diffusion kernel) forced on
+    for every level -- product code, product library -- must stay exact."""
+    c = pf.Context(0, fuse_small_level_px=100000000)
     for (w, h, fwd) in [(150, 131, 1), (64, 257, 0), (300, 90, 1)]:
         r = np.random.default_rng(7 + w + fwd)
         img0 = r.random((h, w)).astype(np.float32); img1 = np.roll(img0, 2, axis=1) + 0.05 * r.random((h, w)).astype(np.float32)
@@ -383,7 +374,10 @@ def test_product_library_ships_one_sweep(pf):
     environment switch (none of the names is in the binary)."""
     with pytest.raises(pf.PanoflowError, match="PF_EXPERIMENTS"):
         pf.Context(0, sweep_impl=1)
-    with pytest.raises(pf.PanoflowError, match="PF_EXPERIMENTS"):
+    for exp in (False, True):   # the relaxation sweep (sweep_impl 3) no longer exists in any build
+        with pytest.raises(pf.PanoflowError):
+            pf.Context(0, exp=exp, sweep_impl=3)
+    with pytest.raises(TypeError, match="unknown pf_config field"):   # the two rejected record paths went with their knob
         pf.Context(0, record_path=2)
     with pytest.raises(pf.PanoflowError, match="PF_EXPERIMENTS"):
         pf.Context(0, sweep_wide=1)   # the rejected wide shape of round 4
@@ -391,8 +385,11 @@ def test_product_library_ships_one_sweep(pf):
         with pytest.raises(pf.PanoflowError):
             pf.Context(0, exp=True, sweep_wide=form)
     blob = open(pf.SO_PATH, "rb").read()
-    assert b"PANOFLOW_" not in blob and b"k_sweep_relax" not in blob
-    assert b"k_sweep_relax" in open(pf.SO_PATH_EXP, "rb").read()
+    lab = open(pf.SO_PATH_EXP, "rb").read()
+    assert b"PANOFLOW_" not in blob and b"k_sweep_relax" not in blob and b"k_sweep_relax" not in lab
+    # k_sweep2 instantiations (TR x FWD x SPARSE): the product ships the latency shape, the lab build the wide shape as well
+    inst = lambda b: set(re.findall(rb"_ZN2pf8k_sweep2I\w+", b))
+    assert len(inst(blob)) == 8 and len(inst(lab)) == 16
 
 
 def test_libraries_ship_one_kernel_per_front_end_stage(pf):

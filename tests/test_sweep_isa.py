@@ -71,12 +71,12 @@ def _kernels(asm, prefix):
 
 
 def _latency_forward_kernel(asm):
-    """mangled name of k_sweep2<SwGeom<4, 1>, TR = false, FWD = true, SPARSE = false, MODE = 0>, found by its demangled name"""
+    """mangled name of k_sweep2<SwGeom<4, 1>, TR = false, FWD = true, SPARSE = false>, found by its demangled name"""
     names = sorted(_kernels(asm, "k_sweep2"))
     dem = _demangle(names)
-    hits = [n for n in names if re.search(r"k_sweep2<.*SwGeom<4, 1>, false, true, false, 0>", dem[n])]
+    hits = [n for n in names if re.search(r"k_sweep2<.*SwGeom<4, 1>, false, true, false>", dem[n])]
     if not hits:   # no demangler: the mangled fragment
-        hits = [n for n in names if "SwGeomILi4ELi1EEELb0ELb1ELb0ELi0" in n]
+        hits = [n for n in names if "SwGeomILi4ELi1EEELb0ELb1ELb0EE" in n]
     assert len(hits) == 1, (hits, list(dem.values())[:4])
     return hits[0]
 
