@@ -4,8 +4,9 @@
 // the time of ONE step instead of bytes moved:
 //   * 8 lanes per pixel.  Everything about a pixel that does not depend on its neighbours -- E(C) and
 //     the gradient step its own incoming flow C would take, rC -- is computed by a fully parallel prepass
-//     (k_sweep_prep) which also packs the static per-pixel inputs into records (32 bytes in memory, 48 in LDS) laid out in the
-//     order the wavefront consumes them.  In the sequential kernel six lanes evaluate
+//     (k_sweep_prep) and written as records (12 bytes in memory: E(C), rC) laid out in the order the wavefront consumes them; the
+//     sweep's loader completes a record in LDS (48 bytes) with the static per-pixel inputs, g0 and blurred, which it reads from their
+//     planes, and with what follows from the slot alone (Ea, the pixel's coordinates).  In the sequential kernel six lanes evaluate
 //     E(L), E(L+dx), E(L+dy), E(T), E(T+dx), E(T+dy) for the two proposals (L = previous column,
 //     T = previous row) AT THE SAME TIME: one gather round per step instead of five dependent ones --
 //     and each proposal takes its own gradient step in its own lane (the same instructions for all lanes)
@@ -68,7 +69,7 @@ struct SwGeom {
   static constexpr int kBPW = BPW;               // adjacent bands that share one gather window and one loader wave
   static constexpr int kLoaders = NW / BPW;
   static constexpr int kRS = BPW == 1 ? 32 : 24; // record ring (steps)
-  static constexpr int kRQ = BPW == 1 ? 3 : 2;   // float4 quads per record in the LDS ring: two quads from memory + (x, y, window offset) formed by the loader, or -- wide form, where
+  static constexpr int kRQ = BPW == 1 ? 3 : 2;   // float4 quads per record in the LDS ring: (g0, blurred) from the planes, (E(C), rC) from the record stream + Ea, (x, y, window offset) formed by the loader, or -- wide form, where
                                                  // LDS is what limits the rings -- its first two quads, the (x, y) of the third in a ring of its own (40 bytes)
   static constexpr int kLoadAhead = BPW == 1 ? 3 : 1;   // chunks per band the loader fetches in one round when the ring has room
   static constexpr int kOS = 32;                 // result ring (steps)
@@ -107,6 +108,7 @@ constexpr int kPollSleep = 1;       // poller wave: s_sleep between two polls of
 #define PF_STR(x) PF_STR2(x)   // ~0.2 s of polling: a stuck band raises ctrl[1] instead of hanging the GPU
 
 struct F2x2 { float a, b, c, d; } __attribute__((aligned(8)));
+struct F3 { float x, y, z; };   // a record of the latency form's stream: (E(C), rC.x, rC.y)
 #ifdef PF_EXPERIMENTS
 // lab build only (PANOFLOW_POISON_LDS=1, tests/test_gpu_hygiene.py): every sweep workgroup fills its gather windows with NaN / inf / +-1e38 before the
 // loaders start -- a result that depends on a window slot its loader never wrote (or on what a pixel that is not updated reads there) then differs
@@ -885,9 +887,12 @@ __device__ __forceinline__ void d_make_record_at(int band, int s, int r, bool in
 }
 // ------------------------------------------------------------------------------------------------
 // prepass: records in wavefront order for the ACTIVE window of the sweep -- the product's latency form (SOA): per band and chunk of 8 steps
-// [64 first quads][64 second quads], record (s % 8) * 8 + r; the wide form (SwWide, AoS): rec[((band*nstepsPad + s)*8 + r)*3 + j] with the third quad (x, y, -, -):
+// 64 records of three floats, the first three of quad j=1, record (s % 8) * 8 + r; the wide form (SwWide, AoS): rec[((band*nstepsPad + s)*8 + r)*3 + j] with the third quad (x, y, -, -):
 // band counts from bandLo, step s handles sweep-order column uLo + s - r (columns [uLo, uHi)).
-//   j=0: (I0x, I0y, blurred.x, blurred.y)   j=1: (E(C), rC.x, rC.y, Ea)   j=2: (x, y, -, -)     (the step reads 16 + 16 + 8 bytes)
+// A record as the step reads it from the LDS ring (16 + 16 + 8 bytes):
+//   j=0: (I0x, I0y, blurred.x, blurred.y)   j=1: (E(C), rC.x, rC.y, Ea)   j=2: (x, y, -, -)
+//   j=0 is g0 and blurred at the record's own pixel for a pixel that is updated and zero otherwise: two planes no sweep changes.  Only the
+//   AoS stream carries it; the latency form's loader reads the two planes itself (k_sweep2), and forms Ea from E(C) and the slot's column.
 //   rC = C after its own gradient step, C - 0.5 * ((E(C+dx), E(C+dy)) - E(C)) / eps (IEEE operations: what the sweep's exact fast
 //   forms reproduce bit for bit for the two proposals) -- the result of the pixel if neither proposal beats E(C);
 //   (x, y) = the pixel's image coordinates as floats; Ea = E(C), or kKeepEnergy at the first pixel of a row in sweep order
@@ -897,10 +902,12 @@ __device__ __forceinline__ void d_make_record_at(int band, int s, int r, bool in
 // When the window does not start at the first band, the row above it never changes during this sweep: its flow
 // is written as the granule row the first workgroup's poller reads (top0).
 // ------------------------------------------------------------------------------------------------
-// SOA (the product's latency form, round 5): the record stream holds TWO quads per record -- the third, (x, y, window offset), is a function of
-// the slot and of E(C)'s sign and is formed by the sweep's loader -- laid out per chunk of 8 steps x 8 rows as [64 first quads][64 second
-// quads]: a wave of this kernel IS one chunk, so its two stores are 1 KB runs without the LDS stage, and a loader lane reads its own record's
-// two quads with two coalesced loads.  32 instead of 48 bytes per record written here and read there (the prepass is bandwidth-bound at the large levels).
+// SOA (the product's latency form): the record stream holds THREE floats per record, (E(C), rC.x, rC.y) -- all this kernel computes.  Quad j=0 is
+// a copy of g0 and blurred at the record's pixel, Ea is E(C) or kKeepEnergy by the slot's column, and the third quad, (x, y, window offset), a
+// function of the slot and of E(C)'s sign: the sweep's loader forms all three.  Laid out per chunk of 8 steps x 8 rows as 64 records: a wave of
+// this kernel IS one chunk, so its store is one 768-byte run without the LDS stage, and a loader lane reads its own record with one coalesced
+// three-dword load.  12 instead of 48 bytes per record written here and read there (the prepass is bandwidth-bound at the large levels); it
+// still READS g0 and blurred, for the energies.  (profiles/prepass_diet_ab.txt)
 template <int ROWS, bool RC, bool SOA = false>
 __global__ __launch_bounds__(256) void k_sweep_prep(const float2* __restrict__ g0, const float2* __restrict__ g1, const float2* __restrict__ blurred,
                                                     const uint8_t* __restrict__ gate, const float2* __restrict__ flow, int W, int H, int forward,
@@ -935,10 +942,11 @@ __global__ __launch_bounds__(256) void k_sweep_prep(const float2* __restrict__ g
   d_make_record_at<ROWS, RC>(band, s, r, band < nbandsPad && s < nstepsPad, g0, g1, blurred, gate, flow, W, H, forward, transposed, rW, cf, uLo, uHi, bandLo, a, b, c);
   if (SOA) {
     static_assert(!SOA || (ROWS == 8 && RC), "chunk layout of the latency form");
-    // float4 index in the band's stream: chunk * 128 + quad * 64 + (record in chunk); lt = 64 * (chunk in block) + (record in chunk)
-    const size_t bandBase2 = size_t(band) * nstepsPad * ROWS * 2;
-    const unsigned o = (unsigned(blockIdx.x) * 4u + (lt >> 6)) * 128u + (lt & 63u);
-    if (s < nstepsPad) { rec[bandBase2 + o] = a; rec[bandBase2 + o + 64u] = b; }   // (nstepsPad is a whole number of chunks; s is wave-uniform up to the chunk)
+    // record index in the band's stream: chunk * 64 + (record in chunk); lt = 64 * (chunk in block) + (record in chunk).  Quad j=0 is not stored
+    // (the sweep's loader reads it from g0 / blurred itself), so nothing here keeps `a` alive; nor is Ea (b.w), which the loader forms from E(C).
+    const size_t bandBase2 = size_t(band) * nstepsPad * ROWS;
+    const unsigned o = (unsigned(blockIdx.x) * 4u + (lt >> 6)) * 64u + (lt & 63u);
+    if (s < nstepsPad) reinterpret_cast<F3*>(rec)[bandBase2 + o] = F3{b.x, b.y, b.z};   // (nstepsPad is a whole number of chunks; s is wave-uniform up to the chunk)
     return;
   }
   __shared__ float4 stage[256 * kQuads];
@@ -1099,10 +1107,10 @@ template <class G, bool TR, bool FWD, bool SPARSE>
 __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict__ rec, const float2* __restrict__ g1, float2* __restrict__ flow,
                                                 unsigned long long* __restrict__ boundary, int* __restrict__ ctrl, int W, int H,
                                                 int nstepsPad, int nbands, float rW, float rEps, int uLo, int LSv, int bandLo, long long budgetTicks,
-                                                const float2* __restrict__ blurred, size_t bstride, SolverCoef cf) {
+                                                const float2* __restrict__ blurred, const float2* __restrict__ g0, size_t bstride, SolverCoef cf) {
   {   // blockIdx.z = pair of a batched launch: an independent sweep with its own ticket, granules and records
     const size_t bo = size_t(blockIdx.z) * bstride;
-    PF_BOFF(rec, bo); PF_BOFF(g1, bo); PF_BOFF(flow, bo); PF_BOFF(boundary, bo); PF_BOFF(ctrl, bo); PF_BOFF(blurred, bo);
+    PF_BOFF(rec, bo); PF_BOFF(g1, bo); PF_BOFF(flow, bo); PF_BOFF(boundary, bo); PF_BOFF(ctrl, bo); PF_BOFF(blurred, bo); PF_BOFF(g0, bo);
   }
   constexpr int kWaves = G::kWaves, kRS = G::kRS, kOS = G::kOS, kLoadAhead = G::kLoadAhead, kLoaders = G::kLoaders;
   using Smem = SmemT<G>;
@@ -1254,8 +1262,9 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
       const int sx = TR ? ov : ou, sy = TR ? ou : ov;   // back to image axes
       ox = FWD ? sx : -sx; oy = FWD ? sy : -sy;
     };
-    // the product's record stream: 32-byte records, [64 first quads][64 second quads] per chunk (k_sweep_prep<.., SOA>)
-    const float4* recw = rec + size_t(band0 + w) * nstepsPad * (kRows * 2);
+    // the product's record stream: three floats per record, (E(C), rC), 64 records per chunk (k_sweep_prep<.., SOA>); the record's first quad -- g0
+    // and blurred at its pixel -- is read here from the planes themselves, and Ea is E(C) or kKeepEnergy by the slot's column
+    const F3* recw = reinterpret_cast<const F3*>(rec) + size_t(band0 + w) * nstepsPad * kRows;
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     // this lane's slot inside a chunk is (step offset lane >> 3, row lane & 7)
     const int lj = lane >> 3, lr = lane & 7;
@@ -1296,7 +1305,7 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
       }
       first = false;
       float4 va[kLoadAhead], vb4[kLoadAhead], vc[kLoadAhead];
-      bool ld[kLoadAhead];
+      bool ld[kLoadAhead], eaKeep[kLoadAhead] = {};
       float cox[kLoadAhead], coy[kLoadAhead]; bool cdupc[kLoadAhead], cdupr[kLoadAhead], cwhole[kLoadAhead];
       // window work of a chunk: the block of new columns (3 texels per lane), a ninth column (lanes 0-23), one new row (one texel per lane)
       float2 wv[kLoadAhead][5]; int wu[kLoadAhead][5], wvv[kLoadAhead][5]; bool wok[kLoadAhead][5];
@@ -1309,14 +1318,22 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
         for (int k = 0; k < 5; ++k) { wv[c][k] = make_float2(0.f, 0.f); wu[c][k] = 0; wvv[c][k] = 0; wok[c][k] = false; }
         if (ld[c]) {
           {   // ---- the chunk's records ----
-            const float4* src = recw + size_t(r0) * (kRows * 2);   // chunk r0 / 8: 128 quads
-            va[c] = src[lane]; vb4[c] = src[lane + 64];            // this lane's own record (step r0 + lane / 8, row lane % 8)
+            const F3 t3 = recw[size_t(r0) * kRows + lane];   // chunk r0 / 8: 64 records; this lane's own (step r0 + lane / 8, row lane % 8)
+            vb4[c] = make_float4(t3.x, t3.y, t3.z, 0.f);
             // its third quad: the pixel's coordinates (0, 0 for a slot without a pixel, as the prepass wrote them until round 5)
             const int sstep = r0 + lj, ia = uLo + sstep - lr;
+            eaKeep[c] = !(ia > 0);   // the first pixel of a row in sweep order: no previous pixel along the step axis, Ea = kKeepEnergy
             const bool inside = sstep - lr >= 0 && ia < uLo + LSv && ia < LS && lib < LB;
             const int cxs = TR ? lib : ia, cys = TR ? ia : lib;   // position in sweep order
             const int px = FWD ? cxs : W - 1 - cxs, py = FWD ? cys : H - 1 - cys;
             vc[c] = make_float4(inside ? float(px) : 0.f, inside ? float(py) : 0.f, 0.f, 0.f);
+            // its first quad: the two static planes at the pixel, issued beside the record load (whether the pixel is updated is only known once
+            // that load is back: the select is made at the LDS store); a slot without a pixel reads nothing
+            if (inside) {
+              const int pi = py * W + px;
+              const float2 sg = g0[pi], sb = blurred[pi];
+              va[c] = make_float4(sg.x, sg.y, sb.x, sb.y);
+            }
           }
           // ---- the chunk's window: offset (at most one texel from the previous chunk's), new columns, new row ----
           const int j = r0 / kChunk;
@@ -1380,7 +1397,12 @@ __global__ __launch_bounds__(G::kThreads) void k_sweep2(const float4* __restrict
           const bool on = vb4[c].x != kKeepEnergy;
           float4 q2 = vc[c];
           q2.z = on ? cox[c] : __builtin_nanf(""); q2.w = on ? coy[c] : __builtin_nanf("");
-          dst[3 * lane] = va[c]; dst[3 * lane + 1] = vb4[c]; dst[3 * lane + 2] = q2;
+          // (a pixel that is not updated carries zeros in its first quad, as the prepass used to write them: whatever g0 and blurred hold there never reaches the ring)
+          // (selected component by component: `on ? va[c] : z4` is a select between two ADDRESSES, which keeps the arrays of this loop out of registers)
+          const float4 q0 = make_float4(on ? va[c].x : 0.f, on ? va[c].y : 0.f, on ? va[c].z : 0.f, on ? va[c].w : 0.f);
+          // Ea = E(C) as the proposal from the previous pixel along the step axis sees it (a pixel that is not updated: E(C) = kKeepEnergy either way)
+          const float4 q1 = make_float4(vb4[c].x, vb4[c].y, vb4[c].z, eaKeep[c] ? kKeepEnergy : vb4[c].x);
+          dst[3 * lane] = q0; dst[3 * lane + 1] = q1; dst[3 * lane + 2] = q2;
 #pragma unroll
           for (int k = 0; k < 3; ++k) if (cwhole[c] || wok[c][k]) win_store_block(wu[c][k], wvv[c][k], wv[c][k], cdupc[c], cdupr[c]);
           if (__any(wok[c][3])) { if (wok[c][3]) win_store(wu[c][3], wvv[c][3], wv[c][3]); }
@@ -1640,7 +1662,7 @@ static bool launch_sweep2_form(hipStream_t st, const SweepArgs& a, float* rec) {
   const int tr = win.tr, uLo = win.uLo, uHi = win.uHi, LSv = win.LSv, bandLo = win.bandLo, nbands = win.nbands;
   const int nwg = win.nwg, nbandsPad = nwg * kWaves, nstepsPad = win.nstepsPad;
   const float rW = (float)(1.0 / (double)(float)a.W), rEps = (float)(1.0 / (double)kGradEpsilon);
-  // the records reach the sweep through k_sweep_prep, launched in front of it: the latency form's 32-byte SOA stream, the wide form's AoS three-quad stream
+  // the records reach the sweep through k_sweep_prep, launched in front of it: the latency form's 12-byte SOA stream, the wide form's AoS three-quad stream
   if (G::kBPW == 1)
     hipExtLaunchKernelGGL((k_sweep_prep<kRows, true, true>), dim3((unsigned)((nstepsPad + 256 / kRows - 1) / (256 / kRows)), (unsigned)nbandsPad, a.bt.n), dim3(256), 0, st, a.ev_start, nullptr, 0, a.g0, a.g1, a.blurred, a.gate, a.flow,
                           a.W, a.H, a.forward, tr, nstepsPad, nbandsPad, rW, reinterpret_cast<float4*>(rec), uLo, uHi, bandLo,
@@ -1654,7 +1676,7 @@ static bool launch_sweep2_form(hipStream_t st, const SweepArgs& a, float* rec) {
   const unsigned nthreads = G::kThreads;
   const dim3 grid(nwg, 1, a.bt.n), block(nthreads);
   const float4* r4 = reinterpret_cast<const float4*>(rec);
-#define PF_LAUNCH_SWEEP2_(TRV, FWV, SPV) hipExtLaunchKernelGGL((k_sweep2<G, TRV, FWV, SPV>), grid, block, 0, st, nullptr, a.ev_stop, 0, r4, a.g1, a.flow, a.boundary, a.ctrl, a.W, a.H, nstepsPad, nbands, rW, rEps, uLo, LSv, bandLo, budget, a.blurred, a.bt.stride, a.cf)
+#define PF_LAUNCH_SWEEP2_(TRV, FWV, SPV) hipExtLaunchKernelGGL((k_sweep2<G, TRV, FWV, SPV>), grid, block, 0, st, nullptr, a.ev_stop, 0, r4, a.g1, a.flow, a.boundary, a.ctrl, a.W, a.H, nstepsPad, nbands, rW, rEps, uLo, LSv, bandLo, budget, a.blurred, a.g0, a.bt.stride, a.cf)
 #define PF_LAUNCH_SWEEP2(TRV, FWV) do { if (a.sparse) PF_LAUNCH_SWEEP2_(TRV, FWV, true); else PF_LAUNCH_SWEEP2_(TRV, FWV, false); } while (0)
   if (tr) { if (a.forward) PF_LAUNCH_SWEEP2(true, true); else PF_LAUNCH_SWEEP2(true, false); }
   else { if (a.forward) PF_LAUNCH_SWEEP2(false, true); else PF_LAUNCH_SWEEP2(false, false); }
