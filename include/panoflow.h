@@ -457,6 +457,32 @@ int pf_vis_panel_dev(pf_ctx* ctx, const float* d_flow, const uint8_t* d_image, i
  * has reused those buffers (any solve: pf_flow*, pf_novel_view*, the throughput mode, a failed step). */
 int pf_stitch_visualize(pf_ctx* ctx, uint8_t* l2r_panel, uint8_t* r2l_panel, size_t step);
 
+/* ---- PNG files made on the device -------------------------------------------------------------
+ * An 8-bit RGBA PNG (colour type 6, no interlace) of a packed BGRA image, of any size pf_blend accepts and any width (the
+ * 3 * cols panels of pf_vis_panel_dev included).  Scanline filtering (per row the filter type with the smallest sum of absolute
+ * residuals), deflate and compaction run in kernels on the device; only the finished stream crosses the link, into its place in
+ * png_out (HOST memory), where the library frames it (its own CRC-32 and Adler-32: no zlib).  Opt-in: no other entry point's
+ * behaviour depends on these.  The deflate stream: the filtered scanlines in segments of pf_png_segment_bytes()
+ * bytes, each compressed on its own into dynamic-Huffman blocks with run matches (the byte 1 or 4 back, lengths up to 258) or, where
+ * that would not shrink it, a stored block; each segment ends on a byte boundary with an empty stored block.  The bytes are a
+ * function of the image alone.
+ *   cap       bytes png_out holds.  A file larger than cap is PF_ERR_ARG: nothing is written and *size_out receives the size
+ *             needed (the batch form: cap_each per file, every sizes_out[k] set).  pf_png_bound(cols, rows) always suffices.
+ *   _dev      d_bgra: device pointers of this context's device, packed rows, 4-byte aligned.
+ *   batch     n same-size images -> the bytes of n single calls, their kernels enqueued together.
+ * pf_stitch_result_png encodes the composite the last pf_stitch_step / pf_stitch_step_planned left in HBM (the one a step with
+ * r_bgra == NULL chains on), pf_stitch_batch_result_png frame slot `frame` of the last host-form pf_stitch_step_batch* call; both
+ * return PF_ERR_ARG where there is none, and neither changes the chain, the prefetch records, the frame slots or what
+ * pf_stitch_visualize reads.  A step may therefore pass out_bgra == NULL and bring down only the file. */
+size_t pf_png_bound(int cols, int rows);
+size_t pf_png_segment_bytes(void);
+int pf_png_encode_dev(pf_ctx* ctx, const uint8_t* d_bgra, int cols, int rows, uint8_t* png_out, size_t cap, size_t* size_out);
+int pf_png_encode(pf_ctx* ctx, const uint8_t* bgra, size_t step_bytes, int cols, int rows, uint8_t* png_out, size_t cap, size_t* size_out);
+int pf_png_encode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_bgra, int cols, int rows, uint8_t* const* png_out, size_t cap_each,
+                            size_t* sizes_out);
+int pf_stitch_result_png(pf_ctx* ctx, uint8_t* png_out, size_t cap, size_t* size_out);
+int pf_stitch_batch_result_png(pf_ctx* ctx, int frame, uint8_t* png_out, size_t cap, size_t* size_out);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

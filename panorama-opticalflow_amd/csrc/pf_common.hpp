@@ -235,4 +235,18 @@ void launch_vis_field(hipStream_t st, const uint8_t* img, int cols, int rows, co
 void launch_vis_panel(hipStream_t st, const float* flow, const uint8_t* img, int cols, int rows, const VisParams* par, const void* arrows,
                       uint8_t* out /* 3 cols x rows BGRA */);
 
+// ---- PNG encoder (kernels_png.hip): filter, deflate of independent segments, compaction; the host frames (png_frame.hpp) ----
+struct PngWork {
+  uint8_t* stream;            // filtered scanlines, png_stream_alloc_bytes()
+  uint8_t* slots;             // png_frame::kSegSlot bytes per segment
+  unsigned* sizes;            // per segment: bytes of its deflate blocks
+  unsigned* adler;            // per segment: Adler-32 of its bytes (from 1), combined on the host
+  unsigned long long* offs;   // segments + 1: exclusive prefix sum of sizes; the last entry is the deflate stream's length
+  uint8_t* packed;            // the deflate stream, png_frame::deflate_bound() bytes
+};
+size_t png_stream_alloc_bytes(int cols, int rows);
+void launch_png_filter(hipStream_t st, const uint8_t* bgra /* packed, 4-byte aligned */, int cols, int rows, const PngWork& w);   // bgra -> stream
+void launch_png_deflate(hipStream_t st, int cols, int rows, const PngWork& w);   // stream -> slots, sizes, adler
+void launch_png_pack(hipStream_t st, int cols, int rows, const PngWork& w);      // sizes -> offs; slots -> packed
+
 }  // namespace pf

@@ -21,6 +21,14 @@ class PanoflowError(RuntimeError):
     pass
 
 
+class PngCapacityError(PanoflowError):
+    """a PNG call's buffer was too small; .needed = the file's size"""
+
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     cmd = ["make", "-C", _HERE, "-j8"] + (["-B"] if force else [])
@@ -88,6 +96,10 @@ def lib(exp=False):
         _lib.pf_last_swept_steps.argtypes = [C.c_void_p]
         _lib.pf_rig_plan_step.restype = C.c_void_p
         _lib.pf_rig_plan_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        _lib.pf_png_bound.restype = C.c_size_t
+        _lib.pf_png_bound.argtypes = [C.c_int, C.c_int]
+        _lib.pf_png_segment_bytes.restype = C.c_size_t
+        _lib.pf_png_segment_bytes.argtypes = []
     return _lib
 
 
@@ -107,6 +119,7 @@ EXPORTS = [
     "pf_stage_blend_smooth", "pf_stage_tile_blur", "pf_stage_box_blur", "pf_stage_gauss15_form", "pf_stage_level_table",
     "pf_stage_preprocess_batch", "pf_stage_pyramid", "pf_stage_adjust_initial_flow_batch", "pf_stage_intensity_ratio",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
+    "pf_png_bound", "pf_png_segment_bytes", "pf_png_encode_dev", "pf_png_encode", "pf_png_encode_batch_dev", "pf_stitch_result_png", "pf_stitch_batch_result_png",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -132,6 +145,16 @@ def max_percentage_by_name(name):
     if v < 0:
         raise PanoflowError(lib().pf_last_error(None).decode())
     return v
+
+
+def png_bound(cols, rows):
+    """capacity that holds the PNG of any cols x rows image (pf_png_bound)"""
+    return int(lib().pf_png_bound(cols, rows))
+
+
+def png_segment_bytes():
+    """bytes of filtered scanlines one deflate segment covers (pf_png_segment_bytes)"""
+    return int(lib().pf_png_segment_bytes())
 
 
 def algorithmic_bytes(cols, rows):
@@ -496,6 +519,48 @@ class Context:
         a = np.empty((rows, 3 * cols, 4), np.uint8); b = np.empty_like(a)
         self._chk(self.l.pf_stitch_visualize(self.h, _p(a), _p(b), C.c_size_t(cols * 12)))
         return a, b
+
+    # ---- PNG files made on the device (pf_png_*): every method returns the file as bytes ----
+    def _png_call(self, cols, rows, call, cap=None):
+        """call(buffer, cap, size_ref) -> rc.  cap=None: pf_png_bound.  A short buffer raises PngCapacityError carrying the needed size."""
+        cap = int(self.l.pf_png_bound(cols, rows)) if cap is None else int(cap)
+        buf = np.empty(max(cap, 1), np.uint8); size = C.c_size_t(0)
+        rc = call(_p(buf), C.c_size_t(cap), C.byref(size))
+        if rc != 0 and 0 < cap < size.value:
+            raise PngCapacityError("panoflow error %d: %s" % (rc, self.l.pf_last_error(self.h).decode()), size.value)
+        self._chk(rc)
+        return buf[:size.value].tobytes()
+
+    def png_encode(self, image, cap=None):
+        """host BGRA (rows, cols, 4) array, any row stride -> PNG file bytes"""
+        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+        if a.strides[2] != 1 or a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_png_encode(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, b, c, s), cap)
+
+    def png_encode_dev(self, d_bgra, cols, rows, cap=None):
+        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_png_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, b, c, s), cap)
+
+    def png_encode_batch_dev(self, d_bgra, cols, rows):
+        """n same-size device images -> list of n files"""
+        n = len(d_bgra)
+        cap = int(self.l.pf_png_bound(cols, rows))
+        bufs = [np.empty(cap, np.uint8) for _ in range(n)]
+        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_bgra]); outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        sizes = (C.c_size_t * n)()
+        self._chk(self.l.pf_png_encode_batch_dev(self.h, n, srcs, cols, rows, outs, C.c_size_t(cap), sizes))
+        return [bufs[k][:sizes[k]].tobytes() for k in range(n)]
+
+    def stitch_result_png(self, shape=None, cap=None):
+        """the PNG of the composite the last stitch_step left in HBM; shape = (rows, cols) of that step (default: the last stitch_step made
+        through this object), used only to size the buffer"""
+        rows, cols = shape if shape is not None else getattr(self, "_step_shape", (1, 1))
+        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_result_png(self.h, b, c, s), cap)
+
+    def stitch_batch_result_png(self, frame, shape, cap=None):
+        """the PNG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
+        rows, cols = shape
+        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
 
     # ---- device-resident entry points (raw device pointers as ints) ----
     def dev_alloc(self, nbytes):

@@ -3,6 +3,7 @@
 //   * TIFF reader: baseline little/big-endian, 8-bit RGB or RGBA, chunky, strips, compression none / LZW /
 //     Deflate / PackBits, predictor 1 or 2.  Tiles, 16-bit, palette and planar files are rejected with a message.
 //   * PNG reader/writer: 8-bit RGB/RGBA, non-interlaced (zlib).
+//   * write_png_device: the same pixels as a PNG the library makes on the GPU (pf_png_*); only the finished file comes to the host.
 // Pixels are delivered as BGRA (CV_8UC4) like cv::imread(-1) followed by the reference's BGR->BGRA (main.cpp:58,68).
 #ifndef PANO_IMAGE_IO_HPP_
 #define PANO_IMAGE_IO_HPP_
@@ -11,6 +12,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -173,6 +175,33 @@ static inline void write_png(const std::string& path, const Mat& bgra) {
   unsigned char ih[13]; be32(ih, (unsigned)w); be32(ih + 4, (unsigned)h); ih[8] = 8; ih[9] = 6; ih[10] = 0; ih[11] = 0; ih[12] = 0;
   png_chunk(f, "IHDR", ih, 13); png_chunk(f, "IDAT", z.data(), zn); png_chunk(f, "IEND", nullptr, 0);
   fclose(f);
+}
+// PNG made on the device: filtering, deflate and framing are the library's (include/panoflow.h, "PNG files made on the device"); this
+// only provides the buffer and writes the file.  `encode(buf, cap, &size)` is one of the pf_*_png calls bound to its source image.
+// The pixels decode to the same image as write_png's file; the bytes of the file differ (other filters, other deflate blocks).
+template <class Encode>
+static inline void write_png_bytes(const std::string& path, pf_ctx* ctx, int cols, int rows, Encode encode) {
+  const size_t cap = pf_png_bound(cols, rows);
+  std::unique_ptr<unsigned char[]> buf(new unsigned char[cap]);   // not value-initialised: pages the file does not reach are never touched
+  size_t size = 0;
+  if (encode(buf.get(), cap, &size) != 0) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) throw VrCamException("failed to write image: " + path);
+  const bool ok = fwrite(buf.get(), 1, size, f) == size;
+  if (fclose(f) != 0 || !ok) throw VrCamException("failed to write image: " + path);
+}
+// a host image (any row step): uploaded, encoded on the device
+static inline void write_png_device(const std::string& path, pf_ctx* ctx, const Mat& bgra) {
+  if (bgra.type() != panocv::CV_8UC4) throw VrCamException("write_png_device expects CV_8UC4");
+  write_png_bytes(path, ctx, bgra.cols, bgra.rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_png_encode(ctx, bgra.data, bgra.step, bgra.cols, bgra.rows, b, cap, n); });
+}
+// the composite the last pf_stitch_step left in HBM (cols x rows: that step's size); no raw image crosses the link
+static inline void write_png_device(const std::string& path, pf_ctx* ctx, int cols, int rows) {
+  write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_stitch_result_png(ctx, b, cap, n); });
+}
+// frame slot `frame` of the last host-form pf_stitch_step_batch* call
+static inline void write_png_device(const std::string& path, pf_ctx* ctx, int frame, int cols, int rows) {
+  write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_stitch_batch_result_png(ctx, frame, b, cap, n); });
 }
 static inline Mat read_png(const std::string& path) {
   const std::vector<unsigned char> b = read_file(path);

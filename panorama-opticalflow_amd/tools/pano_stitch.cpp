@@ -20,6 +20,11 @@
 //   composites at once, so the run holds steps + 1 images per directory until the call returns and steps composites until they are
 //   written: 4 (2 steps + 1) B/px per directory (25 GB for 16 directories of 9000x4000 x 5 steps), where -static_rig 1 alone holds one
 //   step's images at a time.
+//   -png_device 1 (any mode; off by default): every PNG is filtered, deflated and framed on the GPU (pf_png_*) and decodes to the same
+//   pixels as the default writer's file.  The lone fused chain and -test_dirs without -rig_chain encode the composites where they lie in
+//   HBM (pf_stitch_result_png / pf_stitch_batch_result_png) and bring no raw composite down (-static_rig 1: only the first directory's,
+//   which the next plan is made from); -rig_chain 1, -inputs 4, -fused 0 and the -visualize panels hold their images on the host and
+//   send them up to be encoded (pf_png_encode).
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -37,6 +42,13 @@ using namespace panocv;
 using namespace util;
 using namespace optical_flow;
 using namespace stitch_tools;
+
+static bool g_png_device = false;   // -png_device 1
+// a host image to a PNG file, by the default writer or through the device encoder
+static void writeImage(const std::string& path, const Mat& image) {
+  if (g_png_device) pano_io::write_png_device(path, pano::context(), image);
+  else pano_io::imwriteExceptionOnFail(path, image);
+}
 
 static std::map<std::string, std::string> parseFlags(int argc, char** argv) {   // gflags syntax: -name value | --name=value
   std::map<std::string, std::string> f;
@@ -75,16 +87,16 @@ static void buildvisualizations(const Mat flowLtoR, const Mat flowRtoL, const Ma
   Mat flowVisRtoLColorWithLines = visualizeFlowAsVectorField(flowRtoL, ImageR);
   Mat horizontalVisLtoR = stackHorizontal(std::vector<Mat>({toBGRA(flowVisLtoR), toBGRA(flowVisLtoRColorWheel), flowVisLtoRColorWithLines}));
   Mat horizontalVisRtoL = stackHorizontal(std::vector<Mat>({toBGRA(flowVisRtoL), toBGRA(flowVisRtoLColorWheel), flowVisRtoLColorWithLines}));
-  pano_io::imwriteExceptionOnFail(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisLtoR);
-  pano_io::imwriteExceptionOnFail(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisRtoL);
+  writeImage(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisLtoR);
+  writeImage(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", horizontalVisRtoL);
 }
 
 // the same panels of a fused step, from the flows and inputs pf_stitch_step left in HBM
 static void stitchVisualizations(int cols, int rows, const std::string& dir, const std::string& alg, int step) {
   Mat l2r(rows, 3 * cols, CV_8UC4), r2l(rows, 3 * cols, CV_8UC4);
   pano::check(pf_stitch_visualize(pano::context(), l2r.data, r2l.data, l2r.step));
-  pano_io::imwriteExceptionOnFail(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", l2r);
-  pano_io::imwriteExceptionOnFail(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", r2l);
+  writeImage(dir + "/disparity/LtoR_" + alg + "_step" + std::to_string(step) + ".png", l2r);
+  writeImage(dir + "/disparity/RtoL_" + alg + "_step" + std::to_string(step) + ".png", r2l);
 }
 
 // CPU_4Input/main.cpp:54-113: crop every photo to the columns where its centre row is opaque, L = 1 + 3, R = 2 + 4
@@ -109,7 +121,7 @@ static int run4Input(const std::string& dir, const std::string& flow_alg) {
       colorImageR.ptr<unsigned char>(y)[x] = (unsigned char)(r > 255 ? 255 : r);
     }
   Mat FinalResult = stitchStep(colorImageL, &colorImageR, flow_alg);
-  pano_io::imwriteExceptionOnFail(dir + "/FinalResult.png", FinalResult);
+  writeImage(dir + "/FinalResult.png", FinalResult);
   std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
   return EXIT_SUCCESS;
 }
@@ -148,14 +160,17 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
       auto same = [&](const Mat& m) { return m.type() == CV_8UC4 && m.rows == Ls[0].rows && m.cols == Ls[0].cols && m.step == Ls[0].step; };
       if (!same(Ls[k]) || (i == 1 && !same(tops[k])))
         throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
-      outs[k] = Mat(Ls[0].rows, Ls[0].cols, CV_8UC4);
-      l[k] = Ls[k].data; r[k] = tops[k].data; o[k] = outs[k].data;
+      // -png_device: the composites stay in their frame slots and are encoded there; only the one the next plan needs comes down
+      const bool want = !g_png_device || (static_rig && k == 0);
+      outs[k] = want ? Mat(Ls[0].rows, Ls[0].cols, CV_8UC4) : Mat();
+      l[k] = Ls[k].data; r[k] = tops[k].data; o[k] = want ? outs[k].data : nullptr;
     }
+    const size_t ostep = size_t(Ls[0].cols) * 4;   // a fresh Mat's step
     if (static_rig) {
       // outs[0] was replaced above, prev0 still holds the first directory's composite of step i - 1
       StitchPlan plan(Ls[0], i == 1 ? &tops[0] : &prev0);
       const int rc = pf_stitch_step_batch_planned(pano::context(), plan.get(), n, l.data(), i == 1 ? r.data() : nullptr, Ls[0].cols, Ls[0].rows, Ls[0].step,
-                                                  maxPct, o.data(), outs[0].step, in_flight);
+                                                  maxPct, o.data(), ostep, in_flight);
       if (rc != 0) {
         // the frame index is read out of the library's message: the wording "frame <k> differs from the stitch plan" is
         // report_plan_diff()'s in csrc/pf_api_stitch.inl (keep the two in step; tests/test_cli_stitch_static_rig.py pins both)
@@ -170,11 +185,12 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
       }
     } else
     pano::check(pf_stitch_step_batch(pano::context(), n, l.data(), i == 1 ? r.data() : nullptr, Ls[0].cols, Ls[0].rows, Ls[0].step, maxPct,
-                                     o.data(), outs[0].step, in_flight));
+                                     o.data(), ostep, in_flight));
     prev0 = outs[0];
     for (int k = 0; k < n; ++k) {
-      if (i == nsteps) pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "FinalResult.png", outs[k]);
-      else pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", outs[k]);
+      const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
+      if (g_png_device) pano_io::write_png_device(path, pano::context(), k, Ls[0].cols, Ls[0].rows);
+      else pano_io::imwriteExceptionOnFail(path, outs[k]);
     }
     std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
   }
@@ -228,8 +244,8 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
   for (int k = 0; k < n; ++k)
     for (int i = 1; i <= nsteps; ++i) {
       Mat& o_ki = outs[size_t(k) * nsteps + i - 1];
-      if (i == nsteps) pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "FinalResult.png", o_ki);
-      else pano_io::imwriteExceptionOnFail(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", o_ki);
+      if (i == nsteps) writeImage(dirs[k] + "/" + "FinalResult.png", o_ki);
+      else writeImage(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", o_ki);
       o_ki = Mat();
     }
   std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
@@ -239,6 +255,7 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
 int main(int argc, char** argv) {
   try {
     auto flags = parseFlags(argc, argv);
+    g_png_device = flags.count("png_device") && atoi(flags["png_device"].c_str()) != 0;
     if (flags.count("test_dirs")) {   // every refusal before any device call
       if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
       const bool static_rig = flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0;
@@ -282,7 +299,17 @@ int main(int argc, char** argv) {
       if (i == 1) colorImageR = colorImageT; else colorImageR = FinalResult;
       colorImageL = pano_io::imreadExceptionOnFail(FLAGS_test_dir + "/" + char(i + 48) + ".tif");
 
-      if (fused) {
+      if (fused && g_png_device) {
+        // the composite stays in HBM (out_bgra = NULL) for the next step to chain on and for the encoder: only its PNG comes down
+        const int maxPct = pf_max_percentage_by_name(FLAGS_flow_alg.c_str());
+        if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + FLAGS_flow_alg);
+        if (colorImageL.type() != CV_8UC4 || (i == 1 && (colorImageR.type() != CV_8UC4 || colorImageR.rows != colorImageL.rows ||
+                                                         colorImageR.cols != colorImageL.cols || colorImageR.step != colorImageL.step)))
+          throw VrCamException("stitchStep: inputs must be CV_8UC4 images of equal size");
+        pano::check(pf_stitch_step(pano::context(), colorImageL.data, i == 1 ? colorImageR.data : nullptr, colorImageL.cols, colorImageL.rows,
+                                   colorImageL.step, maxPct, nullptr, 0));
+        if (visualize) stitchVisualizations(colorImageL.cols, colorImageL.rows, FLAGS_test_dir, FLAGS_flow_alg, i);
+      } else if (fused) {
         // same kernels, same results; the step's intermediates and the chained R stay in HBM
         FinalResult = stitchStep(colorImageL, i == 1 ? &colorImageR : nullptr, FLAGS_flow_alg);
         if (visualize) stitchVisualizations(colorImageL.cols, colorImageL.rows, FLAGS_test_dir, FLAGS_flow_alg, i);
@@ -307,8 +334,9 @@ int main(int argc, char** argv) {
       delete novelViewGen;
       }
 
-      if (i == nsteps) pano_io::imwriteExceptionOnFail(FLAGS_test_dir + "/" + "FinalResult.png", FinalResult);
-      else pano_io::imwriteExceptionOnFail(FLAGS_test_dir + "/" + "ProcessResult" + char(i + 48) + ".png", FinalResult);
+      const std::string resultPath = FLAGS_test_dir + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
+      if (fused && g_png_device) pano_io::write_png_device(resultPath, pano::context(), colorImageL.cols, colorImageL.rows);
+      else writeImage(resultPath, FinalResult);
       std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
     }
     std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
