@@ -1,8 +1,13 @@
 // The PNG encoder's kernels (csrc/kernels_png.hip) run on the host, thread for thread, under the address and undefined-behaviour
 // sanitizers: every buffer has exactly the size the library gives it, so an index past a segment, a slot or the stream is caught here,
 // without a GPU.  Each file is then framed (csrc/png_frame.hpp), inflated with zlib, unfiltered and compared with the image.
+// With arguments, groups of `IN.bgra cols rows OUT.png`: each raw BGRA file is encoded by the same kernels and the framed file written,
+// for the byte comparison with the serial model (tests/png_model.py).  Without: the shapes below, and build_code on frequency tables
+// that reach both of its length limits.
 // Built and run by tests/test_png_kernels_host.py:  g++ -std=c++20 -fsanitize=address,undefined -Itests/cpp/hip_host_shim ... -lz -pthread
 #include <stdio.h>
+
+#include <queue>
 #include <string.h>
 #include <zlib.h>
 
@@ -45,8 +50,8 @@ static int ref_paeth(int a, int b, int c) {   // the check's own predictor, not 
   return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
-static void encode_and_check(int cols, int rows, int kind) {
-  const std::vector<uint8_t> img = make_image(cols, rows, kind, cols * 131 + rows * 7 + kind);
+// the file of an image, by the kernels and the host framing the library uses; *stream_out = the filtered scanlines
+static std::vector<uint8_t> encode_file(const std::vector<uint8_t>& img, int cols, int rows, std::vector<uint8_t>* stream_out, size_t* nseg_out) {
   const size_t stream = png_frame::stream_bytes(cols, rows), nseg = png_frame::segments(stream);
   std::vector<uint8_t> st(png_stream_alloc_bytes(cols, rows)), slots(nseg * png_frame::kSegSlot), packed(png_frame::deflate_bound(stream));
   std::vector<unsigned> sizes(nseg), adler(nseg);
@@ -57,7 +62,7 @@ static void encode_and_check(int cols, int rows, int kind) {
   host_shim_launch(k_png_gather, (unsigned)nseg, 256u, (const uint8_t*)slots.data(), (const unsigned*)sizes.data(), (const unsigned long long*)offs.data(), packed.data());
   const size_t dlen = offs[nseg];
   CHECK(dlen <= png_frame::deflate_bound(stream));
-  if (dlen > png_frame::deflate_bound(stream)) return;
+  if (dlen > png_frame::deflate_bound(stream)) return {};
   for (size_t s = 0; s < nseg; ++s) CHECK(sizes[s] <= std::min(png_frame::kSegBytes, stream - s * png_frame::kSegBytes) + png_frame::kSegOverhead);
   // the zlib stream as the library frames it
   const png_frame::Frame fr(cols, rows, dlen);
@@ -67,6 +72,19 @@ static void encode_and_check(int cols, int rows, int kind) {
   uint32_t ad = 1;
   for (size_t s = 0; s < nseg; ++s) ad = png_frame::adler32_combine(ad, adler[s], s + 1 < nseg ? png_frame::kSegBytes : stream - s * png_frame::kSegBytes);
   fr.write_tail(file.data(), ad);
+  st.resize(stream);
+  *stream_out = st; *nseg_out = nseg;
+  return file;
+}
+
+static void encode_and_check(int cols, int rows, int kind) {
+  const std::vector<uint8_t> img = make_image(cols, rows, kind, cols * 131 + rows * 7 + kind);
+  std::vector<uint8_t> st;
+  size_t nseg = 0;
+  const std::vector<uint8_t> file = encode_file(img, cols, rows, &st, &nseg);
+  if (file.empty()) return;
+  const size_t stream = png_frame::stream_bytes(cols, rows);
+  const png_frame::Frame fr(cols, rows, file.size() - png_frame::Frame(cols, rows, 0).file_size());
   CHECK(file.size() <= png_frame::bound(cols, rows));
   // inflate (zlib checks the Adler-32), unfilter, compare
   std::vector<uint8_t> raw(stream);
@@ -97,13 +115,125 @@ static void encode_and_check(int cols, int rows, int kind) {
   printf("  %dx%d kind %d: %zu segments, file %zu bytes (%.4f of raw)\n", cols, rows, kind, nseg, file.size(), double(file.size()) / double(img.size()));
 }
 
-int main() {
+// ---- build_code on given frequency tables ----
+__global__ void k_test_build_code(const unsigned* freq, int n, int maxbits, uint8_t* lens, unsigned* codes) {
+  __shared__ HuffScratch hs;
+  build_code(freq, n, maxbits, lens, codes, hs);
+}
+
+// the check's own Huffman tree (a priority queue): the cost of an optimal prefix code and this tree's depth
+static void plain_huffman(const std::vector<unsigned>& freq, unsigned long long* cost, int* depth) {
+  typedef std::pair<unsigned long long, int> Node;   // weight, height
+  std::priority_queue<Node, std::vector<Node>, std::greater<Node>> q;
+  for (unsigned f : freq) if (f) q.push(Node(f, 0));
+  *cost = 0; *depth = 0;
+  while (q.size() > 1) {
+    const Node a = q.top(); q.pop();
+    const Node b = q.top(); q.pop();
+    *cost += a.first + b.first;
+    q.push(Node(a.first + b.first, std::max(a.second, b.second) + 1));
+  }
+  if (!q.empty()) *depth = q.top().second;
+}
+
+// returns whether the unrestricted tree was deeper than the limit
+static bool check_code(const char* what, std::vector<unsigned> freq, int maxbits) {
+  const int n = (int)freq.size();
+  std::vector<uint8_t> lens(std::max(n, 2), 0xAB);
+  std::vector<unsigned> codes(std::max(n, 2), 0xABABABABu);
+  host_shim_launch(k_test_build_code, 1u, 256u, (const unsigned*)freq.data(), n, maxbits, lens.data(), codes.data());
+  int used = 0, maxlen = 0, depth = 0;
+  unsigned long long kraft = 0, cost = 0, best = 0;
+  for (int s = 0; s < n; ++s) {
+    used += freq[s] != 0;
+    if (lens[s]) { CHECK(lens[s] <= maxbits); kraft += 1ull << (maxbits - std::min<int>(lens[s], maxbits)); maxlen = std::max<int>(maxlen, lens[s]); }
+    cost += (unsigned long long)freq[s] * lens[s];
+  }
+  CHECK(kraft == 1ull << maxbits);                   // complete and not over-subscribed, the lone symbol's partner included
+  CHECK(maxlen <= maxbits);
+  if (used >= 2) {
+    for (int s = 0; s < n; ++s) CHECK((lens[s] != 0) == (freq[s] != 0));
+    // lengths do not grow along (freq, index)
+    std::vector<int> order;
+    for (int s = 0; s < n; ++s) if (freq[s]) order.push_back(s);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return freq[a] < freq[b]; });
+    for (size_t i = 1; i < order.size(); ++i) CHECK(lens[order[i]] <= lens[order[i - 1]]);
+    plain_huffman(freq, &best, &depth);
+    if (depth <= maxbits) CHECK(cost == best); else CHECK(cost >= best);   // what fits costs what plain Huffman costs; a limited code no less
+  } else if (used == 1) {
+    int sym = 0, ones = 0;
+    for (int s = 0; s < n; ++s) { if (freq[s]) sym = s; ones += lens[s] == 1; }
+    CHECK(lens[sym] == 1 && ones == 2 && lens[sym == 0 ? 1 : 0] == 1);
+  }
+  // the codes fit their lengths, are distinct, and none is the start of another
+  for (int a = 0; a < n; ++a)
+    for (int b = 0; b < n; ++b) {
+      if (a == b || !lens[a] || !lens[b] || lens[a] > lens[b]) continue;
+      CHECK((codes[b] & ((1u << lens[a]) - 1)) != codes[a]);   // sent from the least significant bit: a start is the low bits
+    }
+  for (int s = 0; s < n; ++s) if (lens[s]) CHECK(codes[s] >> lens[s] == 0);
+  printf("  build_code %s, %d symbols of %d, limit %d: longest %d, plain tree %d deep, cost %llu (optimum %llu)\n", what, used, n, maxbits, maxlen, depth, cost, best);
+  return depth > maxbits;
+}
+
+static void check_build_code() {
+  int limited7 = 0, limited15 = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int maxbits = pass ? 15 : 7, n = pass ? kLitLen : kClSyms;
+    for (int k = pass ? 17 : 10; k <= (pass ? 30 : 19); ++k) {
+      // Fibonacci counts 1, 1, 2, 3, ... on k symbols, the rarest at the highest index and the other way round, and spread over the table
+      std::vector<unsigned> up(n, 0), down(n, 0), spread(n, 0);
+      unsigned a = 1, b = 1;
+      for (int i = 0; i < k; ++i) { up[i] = a; down[k - 1 - i] = a; spread[(i * 7) % n] = a; const unsigned c = a + b; a = b; b = c; }
+      const bool l1 = check_code("fibonacci rising", up, maxbits), l2 = check_code("fibonacci falling", down, maxbits), l3 = check_code("fibonacci spread", spread, maxbits);
+      CHECK(l1 == (k - 1 > maxbits) && l2 == l1 && l3 == l1);
+      (pass ? limited15 : limited7) += l1 + l2 + l3;
+    }
+    check_code("all equal", std::vector<unsigned>(n, 5), maxbits);
+    for (int s : {0, 1, n - 1}) { std::vector<unsigned> f(n, 0); f[s] = 9; check_code("one symbol", f, maxbits); }
+    { std::vector<unsigned> f(n, 0); f[0] = 1; f[n - 1] = 1000; check_code("two symbols", f, maxbits); }
+    { std::vector<unsigned> f(n, 0); f[3] = 4; f[4] = 4; check_code("two equal symbols", f, maxbits); }
+  }
+  CHECK(limited7 > 0 && limited15 > 0);
+}
+
+static std::vector<uint8_t> read_file(const char* path) {
+  std::vector<uint8_t> v;
+  FILE* f = fopen(path, "rb");
+  if (!f) return v;
+  uint8_t buf[65536];
+  for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) v.insert(v.end(), buf, buf + k);
+  fclose(f);
+  return v;
+}
+
+static int encode_files(int argc, char** argv) {
+  if ((argc - 1) % 4) { printf("usage: %s [IN.bgra cols rows OUT.png]...\n", argv[0]); return 2; }
+  for (int i = 1; i < argc; i += 4) {
+    const int cols = atoi(argv[i + 1]), rows = atoi(argv[i + 2]);
+    const std::vector<uint8_t> img = read_file(argv[i]);
+    if (cols <= 0 || rows <= 0 || img.size() != size_t(cols) * rows * 4) { printf("%s is not %d x %d BGRA\n", argv[i], cols, rows); return 2; }
+    std::vector<uint8_t> st;
+    size_t nseg = 0;
+    const std::vector<uint8_t> file = encode_file(img, cols, rows, &st, &nseg);
+    FILE* f = fopen(argv[i + 3], "wb");
+    if (!f || fwrite(file.data(), 1, file.size(), f) != file.size()) { printf("cannot write %s\n", argv[i + 3]); return 2; }
+    fclose(f);
+  }
+  if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
+  printf("ok\n");
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1) return encode_files(argc, argv);
   // (a barrier of 256 host threads is slow: few rows, and only the shapes at which an index can go wrong)
   const int cases[][3] = {{1, 1, 0}, {1, 5, 1}, {7, 1, 1}, {65, 3, 0}, {65, 3, 1},   // no neighbours; a row around 256 bytes
                           {341, 12, 0}, {341, 12, 1}, {341, 13, 1},                     // rows of 1365 bytes: exactly one segment, and a row more
                           {1366, 9, 4}, {1366, 9, 5}};                                  // four segments; runs across thread chunks and segment ends
   for (const auto& cs : cases) encode_and_check(cs[0], cs[1], cs[2]);
   encode_and_check(4099, 3, 2);   // matches of 258 end to end, a run longer than a segment
+  check_build_code();
   if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
   printf("ok\n");
   return 0;

@@ -3,6 +3,8 @@
 decode(data) -> (rows, cols, 4) uint8 BGRA.  It accepts exactly what the encoder promises (8-bit RGBA, no interlace) and raises
 PngError on anything else: a wrong signature, a chunk CRC that zlib.crc32 does not confirm, IHDR fields other than (8, 6, 0, 0, 0),
 a zlib stream that zlib refuses (which covers the Adler-32), does not end or has bytes behind it, a filter type above 4, bytes after IEND.
+
+inflate_trace(z) is an inflate of its own that reports every block: its header, its code lengths, its tokens.
 """
 import struct
 import zlib
@@ -85,6 +87,163 @@ def inflate(z):
     if d.unused_data:
         raise PngError("%d bytes after the zlib stream" % len(d.unused_data))
     return raw
+
+
+# ---- a block-level inflate (RFC 1951), for streams of a few segments: slow, and strict ----
+_LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+_LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+_DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
+_DIST_EXTRA = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+_CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+
+
+def kraft(lens, maxbits=15):
+    """the Kraft sum of a code, in units of 2 ** -maxbits: a complete code gives exactly 2 ** maxbits"""
+    return sum(1 << (maxbits - l) for l in lens if l)
+
+
+def _decoder(lens, what, may_be_lone=False):
+    """{(length, code): symbol} of the canonical code with these lengths.  An over-subscribed code is refused, and so is an incomplete one,
+    but for what RFC 1951 3.2.7 allows the distance code: one code of one bit, or none at all (a block of literals only)."""
+    if max(lens, default=0) > 15:
+        raise PngError("%s code: a length above 15" % what)
+    k, used = kraft(lens), [l for l in lens if l]
+    if k > 1 << 15:
+        raise PngError("%s code is over-subscribed" % what)
+    if k < 1 << 15 and not (may_be_lone and (used == [] or used == [1])):
+        raise PngError("%s code is incomplete" % what)
+    count = [0] * 17
+    for l in used:
+        count[l] += 1
+    nxt, code = [0] * 17, 0
+    for l in range(1, 16):
+        code = (code + count[l - 1]) << 1
+        nxt[l] = code
+    table = {}
+    for s, l in enumerate(lens):
+        if l:
+            table[(l, nxt[l])] = s
+            nxt[l] += 1
+    return table
+
+
+class _BitReader:
+    def __init__(self, data):
+        self.d = data; self.pos = 0
+
+    def bits(self, n):
+        v = 0
+        for i in range(n):
+            if self.pos >> 3 >= len(self.d):
+                raise PngError("the deflate stream ends inside a block")
+            v |= ((self.d[self.pos >> 3] >> (self.pos & 7)) & 1) << i
+            self.pos += 1
+        return v
+
+    def symbol(self, table, what):
+        code = 0
+        for l in range(1, 16):
+            code = code << 1 | self.bits(1)
+            s = table.get((l, code))
+            if s is not None:
+                return s
+        raise PngError("no %s code matches" % what)
+
+
+def inflate_trace(z):
+    """a zlib stream -> (the bytes, blocks).  Per block a dict: bfinal, btype, start_bit / end_bit (offsets into the deflate data, which
+    begins behind the two header bytes), tokens (an int is a literal, (length, distance) a match; a stored block's bytes count as
+    literals) and, for a dynamic block, cl_lens (19), litlen_lens (HLIT + 257), dist_lens (HDIST + 1) and cl_symbols (the code-length
+    symbols as read); for a stored block data_byte,
+    the offset of its first data byte.  Raises PngError on what RFC 1950 / 1951 forbid: a bad header or Adler-32, block type 3,
+    LEN != ~NLEN, a code that is over-subscribed or incomplete, a repeat with nothing before it or past the end of the lengths, no code
+    for the end of the block, length symbols 286 / 287, distance symbols 30 / 31, a distance beyond the output, a stream that ends
+    early, bytes behind it."""
+    z = bytes(z)
+    if len(z) < 6 or z[0] & 15 != 8 or z[0] >> 4 > 7 or (z[0] << 8 | z[1]) % 31 or z[1] & 32:
+        raise PngError("bad zlib header")
+    r = _BitReader(z[2:-4])
+    out, blocks = bytearray(), []
+    while True:
+        blk = {"start_bit": r.pos, "bfinal": r.bits(1), "btype": r.bits(2), "tokens": []}
+        toks = blk["tokens"]
+        if blk["btype"] == 3:
+            raise PngError("block type 3")
+        if blk["btype"] == 0:
+            r.pos = (r.pos + 7) & ~7
+            n, nn = r.bits(16), r.bits(16)
+            if n != nn ^ 0xffff:
+                raise PngError("LEN != ~NLEN")
+            at = r.pos >> 3
+            if at + n > len(r.d):
+                raise PngError("the deflate stream ends inside a stored block")
+            blk["data_byte"] = at
+            toks.extend(r.d[at:at + n]); out += r.d[at:at + n]
+            r.pos += 8 * n
+        else:
+            if blk["btype"] == 1:
+                ll = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8; dl = [5] * 32
+            else:
+                hlit, hdist, hclen = r.bits(5) + 257, r.bits(5) + 1, r.bits(4) + 4
+                if hlit > 286 or hdist > 30:
+                    raise PngError("HLIT / HDIST out of range")
+                cl = [0] * 19
+                for i in range(hclen):
+                    cl[_CL_ORDER[i]] = r.bits(3)
+                cl_table = _decoder(cl, "code-length")
+                lens, blk["cl_symbols"] = [], []
+                while len(lens) < hlit + hdist:
+                    s = r.symbol(cl_table, "code-length")
+                    blk["cl_symbols"].append(s)
+                    if s < 16:
+                        lens.append(s); continue
+                    if s == 16:
+                        if not lens:
+                            raise PngError("repeat with no length before it")
+                        v, k = lens[-1], 3 + r.bits(2)
+                    else:
+                        v, k = 0, (3 + r.bits(3)) if s == 17 else (11 + r.bits(7))
+                    if len(lens) + k > hlit + hdist:
+                        raise PngError("repeat past the end of the code lengths")
+                    lens += [v] * k
+                ll, dl = lens[:hlit], lens[hlit:]
+                blk["cl_lens"], blk["litlen_lens"], blk["dist_lens"] = cl, ll, dl
+                if not ll[256]:
+                    raise PngError("no code for the end of the block")
+            lt, dt = _decoder(ll, "literal / length"), _decoder(dl, "distance", may_be_lone=True)
+            while True:
+                s = r.symbol(lt, "literal / length")
+                if s < 256:
+                    toks.append(s); out.append(s)
+                elif s == 256:
+                    break
+                else:
+                    if s > 285:
+                        raise PngError("length symbol %d" % s)
+                    length = _LEN_BASE[s - 257] + r.bits(_LEN_EXTRA[s - 257])
+                    ds = r.symbol(dt, "distance")
+                    if ds > 29:
+                        raise PngError("distance symbol %d" % ds)
+                    dist = _DIST_BASE[ds] + r.bits(_DIST_EXTRA[ds])
+                    if dist > len(out):
+                        raise PngError("distance %d beyond the output (%d bytes)" % (dist, len(out)))
+                    toks.append((length, dist))
+                    for _ in range(length):
+                        out.append(out[-dist])
+        blk["end_bit"] = r.pos
+        blocks.append(blk)
+        if blk["bfinal"]:
+            break
+    if (r.pos + 7) >> 3 != len(r.d):
+        raise PngError("%d bytes behind the last block" % (len(r.d) - ((r.pos + 7) >> 3)))
+    if zlib.adler32(bytes(out)) != int.from_bytes(z[-4:], "big"):
+        raise PngError("wrong Adler-32")
+    return bytes(out), blocks
+
+
+def zlib_stream(data):
+    """the zlib stream of a file: its IDAT payloads joined"""
+    return b"".join(p for t, p in chunks(bytes(data)) if t == b"IDAT")
 
 
 def decode(data, want_types=False):

@@ -1,5 +1,6 @@
 """The device PNG encoder (pf_png_*, pf_stitch_result_png, pf_stitch_batch_result_png): every file decodes, with the strict reader of
-tests/png_decode_ref.py, to exactly the pixels that went in; the sizes hold their bounds; the bytes are a function of the image."""
+tests/png_decode_ref.py, to exactly the pixels that went in; the sizes hold their bounds; the bytes are a function of the image: the
+function DESIGN.md 8.2 specifies, which tests/png_model.py computes serially, and the files are compared with the model's for equality."""
 import ctypes as C
 import io
 import zlib
@@ -10,6 +11,7 @@ from PIL import Image
 
 import png_cases
 import png_decode_ref as R
+import png_model as M
 
 pytestmark = pytest.mark.gpu
 
@@ -208,3 +210,96 @@ def test_resident_composites_of_a_batch(pf, synth):
             assert np.array_equal(R.decode(c.stitch_batch_result_png(k, (rows, cols))), want[k])
     finally:
         c.close()
+
+
+# ---- byte for byte against the serial model ----
+def _model_images():
+    out = {"small_" + k: v for k, v in SMALL.items()}
+    out.update({"branch_" + k: v for k, v in png_cases.branch_cases().items()})
+    out.update({"constant_zero": png_cases.constant(300, 200, (0, 0, 0, 0)), "constant_7": png_cases.constant(300, 200, (7, 7, 7, 255)),
+                "ramp_sub": png_cases.ramp_sub(), "ramp_up": png_cases.ramp_up(), "noise_300x200": png_cases.noise(300, 200, 1),
+                "alpha_noise_300x200": png_cases.alpha_noise(300, 200, 2), "smooth_300x200": png_cases.smooth(300, 200)})
+    return out
+
+
+MODEL_IMAGES = _model_images()
+_MODEL = {}
+
+
+def _model(img):
+    key = (img.shape, img.tobytes())
+    if key not in _MODEL:
+        _MODEL[key] = M.encode(img)
+    return _MODEL[key]
+
+
+def _first_difference(got, want):
+    k = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    return "%d and %d bytes, first difference at byte %d" % (len(got), len(want), k)
+
+
+@pytest.mark.parametrize("name", sorted(MODEL_IMAGES))
+def test_file_equals_the_serial_model(ctx, name):
+    img = MODEL_IMAGES[name]
+    want, info = _model(img)
+    got = ctx.png_encode(img)
+    if got != want:                                          # say where they part before failing: the filter, the parse or the codes
+        types = R.decode(got, want_types=True)[1]
+        print("filter types differ in rows", np.flatnonzero(types != info["types"]).tolist()[:10])
+    assert got == want, _first_difference(got, want)
+    if name.startswith("branch_"):                           # the stream's promises, read back from the device's own bytes
+        M.check_against_model(got, info)
+
+
+def test_padded_host_rows_equal_the_serial_model(ctx):
+    img = png_cases.smooth(65, 37); img[3:9, 5:40, :] = png_cases.noise(35, 6, 9)
+    padded = np.full((37, 65 + 11, 4), 0xEE, np.uint8); padded[:, :65] = img
+    assert ctx.png_encode(padded[:, :65]) == _model(img)[0]
+
+
+def _batch(ctx, imgs):
+    rows, cols, _ = imgs[0].shape
+    ptrs = [ctx.dev_alloc(im.nbytes) for im in imgs]
+    try:
+        for p, im in zip(ptrs, imgs):
+            ctx.upload(p, im)
+        return ctx.png_encode_batch_dev(ptrs, cols, rows)
+    finally:
+        for p in ptrs:
+            ctx.dev_free(p)
+
+
+def test_batch_of_equal_shapes_equals_the_serial_model(ctx):
+    groups = {}
+    for name, img in png_cases.branch_cases().items():
+        groups.setdefault(img.shape, []).append((name, img))
+    groups = {k: v for k, v in groups.items() if len(v) > 1}
+    assert {(1, 2, 4), (1, 3, 4), (1, 4, 4), (2, 4, 4), (1, 4134, 4)} <= set(groups)
+    for shape, members in sorted(groups.items()):
+        files = _batch(ctx, [im for _, im in members])
+        for (name, im), got in zip(members, files):
+            assert got == _model(im)[0], name
+
+
+def test_batch_of_one_row_cases_at_a_common_width_equals_the_serial_model(ctx):
+    """every one-row case, zero pixels behind it up to the widest: other images than the cases themselves (the filter may choose
+    otherwise), of mixed content and one shape, in one call; the model encodes the padded images"""
+    rows1 = {k: v for k, v in png_cases.branch_cases().items() if v.shape[0] == 1}
+    width = max(v.shape[1] for v in rows1.values())
+    assert len(rows1) >= 20 and width == 4134
+    imgs = []
+    for name in sorted(rows1):
+        im = np.zeros((1, width, 4), np.uint8); im[:, :rows1[name].shape[1]] = rows1[name]
+        imgs.append(im)
+    files = _batch(ctx, imgs)
+    assert len(set(files)) == len(files)
+    for name, im, got in zip(sorted(rows1), imgs, files):
+        assert got == _model(im)[0], name
+
+
+def test_synth_image_filter_types_equal_the_models(ctx, synth):
+    img = synth.make_pair_np(1800, 800, 1234)[0]
+    types = R.decode(ctx.png_encode(img), want_types=True)[1]
+    want = M.filter_image(img)[1]
+    print("filter types %s" % np.bincount(want, minlength=5).tolist())
+    assert np.array_equal(types, want), "rows %s" % np.flatnonzero(types != want).tolist()[:10]
