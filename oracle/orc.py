@@ -1,7 +1,8 @@
 """ctypes binding of the CPU oracle (oracle/pixflow_oracle.cpp).
 
 TEST INFRASTRUCTURE ONLY: may be imported by tests/, __graft_entry__.smoke() and bench.py's
-cpu_baseline leg -- never by the product package.  PARITY UNPINNED (see the .cpp header).
+cpu_baseline leg -- never by the product package.  Reference-owned text pinned by compilation (refcore.py), OpenCV
+primitive arithmetic unpinned (see the .cpp header).
 """
 import ctypes as C
 import os
@@ -162,6 +163,15 @@ def adjust_initial_flow(I0, I1, a0, a1, hint, max_pct):
     flow = np.zeros((h, w, 2), np.float32)
     lib().orc_adjust_initial_flow(_p(I0), _p(_f32(I1)), _p(_f32(a0)), _p(_f32(a1)), w, h, hint, max_pct, _p(flow))
     return flow
+
+
+def patch_error(I0, a0, I1, a1, pts, max_pct):
+    """computePatchError at (N, 4) int32 rows of (i0x, i0y, i1x, i1y)."""
+    I0 = _f32(I0); h, w = I0.shape
+    p = np.ascontiguousarray(pts, dtype=np.int32)
+    out = np.empty(len(p), np.float32)
+    lib().orc_patch_error(_p(I0), _p(_f32(a0)), _p(_f32(I1)), _p(_f32(a1)), w, h, _p(p), len(p), max_pct, _p(out))
+    return out
 
 
 def diffusion(a0, a1, flow):

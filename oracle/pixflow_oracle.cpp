@@ -1,5 +1,5 @@
 // =============================================================================================
-// oracle/pixflow_oracle.cpp  --  TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED (see below).
+// oracle/pixflow_oracle.cpp  --  TEST INFRASTRUCTURE ONLY.  REFERENCE-OWNED TEXT PINNED, OPENCV PRIMITIVES UNPINNED (see below).
 //
 // CPU restatement of the reference's asymmetric bidirectional optical-flow blending path:
 //   /root/reference/CPU/PixFlow.hpp (all), CPU/OpticalFlow.cpp:9-145, CPU/StitchTool.cpp (all),
@@ -7,9 +7,11 @@
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may build/link/call this
 // file.  The product (panorama-opticalflow_amd/) never does.
 //
-// PARITY UNPINNED: the reference has no tests / golden vectors (Test_data is absent), and all its
-// pixel arithmetic lives in OpenCV 3.2 which is neither vendored nor installed here, so the
-// reference cannot be compiled in this image.  The OpenCV primitives below are restated from the
+// PARITY STATUS: every line the reference's authors wrote is pinned by compilation -- `make -C oracle refcore` builds the
+// reference's own translation units unmodified against a stand-in for OpenCV (oracle/cvstub) that delegates the primitives
+// to this file's exports, and tests/test_ref_core.py compares that build with this restatement bit for bit (DESIGN.md
+// section 6; no disagreement found).  UNPINNED is the arithmetic inside the OpenCV primitives: the reference has no tests /
+// golden vectors (Test_data is absent) and OpenCV 3.2 is neither vendored nor installed here.  They are restated from the
 // published OpenCV-3.2 algorithms (imgproc/src/{imgwarp,smooth,filter,deriv,color}.cpp, scalar
 // non-IPP paths); each one says which.  They are cross-checked against independent
 // implementations (scipy.ndimage, torch.nn.functional.interpolate) in tests/test_oracle_primitives.py.
@@ -883,6 +885,11 @@ void orc_adjust_initial_flow(const float* I0, const float* I1, const float* a0, 
   adjustInitialFlow(i0, i1, A0, A1, f, hint, maxPct);
   std::memcpy(flow, f.d.data(), f.d.size() * 4);
 }
+// PixFlow<P>::computePatchError (PixFlow.hpp:157-188) at n explicit (i0x, i0y, i1x, i1y) -- for the comparison with the reference's own text
+void orc_patch_error(const float* I0, const float* a0, const float* I1, const float* a1, int w, int h, const int* pts, int n, int maxPct, float* out) {
+  ImgF i0 = wrapF(I0, w, h, 1), A0 = wrapF(a0, w, h, 1), i1 = wrapF(I1, w, h, 1), A1 = wrapF(a1, w, h, 1);
+  for (int i = 0; i < n; ++i) out[i] = computePatchError(i0, A0, pts[4 * i], pts[4 * i + 1], i1, A1, pts[4 * i + 2], pts[4 * i + 3], maxPct);
+}
 void orc_diffusion(const float* a0, const float* a1, float* flow, int w, int h) {
   ImgF A0 = wrapF(a0, w, h, 1), A1 = wrapF(a1, w, h, 1), f = wrapF(flow, w, h, 2);
   lowAlphaFlowDiffusion(A0, A1, f); std::memcpy(flow, f.d.data(), f.d.size() * 4);
@@ -950,5 +957,5 @@ void orc_stitch_gather(const uint8_t* L, const uint8_t* R, const uint8_t* merged
   s.Map = wrapU8(map, cols, rows, 1); s.Gather();
   std::memcpy(out, s.FinalResult.d.data(), s.FinalResult.d.size());
 }
-const char* orc_version() { return "pixflow-oracle r1 (parity unpinned: OpenCV 3.2 semantics restated)"; }
+const char* orc_version() { return "pixflow-oracle r1 (reference text pinned by compilation; OpenCV 3.2 primitives restated, unpinned)"; }
 }

@@ -7,7 +7,8 @@ oracle/_ref/pano_ref on it for both algorithms, runs the oracle on the same imag
   * reports per-step PSNR / max LSB difference between the two (the oracle's claim is: identical),
   * stores the reference's own FinalResult as tests/golden/ref_<alg>_<cols>x<rows>.npz, i.e. fixtures produced by the
     reference itself, which tests/test_golden.py then holds the oracle (and through it the HIP path) to.
-Until this has run somewhere, DESIGN.md / the oracle header say "parity unpinned".
+Until this has run somewhere, DESIGN.md / the oracle header say: the reference's own text is pinned by compilation against a stand-in
+(`make -C oracle refcore`), the arithmetic inside the OpenCV primitives is unpinned.  This script is what pins that remainder.
 """
 import importlib.util
 import os
