@@ -483,6 +483,36 @@ int pf_png_encode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_bgra, in
 int pf_stitch_result_png(pf_ctx* ctx, uint8_t* png_out, size_t cap, size_t* size_out);
 int pf_stitch_batch_result_png(pf_ctx* ctx, int frame, uint8_t* png_out, size_t cap, size_t* size_out);
 
+/* ---- TIFF files decoded on the device ----------------------------------------------------------
+ * The counterpart of the PNG encoder: the bytes of a TIFF file (HOST memory) go up as they are, the strips decode in parallel on the
+ * device (one workgroup per strip: LZW -- compression 5 -- and PackBits -- 32773 --; uncompressed strips are read in place), the
+ * predictor (2 = horizontal differencing) is undone per row and the pixels are stored as packed BGRA, alpha 255 for RGB files: what
+ * cv::imread(-1) + BGR->BGRA delivers.  Opt-in: no other entry point's behaviour depends on these.
+ * Accepted: the first IFD of a little- or big-endian classic TIFF with 8-bit chunky RGB / RGBA strips.  Tiles, 16-bit, palette and
+ * planar files, FillOrder 2, an inconsistent strip table, a strip that does not lie inside the file and images over 4e9 pixels are
+ * refused with a message; a hostile IFD cannot cause a read outside `file`.
+ *   pf_tiff_probe   host only, needs no device; ctx may be NULL (pf_last_error(ctx) / pf_last_error(NULL) explains a refusal).
+ *                   out->struct_size must be set to sizeof(pf_tiff_info).  device_decodable is 0 for deflate files
+ *                   (compression 8 / 32946), which the decode calls refuse with PF_ERR_ARG: use a host reader for them.
+ *   cols, rows      what the caller expects, as learned from the probe; a file of another size is PF_ERR_ARG before any work.
+ *   _dev            d_out_bgra: device memory of this context's device, cols * rows * 4 bytes, packed rows, 4-byte aligned.
+ *   pf_tiff_decode  delivers to HOST memory with a row step of out_step bytes; bytes of a row beyond cols * 4 are left untouched.
+ *   batch           n same-size files -> the bytes of n single calls, their kernels enqueued together before one drain.
+ * A strip whose stream is malformed or ends before the strip's rows are filled fails the call with PF_ERR_ARG; pf_last_error names
+ * the first such strip and how many of its bytes decoded.  The device forms then zero-fill their outputs (all of them, in the batch
+ * form) and the host form writes nothing.  This differs from the drop-in CLI's host reader (tools/image_io.hpp read_tiff), which
+ * zero-fills the rest of a short strip silently and returns the image: the device path refuses the file.
+ * The scratch is the decoder's own: these calls leave alone the chain state, the prefetch records, the frame slots, the plans and
+ * what pf_stitch_visualize reads.  Kernel families in pf_profile_*: tiff_lzw, tiff_packbits, tiff_finish. */
+typedef struct pf_tiff_info {
+  int struct_size, cols, rows, samples, compression, predictor, rows_per_strip, n_strips, big_endian, device_decodable;
+} pf_tiff_info;
+int pf_tiff_probe(pf_ctx* ctx, const uint8_t* file, size_t bytes, pf_tiff_info* out);
+int pf_tiff_decode_dev(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* d_out_bgra);
+int pf_tiff_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* out_bgra, size_t out_step);
+int pf_tiff_decode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, int cols, int rows,
+                             uint8_t* const* d_out_bgra);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

@@ -18,11 +18,12 @@
 #include "../../include/panoflow.h"
 #include "pf_common.hpp"
 #include "png_frame.hpp"
+#include "tiff_parse.hpp"
 
 using namespace pf;
 
 
-// One translation unit in eight parts (the anonymous namespace and the extern "C" block span several of them):
+// One translation unit in nine parts (the anonymous namespace and the extern "C" block span several of them):
 #include "pf_api_ctx.inl"      // pf_ctx, errors / warnings, arena, profiling events, geometry, checks
 #include "pf_api_solve.inl"    // run_level, solve buffers, solve / solve_n (stream orchestration)
 #include "pf_api_life.inl"     // finish / CallGuard, pf_create* / pf_destroy, memory helpers            (opens extern "C")
@@ -31,5 +32,6 @@ using namespace pf;
 #include "pf_api_stage.inl"    // pf_stage_*, pf_profile_*, pf_level_pixels / pf_algorithmic_bytes
 #include "pf_api_vis.inl"      // pf_vis_*, pf_stitch_visualize (flow visualisers)
 #include "pf_api_png.inl"      // pf_png_*, pf_stitch_result_png (PNG files made on the device)
+#include "pf_api_tiff.inl"     // pf_tiff_* (TIFF files decoded on the device)
 }  // extern "C"
 

@@ -249,4 +249,23 @@ void launch_png_filter(hipStream_t st, const uint8_t* bgra /* packed, 4-byte ali
 void launch_png_deflate(hipStream_t st, int cols, int rows, const PngWork& w);   // stream -> slots, sizes, adler
 void launch_png_pack(hipStream_t st, int cols, int rows, const PngWork& w);      // sizes -> offs; slots -> packed
 
+// ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits), then predictor + RGB(A) -> BGRA per row ----
+// A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled
+// the strip; the strip is good when the low half equals its expected bytes).
+constexpr unsigned kTiffBadCode = 1;        // LZW: a code above the table's next entry, or a non-literal first code after a Clear
+constexpr unsigned kTiffBadTableFull = 2;   // LZW: code == next with the table full
+constexpr unsigned kTiffCutPacket = 3;      // PackBits: a packet runs past the strip's bytes
+struct TiffWork {
+  const uint8_t* file;         // the uploaded file bytes
+  unsigned long long bytes;    // ... and how many
+  const uint32_t* offsets;     // per strip: file offset
+  const uint32_t* counts;      // per strip: compressed bytes
+  int n_strips, cols, rows, samples, rows_per_strip, predictor;
+  uint8_t* plane;              // decoded samples, rows * cols * samples bytes (unused for compression 1)
+  unsigned long long* status;  // per strip
+};
+void launch_tiff_lzw(hipStream_t st, const TiffWork& w);        // file -> plane, status
+void launch_tiff_packbits(hipStream_t st, const TiffWork& w);   // file -> plane, status
+void launch_tiff_finish(hipStream_t st, const TiffWork& w, bool from_file /* compression 1: samples read from the file */, uint8_t* bgra /* packed, 4-byte aligned */);
+
 }  // namespace pf

@@ -54,6 +54,12 @@ class SolverParams(C.Structure):
                 ("directional_regularization_coef", C.c_float)]
 
 
+class TiffInfo(C.Structure):
+    """pf_tiff_info (include/panoflow.h)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "cols", "rows", "samples", "compression", "predictor", "rows_per_strip", "n_strips", "big_endian",
+                                        "device_decodable")]
+
+
 def lib(exp=False):
     """exp=False: the product library.  exp=True: the lab build with the cross-check sweeps (tests / diagnostics only)."""
     _lib = _libs.get(bool(exp))
@@ -100,6 +106,10 @@ def lib(exp=False):
         _lib.pf_png_bound.argtypes = [C.c_int, C.c_int]
         _lib.pf_png_segment_bytes.restype = C.c_size_t
         _lib.pf_png_segment_bytes.argtypes = []
+        _lib.pf_tiff_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TiffInfo)]
+        _lib.pf_tiff_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_tiff_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        _lib.pf_tiff_decode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     return _lib
 
 
@@ -120,6 +130,7 @@ EXPORTS = [
     "pf_stage_preprocess_batch", "pf_stage_pyramid", "pf_stage_adjust_initial_flow_batch", "pf_stage_intensity_ratio",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_png_bound", "pf_png_segment_bytes", "pf_png_encode_dev", "pf_png_encode", "pf_png_encode_batch_dev", "pf_stitch_result_png", "pf_stitch_batch_result_png",
+    "pf_tiff_probe", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -150,6 +161,15 @@ def max_percentage_by_name(name):
 def png_bound(cols, rows):
     """capacity that holds the PNG of any cols x rows image (pf_png_bound)"""
     return int(lib().pf_png_bound(cols, rows))
+
+
+def tiff_probe(data):
+    """TiffInfo of the first IFD of a TIFF file's bytes (pf_tiff_probe: host only, no device needed); raises on a refusal"""
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)   # (an empty file is still a pointer and a length of 0)
+    info = TiffInfo(); info.struct_size = C.sizeof(TiffInfo)
+    if lib().pf_tiff_probe(None, _p(buf), C.c_size_t(len(data)), C.byref(info)) != 0:
+        raise PanoflowError(lib().pf_last_error(None).decode())
+    return info
 
 
 def png_segment_bytes():
@@ -561,6 +581,32 @@ class Context:
         """the PNG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
         rows, cols = shape
         return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
+
+    # ---- TIFF files decoded on the device (pf_tiff_*): `data` = the file's bytes ----
+    def tiff_decode(self, data, shape=None, row_step=None, out=None):
+        """file bytes -> host BGRA (rows, cols, 4); shape = (rows, cols) the caller expects (default: the probe's).  row_step (bytes) or
+        out (an array whose rows are row_step apart) selects a padded destination; the padding is left as it is"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        if shape is None:
+            info = tiff_probe(data); shape = (info.rows, info.cols)
+        rows, cols = shape
+        step = int(row_step) if row_step is not None else cols * 4
+        if out is None:
+            out = np.empty((rows, step), np.uint8)
+        self._chk(self.l.pf_tiff_decode(self.h, _p(buf), C.c_size_t(buf.size), cols, rows, _p(out), C.c_size_t(step)))
+        return out[:, :cols * 4].reshape(rows, cols, 4)
+
+    def tiff_decode_dev(self, data, cols, rows, d_out):
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self._chk(self.l.pf_tiff_decode_dev(self.h, _p(buf), C.c_size_t(buf.size), cols, rows, C.c_void_p(d_out)))
+
+    def tiff_decode_batch_dev(self, datas, cols, rows, d_outs):
+        """n same-size files -> n device images"""
+        n = len(datas)
+        bufs = [np.frombuffer(bytes(d), np.uint8) for d in datas]
+        files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)(*[b.size for b in bufs])
+        outs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_outs])
+        self._chk(self.l.pf_tiff_decode_batch_dev(self.h, n, files, sizes, cols, rows, outs))
 
     # ---- device-resident entry points (raw device pointers as ints) ----
     def dev_alloc(self, nbytes):

@@ -4,6 +4,8 @@
 //     Deflate / PackBits, predictor 1 or 2.  Tiles, 16-bit, palette and planar files are rejected with a message.
 //   * PNG reader/writer: 8-bit RGB/RGBA, non-interlaced (zlib).
 //   * write_png_device: the same pixels as a PNG the library makes on the GPU (pf_png_*); only the finished file comes to the host.
+//   * imread_device / imread_to_device: a TIFF's strips decoded on the GPU (pf_tiff_*); only the file's bytes go up.  read_tiff stays
+//     the behaviour model and the fallback (deflate files, files of few strips).
 // Pixels are delivered as BGRA (CV_8UC4) like cv::imread(-1) followed by the reference's BGR->BGRA (main.cpp:58,68).
 #ifndef PANO_IMAGE_IO_HPP_
 #define PANO_IMAGE_IO_HPP_
@@ -245,6 +247,50 @@ static inline Mat imreadExceptionOnFail(const std::string& path) {
   throw VrCamException("failed to load image (unsupported extension): " + path);
 }
 static inline void imwriteExceptionOnFail(const std::string& path, const Mat& image) { write_png(path, image); }
+
+// ---------------------------------------------------------------- TIFF decoded on the device (pf_tiff_*)
+static inline bool is_tiff_name(const std::string& path) {
+  const size_t dot = path.rfind('.'); std::string ext = dot == std::string::npos ? "" : path.substr(dot + 1);
+  for (auto& c : ext) c = (char)tolower(c);
+  return ext == "tif" || ext == "tiff";
+}
+// The device rule: a file goes to the device when the library can decode it there (no compression, LZW, PackBits) and it either is
+// uncompressed or has at least 64 strips -- the strips are what runs in parallel; a single LZW strip is one serial stream and stays with
+// the host.  Everything else (deflate, few strips, anything the probe refuses) goes to read_tiff, which also words the refusals.
+static inline bool tiff_goes_to_device(pf_ctx* ctx, const std::vector<unsigned char>& b, pf_tiff_info* info) {
+  info->struct_size = (int)sizeof *info;
+  if (pf_tiff_probe(ctx, b.data(), b.size(), info) != 0) return false;
+  return info->device_decodable && (info->compression == 1 || info->n_strips >= 64);
+}
+// imreadExceptionOnFail with -tiff_device 1: the same pixels; a .tif under the device rule is decoded on the GPU into the host image
+static inline Mat imread_device(const std::string& path, pf_ctx* ctx) {
+  if (!is_tiff_name(path)) return imreadExceptionOnFail(path);
+  const std::vector<unsigned char> b = read_file(path);
+  pf_tiff_info info;
+  if (!tiff_goes_to_device(ctx, b, &info)) return read_tiff(path);
+  Mat m(info.rows, info.cols, panocv::CV_8UC4);
+  if (pf_tiff_decode(ctx, b.data(), b.size(), info.cols, info.rows, m.data, m.step) != 0) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx) + ": " + path);
+  return m;
+}
+// ... into a fresh pf_dev_alloc buffer (the caller frees it): under the device rule only the file's bytes cross the link, otherwise the
+// host reader's image is uploaded
+static inline uint8_t* imread_to_device(const std::string& path, pf_ctx* ctx, int* cols, int* rows) {
+  std::vector<unsigned char> b;
+  pf_tiff_info info;
+  const bool dev = is_tiff_name(path) && (b = read_file(path), tiff_goes_to_device(ctx, b, &info));
+  Mat host;
+  if (!dev) { host = imreadExceptionOnFail(path); info.cols = host.cols; info.rows = host.rows; }
+  uint8_t* d = (uint8_t*)pf_dev_alloc(ctx, size_t(info.cols) * info.rows * 4);
+  if (!d) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+  const size_t row = size_t(info.cols) * 4;
+  int rc = 0;
+  if (dev) rc = pf_tiff_decode_dev(ctx, b.data(), b.size(), info.cols, info.rows, d);
+  else if (host.step == row) rc = pf_upload(ctx, d, host.data, row * host.rows);
+  else for (int y = 0; y < host.rows && rc == 0; ++y) rc = pf_upload(ctx, d + y * row, host.data + y * host.step, row);   // padded rows; the device image is packed
+  if (rc != 0) { pf_dev_free(ctx, d); throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx) + ": " + path); }
+  *cols = info.cols; *rows = info.rows;
+  return d;
+}
 
 }  // namespace pano_io
 #endif

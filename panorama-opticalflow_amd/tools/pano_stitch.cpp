@@ -25,6 +25,14 @@
 //   HBM (pf_stitch_result_png / pf_stitch_batch_result_png) and bring no raw composite down (-static_rig 1: only the first directory's,
 //   which the next plan is made from); -rig_chain 1, -inputs 4, -fused 0 and the -visualize panels hold their images on the host and
 //   send them up to be encoded (pf_png_encode).
+//   -tiff_device 1 (any mode; off by default): a .tif input is decoded on the GPU (pf_tiff_*) when the library can decode it there -- no
+//   compression, LZW or PackBits -- and it is uncompressed or has at least 64 strips (strips decode in parallel; a single LZW strip is one
+//   serial stream and stays with the host).  Every other file, deflate TIFFs included, goes through the host reader as before.  The
+//   pixels are the host reader's, with one difference: a malformed or short strip, which the host reader zero-fills silently, ends the run
+//   with an error.  With -rig_chain 1 every input is decoded into its own device buffer, the rig plan is made from device images
+//   (pf_rig_plan_create_dev) and the chains run through pf_rig_stitch_batch_dev; with -png_device 1 as well each composite is encoded
+//   where it lies, so no raw image crosses the link in either direction; without it the composites are downloaded and written by the
+//   default writer.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -48,6 +56,11 @@ static bool g_png_device = false;   // -png_device 1
 static void writeImage(const std::string& path, const Mat& image) {
   if (g_png_device) pano_io::write_png_device(path, pano::context(), image);
   else pano_io::imwriteExceptionOnFail(path, image);
+}
+static bool g_tiff_device = false;   // -tiff_device 1
+// an image file to a host image, by the host readers or (a .tif under the device rule, see the usage note) through the device decoder
+static Mat readImage(const std::string& path) {
+  return g_tiff_device ? pano_io::imread_device(path, pano::context()) : pano_io::imreadExceptionOnFail(path);
 }
 
 static std::map<std::string, std::string> parseFlags(int argc, char** argv) {   // gflags syntax: -name value | --name=value
@@ -105,7 +118,7 @@ static void stitchVisualizations(int cols, int rows, const std::string& dir, con
 static int run4Input(const std::string& dir, const std::string& flow_alg) {
   double StartTime = getCurrTimeSec();
   Mat im[4];
-  for (int i = 0; i < 4; ++i) im[i] = pano_io::imreadExceptionOnFail(dir + "/" + char(i + 49) + ".tif");
+  for (int i = 0; i < 4; ++i) im[i] = readImage(dir + "/" + char(i + 49) + ".tif");
   for (int i = 1; i < 4; ++i)
     if (im[i].rows != im[0].rows || im[i].cols != im[0].cols) throw VrCamException("4-input mode: the four photos must have the same size");
   const int rows = im[0].rows, cols = im[0].cols;
@@ -150,10 +163,10 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
   const int n = (int)dirs.size();
   std::vector<Mat> tops(n), Ls(n), outs(n);
   Mat prev0;   // -static_rig: the first directory's previous composite, the R of its next plan
-  for (int k = 0; k < n; ++k) tops[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + top_img);
+  for (int k = 0; k < n; ++k) tops[k] = readImage(dirs[k] + "/" + top_img);
   for (int i = 1; i <= nsteps; i++) {
     double StepStart = getCurrTimeSec();
-    for (int k = 0; k < n; ++k) Ls[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + char(i + 48) + ".tif");
+    for (int k = 0; k < n; ++k) Ls[k] = readImage(dirs[k] + "/" + char(i + 48) + ".tif");
     std::vector<const uint8_t*> l(n), r(n);
     std::vector<uint8_t*> o(n);
     for (int k = 0; k < n; ++k) {
@@ -209,8 +222,8 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
   std::vector<const uint8_t*> t(n), l(size_t(n) * nsteps);
   std::vector<uint8_t*> o(size_t(n) * nsteps);
   for (int k = 0; k < n; ++k) {
-    tops[k] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + top_img);
-    for (int i = 0; i < nsteps; ++i) Ls[size_t(k) * nsteps + i] = pano_io::imreadExceptionOnFail(dirs[k] + "/" + char(i + 49) + ".tif");
+    tops[k] = readImage(dirs[k] + "/" + top_img);
+    for (int i = 0; i < nsteps; ++i) Ls[size_t(k) * nsteps + i] = readImage(dirs[k] + "/" + char(i + 49) + ".tif");
   }
   auto same = [&](const Mat& m) { return m.type() == CV_8UC4 && m.rows == tops[0].rows && m.cols == tops[0].cols && m.step == tops[0].step; };
   for (int k = 0; k < n; ++k) {
@@ -252,10 +265,77 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
   return EXIT_SUCCESS;
 }
 
+// -rig_chain 1 -tiff_device 1: the same chains with every image in device memory.  Each input is decoded into its own pf_dev_alloc buffer,
+// the rig plan is made from the first directory's device images, the chains run through pf_rig_stitch_batch_dev with a d_out per step, and
+// each composite is encoded where it lies (-png_device 1) or downloaded for the default writer.
+static int runRigChainDevice(const std::vector<std::string>& dirs, const std::string& top_img, const std::string& flow_alg, int nsteps, int in_flight) {
+  const int maxPct = pf_max_percentage_by_name(flow_alg.c_str());
+  if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + flow_alg);
+  if (nsteps < 1 || nsteps > 9) throw VrCamException("-rig_chain: -steps must be 1..9");
+  double StartTime = getCurrTimeSec();
+  pf_ctx* ctx = pano::context();
+  const int n = (int)dirs.size();
+  struct DevImages {   // frees what was allocated, however the run ends
+    pf_ctx* ctx; std::vector<uint8_t*> p;
+    ~DevImages() { for (uint8_t* q : p) if (q) pf_dev_free(ctx, q); }
+  } dev{ctx, {}};
+  std::vector<const uint8_t*> t(n), l(size_t(n) * nsteps);
+  std::vector<uint8_t*> o(size_t(n) * nsteps);
+  int cols = 0, rows = 0;
+  auto load = [&](const std::string& path) {
+    int c = 0, r = 0;
+    dev.p.push_back(pano_io::imread_to_device(path, ctx, &c, &r));
+    if (cols == 0) { cols = c; rows = r; }
+    if (c != cols || r != rows) throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
+    return dev.p.back();
+  };
+  for (int k = 0; k < n; ++k) {
+    t[k] = load(dirs[k] + "/" + top_img);
+    for (int i = 0; i < nsteps; ++i) l[size_t(k) * nsteps + i] = load(dirs[k] + "/" + char(i + 49) + ".tif");
+  }
+  for (size_t at = 0; at < o.size(); ++at) {
+    o[at] = (uint8_t*)pf_dev_alloc(ctx, size_t(cols) * rows * 4);
+    if (!o[at]) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+    dev.p.push_back(o[at]);
+  }
+  pf_rig_plan* rig = nullptr;
+  pano::check(pf_rig_plan_create_dev(ctx, nsteps, t[0], l.data(), cols, rows, &rig));
+  std::cout << "Rig plan of " << nsteps << " steps made!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
+  const int rc = pf_rig_stitch_batch_dev(ctx, rig, n, t.data(), l.data(), cols, rows, maxPct, o.data(), in_flight);
+  const std::string msg = rc != 0 ? pf_last_error(ctx) : "";
+  pf_rig_plan_destroy(ctx, rig);
+  if (rc != 0) {
+    // the same wording as runRigChain's: "frame <k> differs from the rig plan at step <i>" is report_rig_diff()'s (tests/test_cli_rig_chain.py pins both)
+    const size_t at = msg.find("frame "), st = msg.find("differs from the rig plan at step ");
+    if (at != std::string::npos && st != std::string::npos) {
+      const int k = atoi(msg.c_str() + at + 6), i = atoi(msg.c_str() + st + 34);
+      if (k >= 0 && k < n)
+        throw VrCamException("-rig_chain: step " + std::to_string(i) + ": the alpha masks of directory " + dirs[k] + " are not those of " + dirs[0] +
+                             " (panoflow: " + msg + ")");
+    }
+    throw VrCamException("panoflow: " + msg);
+  }
+  for (int k = 0; k < n; ++k)
+    for (int i = 1; i <= nsteps; ++i) {
+      const uint8_t* d = o[size_t(k) * nsteps + i - 1];
+      const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
+      if (g_png_device) {
+        pano_io::write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* size) { return pf_png_encode_dev(ctx, d, cols, rows, b, cap, size); });
+      } else {
+        Mat m(rows, cols, CV_8UC4);
+        for (int y = 0; y < rows; ++y) pano::check(pf_download(ctx, m.ptr<unsigned char>(y), d + size_t(y) * cols * 4, size_t(cols) * 4));
+        pano_io::imwriteExceptionOnFail(path, m);
+      }
+    }
+  std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
+  return EXIT_SUCCESS;
+}
+
 int main(int argc, char** argv) {
   try {
     auto flags = parseFlags(argc, argv);
     g_png_device = flags.count("png_device") && atoi(flags["png_device"].c_str()) != 0;
+    g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     if (flags.count("test_dirs")) {   // every refusal before any device call
       if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
       const bool static_rig = flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0;
@@ -271,6 +351,7 @@ int main(int argc, char** argv) {
       const int nsteps = flags.count("steps") ? atoi(flags["steps"].c_str()) : 5;
       const int in_flight = flags.count("in_flight") ? atoi(flags["in_flight"].c_str()) : 8;
       if (in_flight < 1 || in_flight > 32) throw VrCamException("-in_flight must be 1..32");
+      if (rig_chain && g_tiff_device) return runRigChainDevice(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight);
       if (rig_chain) return runRigChain(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight);
       return runBatchDirs(dirs, flags["top_img"], flags["flow_alg"], nsteps, in_flight, static_rig);
     }
@@ -291,13 +372,13 @@ int main(int argc, char** argv) {
     requireArg(FLAGS_flow_alg, "flow_alg");
 
     Mat colorImageL, colorImageR, FinalResult;
-    Mat colorImageT = pano_io::imreadExceptionOnFail(FLAGS_test_dir + "/" + FLAGS_top_img);
+    Mat colorImageT = readImage(FLAGS_test_dir + "/" + FLAGS_top_img);
     if (visualize && mkdir((FLAGS_test_dir + "/disparity").c_str(), 0777) != 0 && errno != EEXIST)
       throw VrCamException("cannot create " + FLAGS_test_dir + "/disparity");
     for (int i = 1; i <= nsteps; i++) {
       double StepStart = getCurrTimeSec();
       if (i == 1) colorImageR = colorImageT; else colorImageR = FinalResult;
-      colorImageL = pano_io::imreadExceptionOnFail(FLAGS_test_dir + "/" + char(i + 48) + ".tif");
+      colorImageL = readImage(FLAGS_test_dir + "/" + char(i + 48) + ".tif");
 
       if (fused && g_png_device) {
         // the composite stays in HBM (out_bgra = NULL) for the next step to chain on and for the encoder: only its PNG comes down
