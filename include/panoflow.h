@@ -492,8 +492,16 @@ int pf_stitch_batch_result_png(pf_ctx* ctx, int frame, uint8_t* png_out, size_t 
  * planar files, FillOrder 2, an inconsistent strip table, a strip that does not lie inside the file and images over 4e9 pixels are
  * refused with a message; a hostile IFD cannot cause a read outside `file`.
  *   pf_tiff_probe   host only, needs no device; ctx may be NULL (pf_last_error(ctx) / pf_last_error(NULL) explains a refusal).
- *                   out->struct_size must be set to sizeof(pf_tiff_info).  device_decodable is 0 for deflate files
- *                   (compression 8 / 32946), which the decode calls refuse with PF_ERR_ARG: use a host reader for them.
+ *                   out->struct_size must be set to sizeof(pf_tiff_info).  device_decodable means "with default settings": it
+ *                   is 0 for deflate files (compression 8 / 32946), which the decode calls refuse with PF_ERR_ARG by default:
+ *                   use a host reader for them, or the switch below.
+ *   pf_tiff_set_inflate   on != 0: this context's decode calls also take deflate files -- every strip one zlib stream, stored,
+ *                   fixed and dynamic blocks, predictor 1 or 2 -- alone or mixed with the other classes in a batch.  Default 0:
+ *                   deflate files are refused as before.  A deflate strip is accepted exactly when zlib's own
+ *                   uncompress(dst, expected bytes, strip) returns Z_OK or Z_BUF_ERROR with all expected bytes delivered (an
+ *                   over-long stream is clipped; a wrong Adler-32 or any malformed block refuses the file, as below).
+ *   pf_tiff_device_decodable   1 / 0: would this context's decode calls take the probed file?  ctx == NULL: the defaults, i.e.
+ *                   the probe's own field.  Host only.
  *   cols, rows      what the caller expects, as learned from the probe; a file of another size is PF_ERR_ARG before any work.
  *   _dev            d_out_bgra: device memory of this context's device, cols * rows * 4 bytes, packed rows, 4-byte aligned.
  *   pf_tiff_decode  delivers to HOST memory with a row step of out_step bytes; bytes of a row beyond cols * 4 are left untouched.
@@ -503,11 +511,13 @@ int pf_stitch_batch_result_png(pf_ctx* ctx, int frame, uint8_t* png_out, size_t 
  * form) and the host form writes nothing.  This differs from the drop-in CLI's host reader (tools/image_io.hpp read_tiff), which
  * zero-fills the rest of a short strip silently and returns the image: the device path refuses the file.
  * The scratch is the decoder's own: these calls leave alone the chain state, the prefetch records, the frame slots, the plans and
- * what pf_stitch_visualize reads.  Kernel families in pf_profile_*: tiff_lzw, tiff_packbits, tiff_finish. */
+ * what pf_stitch_visualize reads.  Kernel families in pf_profile_*: tiff_lzw, tiff_packbits, tiff_inflate, tiff_finish. */
 typedef struct pf_tiff_info {
   int struct_size, cols, rows, samples, compression, predictor, rows_per_strip, n_strips, big_endian, device_decodable;
 } pf_tiff_info;
 int pf_tiff_probe(pf_ctx* ctx, const uint8_t* file, size_t bytes, pf_tiff_info* out);
+int pf_tiff_set_inflate(pf_ctx* ctx, int on);            /* default 0 */
+int pf_tiff_device_decodable(const pf_ctx* ctx, const pf_tiff_info* info);   /* 1 / 0; ctx == NULL: the defaults */
 int pf_tiff_decode_dev(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* d_out_bgra);
 int pf_tiff_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* out_bgra, size_t out_step);
 int pf_tiff_decode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, int cols, int rows,

@@ -79,6 +79,7 @@ struct pf_ctx {
   unsigned* d_rig_diff = nullptr;       // pixels whose region code differs from the rig's (k_rig_maps adds, the host reads after a sync)
   size_t rig_diff_cap = 0;
   bool rig_overlap_uploads = true;   // pf_rig_stitch_batch: later waves' second upload beside the compute (pf_rig_set_upload_overlap)
+  bool tiff_inflate = false;         // pf_tiff_decode*: deflate strips decode on the device (pf_tiff_set_inflate); off: they are refused
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;
   std::vector<ProfPending> prof_pending;

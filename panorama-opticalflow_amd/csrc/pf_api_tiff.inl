@@ -2,6 +2,8 @@
 // uploads the file's bytes and its strip tables; the strips decode in kernels_tiff.hip, one workgroup each, and one workgroup per row
 // undoes the predictor and stores BGRA.  Only the compressed file crosses the link.  The scratch ("tiff_*") is the decoder's own: no
 // entry point here touches the chain, the prefetch records, the batch slots, the plans or what pf_stitch_visualize reads.
+// Deflate files are refused unless the context's switch is on (pf_tiff_set_inflate); then their strips go to k_tiff_inflate, and a
+// deflate strip is bad when it is short OR carries a reason (a wrong Adler-32 is full and wrong).
 }  // extern "C"
 namespace {
 
@@ -10,6 +12,12 @@ const char* tiff_reason(unsigned r) {
     case kTiffBadCode: return "an LZW code the encoder cannot have produced";
     case kTiffBadTableFull: return "an LZW code beyond the full table";
     case kTiffCutPacket: return "a PackBits packet runs past the strip";
+    case kTiffZlibHeader: return "a bad zlib header";
+    case kTiffBlockHeader: return "a bad deflate block header";
+    case kTiffCodeLengths: return "a bad deflate code lengths set";
+    case kTiffInvalidSymbol: return "an invalid deflate symbol";
+    case kTiffFarBack: return "a deflate distance too far back";
+    case kTiffDataCheck: return "the Adler-32 does not match";
     default: return "the stream ends early";
   }
 }
@@ -22,8 +30,9 @@ int tiff_check_file(pf_ctx* c, int k, const uint8_t* file, size_t bytes, int col
   if (!tiff_parse::parse(file, bytes, info, &why)) return fail(c, PF_ERR_ARG, "tiff: file %d: %s", k, why.c_str());
   const tiff_parse::Info& f = *info;
   if ((long long)f.cols != cols || (long long)f.rows != rows) return fail(c, PF_ERR_ARG, "tiff: file %d is %u x %u, the caller expects %d x %d", k, f.cols, f.rows, cols, rows);
-  if (f.compression == 8 || f.compression == 32946) return fail(c, PF_ERR_ARG, "tiff: file %d is deflate-compressed (compression %u), which the device does not decode; use the host reader", k, f.compression);
-  if (!tiff_parse::device_decodable(f)) return fail(c, PF_ERR_ARG, "tiff: file %d is not device-decodable (compression %u, %u rows per strip)", k, f.compression, f.rows_per_strip);
+  const bool deflate = f.compression == 8 || f.compression == 32946;
+  if (deflate && !c->tiff_inflate) return fail(c, PF_ERR_ARG, "tiff: file %d is deflate-compressed (compression %u), which the device does not decode; use the host reader", k, f.compression);
+  if (!(deflate ? tiff_parse::device_decodable_with_inflate(f) : tiff_parse::device_decodable(f))) return fail(c, PF_ERR_ARG, "tiff: file %d is not device-decodable (compression %u, %u rows per strip)", k, f.compression, f.rows_per_strip);
   if (f.compression == 1)   // known from the tables alone: no kernel needs to find it
     for (size_t s = 0; s < f.n_strips(); ++s)
       if (f.counts[s] < f.strip_bytes(s)) return fail(c, PF_ERR_ARG, "tiff: file %d: strip %zu is short: %u of %llu bytes", k, s, f.counts[s], (unsigned long long)f.strip_bytes(s));
@@ -64,6 +73,7 @@ int tiff_decode_group(pf_ctx* c, int n, const uint8_t* const* files, const size_
     w.plane = d_plane + plane_at[k]; w.status = d_status + status_at[k];
     if (f.compression == 5) { PROF(c, sm, "tiff_lzw"); launch_tiff_lzw(sm, w); }
     else if (f.compression == 32773) { PROF(c, sm, "tiff_packbits"); launch_tiff_packbits(sm, w); }
+    else if (f.compression == 8 || f.compression == 32946) { PROF(c, sm, "tiff_inflate"); launch_tiff_inflate(sm, w); }
     { PROF(c, sm, "tiff_finish"); launch_tiff_finish(sm, w, f.compression == 1, d_out[k]); }
   }
   std::vector<unsigned long long> status(strips_total);
@@ -75,7 +85,8 @@ int tiff_decode_group(pf_ctx* c, int n, const uint8_t* const* files, const size_
     if (f.compression == 1) continue;
     for (size_t s = 0; s < f.n_strips(); ++s) {
       const unsigned long long st = status[status_at[k] + s];
-      if ((st & 0xffffffffull) == f.strip_bytes(s)) continue;
+      // a deflate strip is also bad when it is full and zlib refuses it (a wrong Adler-32, an error behind the last byte)
+      if ((st & 0xffffffffull) == f.strip_bytes(s) && !((f.compression == 8 || f.compression == 32946) && (st >> 32))) continue;
       c->drained = false;
       for (int q = -done; q < n; ++q) HIPCHK(c, hipMemsetAsync(d_out[q], 0, size_t(cols) * rows * 4, sm));
       if (int e = finish(c)) return e;
@@ -112,6 +123,21 @@ int pf_tiff_probe(pf_ctx* c, const uint8_t* file, size_t bytes, pf_tiff_info* ou
   out->rows_per_strip = (int)f.rows_per_strip; out->n_strips = (int)f.n_strips(); out->big_endian = f.big_endian ? 1 : 0;
   out->device_decodable = (tiff_parse::device_decodable(f) && (double)f.cols * f.rows <= 2.0e9) ? 1 : 0;
   return 0;
+}
+
+int pf_tiff_set_inflate(pf_ctx* c, int on) {
+  if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
+  c->tiff_inflate = on != 0;
+  return 0;
+}
+
+int pf_tiff_device_decodable(const pf_ctx* c, const pf_tiff_info* info) {
+  if (!info || info->struct_size != (int)sizeof(pf_tiff_info) || info->cols <= 0 || info->rows <= 0 || info->rows_per_strip <= 0) return 0;
+  tiff_parse::Info f;
+  f.cols = (uint32_t)info->cols; f.rows = (uint32_t)info->rows; f.samples = (uint32_t)info->samples; f.compression = (uint32_t)info->compression;
+  f.rows_per_strip = (uint32_t)info->rows_per_strip;
+  const bool ok = (c && c->tiff_inflate) ? tiff_parse::device_decodable_with_inflate(f) : tiff_parse::device_decodable(f);
+  return (ok && (double)f.cols * f.rows <= 2.0e9) ? 1 : 0;
 }
 
 int pf_tiff_decode_dev(pf_ctx* c, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* d_out_bgra) {

@@ -249,12 +249,20 @@ void launch_png_filter(hipStream_t st, const uint8_t* bgra /* packed, 4-byte ali
 void launch_png_deflate(hipStream_t st, int cols, int rows, const PngWork& w);   // stream -> slots, sizes, adler
 void launch_png_pack(hipStream_t st, int cols, int rows, const PngWork& w);      // sizes -> offs; slots -> packed
 
-// ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits), then predictor + RGB(A) -> BGRA per row ----
+// ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits, deflate), then predictor + RGB(A) -> BGRA per row ----
 // A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled
 // the strip; the strip is good when the low half equals its expected bytes).
 constexpr unsigned kTiffBadCode = 1;        // LZW: a code above the table's next entry, or a non-literal first code after a Clear
 constexpr unsigned kTiffBadTableFull = 2;   // LZW: code == next with the table full
 constexpr unsigned kTiffCutPacket = 3;      // PackBits: a packet runs past the strip's bytes
+// deflate strips (opt-in, pf_tiff_set_inflate): the classes of zlib's own refusals.  A deflate strip is good when the low half equals
+// its expected bytes AND the reason is 0 (a wrong Adler-32 is full and wrong).
+constexpr unsigned kTiffZlibHeader = 4;     // CM, CINFO, FCHECK, a preset dictionary
+constexpr unsigned kTiffBlockHeader = 5;    // block type 3, stored LEN != ~NLEN
+constexpr unsigned kTiffCodeLengths = 6;    // too many symbols, a bad repeat, an over-subscribed or incomplete set, no end-of-block code
+constexpr unsigned kTiffInvalidSymbol = 7;  // literal/length 286-287, distance 30-31, bits no code of an incomplete set spells
+constexpr unsigned kTiffFarBack = 8;        // a distance that reaches before the strip's first byte
+constexpr unsigned kTiffDataCheck = 9;      // the Adler-32 does not match the bytes written
 struct TiffWork {
   const uint8_t* file;         // the uploaded file bytes
   unsigned long long bytes;    // ... and how many
@@ -266,6 +274,7 @@ struct TiffWork {
 };
 void launch_tiff_lzw(hipStream_t st, const TiffWork& w);        // file -> plane, status
 void launch_tiff_packbits(hipStream_t st, const TiffWork& w);   // file -> plane, status
+void launch_tiff_inflate(hipStream_t st, const TiffWork& w);    // file -> plane, status
 void launch_tiff_finish(hipStream_t st, const TiffWork& w, bool from_file /* compression 1: samples read from the file */, uint8_t* bgra /* packed, 4-byte aligned */);
 
 }  // namespace pf

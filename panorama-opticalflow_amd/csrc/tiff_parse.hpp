@@ -124,6 +124,13 @@ inline bool device_decodable(const Info& f) {
   return uint64_t(f.rows_per_strip) * f.row_bytes() < (uint64_t(1) << 31);
 }
 
+// the same with the decoder's inflate switch on (pf_tiff_set_inflate): deflate strips (8, and 32946 of older writers) join, under the
+// same strip-size limit
+inline bool device_decodable_with_inflate(const Info& f) {
+  if (f.compression != 8 && f.compression != 32946) return device_decodable(f);
+  return uint64_t(f.rows_per_strip) * f.row_bytes() < (uint64_t(1) << 31);
+}
+
 // LZW code geometry (TIFF flavour, early change).  Code j (j = 0 is the first code after a Clear, or the first code of the strip) is
 // read while the table holds min(4096, 258 + max(0, j - 1)) entries; the width steps up after the codes that bring the table to 511,
 // 1023 and 2047 entries, which are j = 253, 765 and 1789.  So the width and the bit offset are closed functions of j alone.

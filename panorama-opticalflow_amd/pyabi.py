@@ -107,6 +107,8 @@ def lib(exp=False):
         _lib.pf_png_segment_bytes.restype = C.c_size_t
         _lib.pf_png_segment_bytes.argtypes = []
         _lib.pf_tiff_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TiffInfo)]
+        _lib.pf_tiff_set_inflate.argtypes = [C.c_void_p, C.c_int]
+        _lib.pf_tiff_device_decodable.argtypes = [C.c_void_p, C.POINTER(TiffInfo)]
         _lib.pf_tiff_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         _lib.pf_tiff_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         _lib.pf_tiff_decode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -130,7 +132,7 @@ EXPORTS = [
     "pf_stage_preprocess_batch", "pf_stage_pyramid", "pf_stage_adjust_initial_flow_batch", "pf_stage_intensity_ratio",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_png_bound", "pf_png_segment_bytes", "pf_png_encode_dev", "pf_png_encode", "pf_png_encode_batch_dev", "pf_stitch_result_png", "pf_stitch_batch_result_png",
-    "pf_tiff_probe", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
+    "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -170,6 +172,11 @@ def tiff_probe(data):
     if lib().pf_tiff_probe(None, _p(buf), C.c_size_t(len(data)), C.byref(info)) != 0:
         raise PanoflowError(lib().pf_last_error(None).decode())
     return info
+
+
+def tiff_device_decodable(info, ctx=None):
+    """would the decode calls of `ctx` (a Context; None: default settings) take the probed file?  (pf_tiff_device_decodable)"""
+    return bool(lib().pf_tiff_device_decodable(ctx.h if ctx is not None else None, C.byref(info)))
 
 
 def png_segment_bytes():
@@ -583,6 +590,10 @@ class Context:
         return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
 
     # ---- TIFF files decoded on the device (pf_tiff_*): `data` = the file's bytes ----
+    def tiff_set_inflate(self, on):
+        """on: this context's tiff_decode* calls also take deflate files (pf_tiff_set_inflate; default off: they are refused)"""
+        self._chk(self.l.pf_tiff_set_inflate(self.h, int(bool(on))))
+
     def tiff_decode(self, data, shape=None, row_step=None, out=None):
         """file bytes -> host BGRA (rows, cols, 4); shape = (rows, cols) the caller expects (default: the probe's).  row_step (bytes) or
         out (an array whose rows are row_step apart) selects a padded destination; the padding is left as it is"""

@@ -257,10 +257,12 @@ static inline bool is_tiff_name(const std::string& path) {
 // The device rule: a file goes to the device when the library can decode it there (no compression, LZW, PackBits) and it either is
 // uncompressed or has at least 64 strips -- the strips are what runs in parallel; a single LZW strip is one serial stream and stays with
 // the host.  Everything else (deflate, few strips, anything the probe refuses) goes to read_tiff, which also words the refusals.
+// The context's own settings decide what "can decode": with its inflate switch on (pf_tiff_set_inflate, which the caller sets where it
+// makes the context) deflate files fall under the rule LZW files do.
 static inline bool tiff_goes_to_device(pf_ctx* ctx, const std::vector<unsigned char>& b, pf_tiff_info* info) {
   info->struct_size = (int)sizeof *info;
   if (pf_tiff_probe(ctx, b.data(), b.size(), info) != 0) return false;
-  return info->device_decodable && (info->compression == 1 || info->n_strips >= 64);
+  return pf_tiff_device_decodable(ctx, info) && (info->compression == 1 || info->n_strips >= 64);
 }
 // imreadExceptionOnFail with -tiff_device 1: the same pixels; a .tif under the device rule is decoded on the GPU into the host image
 static inline Mat imread_device(const std::string& path, pf_ctx* ctx) {

@@ -33,6 +33,9 @@
 //   (pf_rig_plan_create_dev) and the chains run through pf_rig_stitch_batch_dev; with -png_device 1 as well each composite is encoded
 //   where it lies, so no raw image crosses the link in either direction; without it the composites are downloaded and written by the
 //   default writer.
+//   -tiff_inflate 1 (with -tiff_device 1; off by default): deflate TIFFs (compression 8 / 32946) fall under the same rule as LZW ones --
+//   at least 64 strips -- through the library's inflate switch (pf_tiff_set_inflate).  A strip is accepted exactly when zlib's uncompress
+//   into the strip's size succeeds or ends with Z_BUF_ERROR and the strip full; a short or malformed strip ends the run.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -58,9 +61,18 @@ static void writeImage(const std::string& path, const Mat& image) {
   else pano_io::imwriteExceptionOnFail(path, image);
 }
 static bool g_tiff_device = false;   // -tiff_device 1
+static bool g_tiff_inflate = false;  // -tiff_inflate 1
+// the context the device readers decode with: the process's one context (this program is single-threaded), its inflate switch set once,
+// when the first reader asks for it -- after every refusal of the command line
+static pf_ctx* tiffContext() {
+  pf_ctx* ctx = pano::context();
+  static bool set = false;
+  if (!set) { pano::check(pf_tiff_set_inflate(ctx, g_tiff_inflate ? 1 : 0)); set = true; }
+  return ctx;
+}
 // an image file to a host image, by the host readers or (a .tif under the device rule, see the usage note) through the device decoder
 static Mat readImage(const std::string& path) {
-  return g_tiff_device ? pano_io::imread_device(path, pano::context()) : pano_io::imreadExceptionOnFail(path);
+  return g_tiff_device ? pano_io::imread_device(path, tiffContext()) : pano_io::imreadExceptionOnFail(path);
 }
 
 static std::map<std::string, std::string> parseFlags(int argc, char** argv) {   // gflags syntax: -name value | --name=value
@@ -273,7 +285,7 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
   if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + flow_alg);
   if (nsteps < 1 || nsteps > 9) throw VrCamException("-rig_chain: -steps must be 1..9");
   double StartTime = getCurrTimeSec();
-  pf_ctx* ctx = pano::context();
+  pf_ctx* ctx = tiffContext();
   const int n = (int)dirs.size();
   struct DevImages {   // frees what was allocated, however the run ends
     pf_ctx* ctx; std::vector<uint8_t*> p;
@@ -336,6 +348,7 @@ int main(int argc, char** argv) {
     auto flags = parseFlags(argc, argv);
     g_png_device = flags.count("png_device") && atoi(flags["png_device"].c_str()) != 0;
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
+    g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
       if (flags.count("test_dir")) throw VrCamException("-test_dirs and -test_dir are exclusive");
       const bool static_rig = flags.count("static_rig") && atoi(flags["static_rig"].c_str()) != 0;
