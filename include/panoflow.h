@@ -483,6 +483,40 @@ int pf_png_encode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_bgra, in
 int pf_stitch_result_png(pf_ctx* ctx, uint8_t* png_out, size_t cap, size_t* size_out);
 int pf_stitch_batch_result_png(pf_ctx* ctx, int frame, uint8_t* png_out, size_t cap, size_t* size_out);
 
+/* ---- JPEG files made on the device ------------------------------------------------------------
+ * A baseline sequential JPEG (SOF0, 8 bits, Y Cb Cr, JFIF 1.01, Annex K's Huffman tables) of a packed BGRA image; alpha is dropped
+ * and the colour bytes are encoded as stored.  Any size pf_png_encode_dev accepts up to the format's 65535 a side, any width (the
+ * 3 * cols panels included).  The colour transform, libjpeg's integer DCT, quantisation and the entropy coder run in kernels on the
+ * device; only the finished entropy-coded segment crosses the link, into its place in jpg_out (HOST memory) behind
+ * the header the library writes.  Opt-in: no other entry point's behaviour depends on these.  The bytes are a function of the image
+ * and the three parameters alone, and with gpano == 0 they are the file libjpeg writes for that image at that quality and
+ * subsampling with a restart interval of pf_jpeg_restart_interval(subsampling) MCUs.
+ *   params    NULL: the defaults pf_jpeg_params_init sets.  quality 1..100 (default 90); subsampling 0 = 4:4:4, 1 = 4:2:0
+ *             (default); gpano 1: an APP1 segment directly behind APP0 holds an XMP packet that declares the image a full
+ *             equirectangular sphere (GPano:ProjectionType, UsePanoramaViewer, the full and cropped sizes = the image's, left and top
+ *             0), for which the image must be 2:1 -- removing that segment gives the gpano == 0 file exactly.  Anything else is
+ *             PF_ERR_ARG, as is a side above 65535.
+ *   cap       bytes jpg_out holds.  A file larger than cap is PF_ERR_ARG: nothing is written and *size_out receives the size
+ *             needed (the batch form: cap_each per file, every sizes_out[k] set).  pf_jpeg_bound(cols, rows, params) always suffices
+ *             (it is a worst case, about 20 bytes per pixel at 4:4:4; 0 for a shape or subsampling the encoder refuses).
+ *   _dev, batch, pf_stitch_result_jpeg, pf_stitch_batch_result_jpeg: as the PNG family's. */
+typedef struct pf_jpeg_params {
+  int struct_size;   /* sizeof(pf_jpeg_params), set by pf_jpeg_params_init */
+  int quality;
+  int subsampling;
+  int gpano;
+} pf_jpeg_params;
+void pf_jpeg_params_init(pf_jpeg_params* params);
+size_t pf_jpeg_bound(int cols, int rows, const pf_jpeg_params* params);
+int pf_jpeg_restart_interval(int subsampling);   /* MCUs per restart interval; 0 for an unknown subsampling */
+int pf_jpeg_encode_dev(pf_ctx* ctx, const uint8_t* d_bgra, int cols, int rows, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap, size_t* size_out);
+int pf_jpeg_encode(pf_ctx* ctx, const uint8_t* bgra, size_t step_bytes, int cols, int rows, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap,
+                   size_t* size_out);
+int pf_jpeg_encode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_bgra, int cols, int rows, const pf_jpeg_params* params, uint8_t* const* jpg_out,
+                             size_t cap_each, size_t* sizes_out);
+int pf_stitch_result_jpeg(pf_ctx* ctx, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap, size_t* size_out);
+int pf_stitch_batch_result_jpeg(pf_ctx* ctx, int frame, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap, size_t* size_out);
+
 /* ---- TIFF files decoded on the device ----------------------------------------------------------
  * The counterpart of the PNG encoder: the bytes of a TIFF file (HOST memory) go up as they are, the strips decode in parallel on the
  * device (one workgroup per strip: LZW -- compression 5 -- and PackBits -- 32773 --; uncompressed strips are read in place), the

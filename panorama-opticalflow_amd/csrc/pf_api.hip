@@ -18,12 +18,13 @@
 #include "../../include/panoflow.h"
 #include "pf_common.hpp"
 #include "png_frame.hpp"
+#include "jpeg_frame.hpp"
 #include "tiff_parse.hpp"
 
 using namespace pf;
 
 
-// One translation unit in nine parts (the anonymous namespace and the extern "C" block span several of them):
+// One translation unit in ten parts (the anonymous namespace and the extern "C" block span several of them):
 #include "pf_api_ctx.inl"      // pf_ctx, errors / warnings, arena, profiling events, geometry, checks
 #include "pf_api_solve.inl"    // run_level, solve buffers, solve / solve_n (stream orchestration)
 #include "pf_api_life.inl"     // finish / CallGuard, pf_create* / pf_destroy, memory helpers            (opens extern "C")
@@ -33,5 +34,6 @@ using namespace pf;
 #include "pf_api_vis.inl"      // pf_vis_*, pf_stitch_visualize (flow visualisers)
 #include "pf_api_png.inl"      // pf_png_*, pf_stitch_result_png (PNG files made on the device)
 #include "pf_api_tiff.inl"     // pf_tiff_* (TIFF files decoded on the device)
+#include "pf_api_jpeg.inl"     // pf_jpeg_*, pf_stitch_result_jpeg (JPEG files made on the device)
 }  // extern "C"
 

@@ -249,6 +249,18 @@ void launch_png_filter(hipStream_t st, const uint8_t* bgra /* packed, 4-byte ali
 void launch_png_deflate(hipStream_t st, int cols, int rows, const PngWork& w);   // stream -> slots, sizes, adler
 void launch_png_pack(hipStream_t st, int cols, int rows, const PngWork& w);      // sizes -> offs; slots -> packed
 
+// ---- JPEG encoder (kernels_jpeg.hip): blocks, the entropy coder's size pass, a scan, its write pass; the host frames (jpeg_frame.hpp) ----
+struct JpegWork {
+  int16_t* coef;              // jpeg_frame::coef_bytes(): 64 int16 per block in MCU order
+  const void* tables;         // a jpeg_frame::Tables in device memory
+  unsigned* sizes;            // per restart interval: its bytes, stuffing and marker included
+  unsigned long long* offs;   // intervals + 1: exclusive prefix sums of sizes; the last is the segment's length
+};
+bool jpeg_restart_fits(int subsampling, int restart);   // can the entropy kernel's workgroup hold an interval of `restart` MCUs?
+void launch_jpeg_blocks(hipStream_t st, const uint8_t* bgra /* packed, 4-byte aligned */, int cols, int rows, int subsampling, const JpegWork& w);   // bgra -> coef
+void launch_jpeg_sizes(hipStream_t st, int cols, int rows, int subsampling, int restart, const JpegWork& w);                                          // coef -> sizes, offs
+void launch_jpeg_write(hipStream_t st, int cols, int rows, int subsampling, int restart, const JpegWork& w, uint8_t* packed /* offs[intervals] bytes */);
+
 // ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits, deflate), then predictor + RGB(A) -> BGRA per row ----
 // A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled
 // the strip; the strip is good when the low half equals its expected bytes).

@@ -54,6 +54,11 @@ class SolverParams(C.Structure):
                 ("directional_regularization_coef", C.c_float)]
 
 
+class JpegParams(C.Structure):
+    """pf_jpeg_params (include/panoflow.h)"""
+    _fields_ = [("struct_size", C.c_int), ("quality", C.c_int), ("subsampling", C.c_int), ("gpano", C.c_int)]
+
+
 class TiffInfo(C.Structure):
     """pf_tiff_info (include/panoflow.h)"""
     _fields_ = [(n, C.c_int) for n in ("struct_size", "cols", "rows", "samples", "compression", "predictor", "rows_per_strip", "n_strips", "big_endian",
@@ -106,6 +111,16 @@ def lib(exp=False):
         _lib.pf_png_bound.argtypes = [C.c_int, C.c_int]
         _lib.pf_png_segment_bytes.restype = C.c_size_t
         _lib.pf_png_segment_bytes.argtypes = []
+        _lib.pf_jpeg_params_init.restype = None
+        _lib.pf_jpeg_params_init.argtypes = [C.POINTER(JpegParams)]
+        _lib.pf_jpeg_bound.restype = C.c_size_t
+        _lib.pf_jpeg_bound.argtypes = [C.c_int, C.c_int, C.POINTER(JpegParams)]
+        _lib.pf_jpeg_restart_interval.argtypes = [C.c_int]
+        _lib.pf_jpeg_encode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(JpegParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.pf_jpeg_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(JpegParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.pf_jpeg_encode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(JpegParams), C.c_void_p, C.c_size_t, C.c_void_p]
+        _lib.pf_stitch_result_jpeg.argtypes = [C.c_void_p, C.POINTER(JpegParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        _lib.pf_stitch_batch_result_jpeg.argtypes = [C.c_void_p, C.c_int, C.POINTER(JpegParams), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib.pf_tiff_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TiffInfo)]
         _lib.pf_tiff_set_inflate.argtypes = [C.c_void_p, C.c_int]
         _lib.pf_tiff_device_decodable.argtypes = [C.c_void_p, C.POINTER(TiffInfo)]
@@ -132,6 +147,8 @@ EXPORTS = [
     "pf_stage_preprocess_batch", "pf_stage_pyramid", "pf_stage_adjust_initial_flow_batch", "pf_stage_intensity_ratio",
     "pf_vis_grey_disparity", "pf_vis_color_wheel", "pf_vis_vector_field", "pf_vis_panel", "pf_vis_panel_dev", "pf_stitch_visualize",
     "pf_png_bound", "pf_png_segment_bytes", "pf_png_encode_dev", "pf_png_encode", "pf_png_encode_batch_dev", "pf_stitch_result_png", "pf_stitch_batch_result_png",
+    "pf_jpeg_params_init", "pf_jpeg_bound", "pf_jpeg_restart_interval", "pf_jpeg_encode_dev", "pf_jpeg_encode", "pf_jpeg_encode_batch_dev",
+    "pf_stitch_result_jpeg", "pf_stitch_batch_result_jpeg",
     "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
@@ -163,6 +180,26 @@ def max_percentage_by_name(name):
 def png_bound(cols, rows):
     """capacity that holds the PNG of any cols x rows image (pf_png_bound)"""
     return int(lib().pf_png_bound(cols, rows))
+
+
+def jpeg_params(quality=None, subsampling=None, gpano=None):
+    """a JpegParams with the library's defaults (pf_jpeg_params_init) and the given fields over them"""
+    p = JpegParams()
+    lib().pf_jpeg_params_init(C.byref(p))
+    for name, v in (("quality", quality), ("subsampling", subsampling), ("gpano", gpano)):
+        if v is not None:
+            setattr(p, name, int(v))
+    return p
+
+
+def jpeg_bound(cols, rows, params=None):
+    """capacity that holds the JPEG of any cols x rows image (pf_jpeg_bound); 0 for a shape the encoder refuses"""
+    return int(lib().pf_jpeg_bound(cols, rows, C.byref(params) if params is not None else None))
+
+
+def jpeg_restart_interval(subsampling):
+    """MCUs per restart interval of the device JPEG encoder (pf_jpeg_restart_interval)"""
+    return int(lib().pf_jpeg_restart_interval(subsampling))
 
 
 def tiff_probe(data):
@@ -588,6 +625,50 @@ class Context:
         """the PNG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
         rows, cols = shape
         return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
+
+    # ---- JPEG files made on the device (pf_jpeg_*): every method returns the file as bytes; params = a JpegParams or None (defaults) ----
+    def _jpeg_call(self, cols, rows, params, call, cap=None):
+        """call(params_ref, buffer, cap, size_ref) -> rc.  cap=None: pf_jpeg_bound.  A short buffer raises PngCapacityError carrying the needed size."""
+        pr = C.byref(params) if params is not None else None
+        cap = int(self.l.pf_jpeg_bound(cols, rows, pr)) if cap is None else int(cap)
+        buf = np.empty(max(cap, 1), np.uint8); size = C.c_size_t(0)
+        rc = call(pr, _p(buf), C.c_size_t(cap), C.byref(size))
+        if rc != 0 and 0 < cap < size.value:
+            raise PngCapacityError("panoflow error %d: %s" % (rc, self.l.pf_last_error(self.h).decode()), size.value)
+        self._chk(rc)
+        return buf[:size.value].tobytes()
+
+    def jpeg_encode(self, image, params=None, cap=None):
+        """host BGRA (rows, cols, 4) array, any row stride -> JPEG file bytes"""
+        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+        if a.strides[2] != 1 or a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_jpeg_encode(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, pr, b, c, s), cap)
+
+    def jpeg_encode_dev(self, d_bgra, cols, rows, params=None, cap=None):
+        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_jpeg_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, pr, b, c, s), cap)
+
+    def jpeg_encode_batch_dev(self, d_bgra, cols, rows, params=None):
+        """n same-size device images -> list of n files"""
+        n = len(d_bgra)
+        pr = C.byref(params) if params is not None else None
+        cap = int(self.l.pf_jpeg_bound(cols, rows, pr))
+        bufs = [np.empty(max(cap, 1), np.uint8) for _ in range(n)]
+        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_bgra]); outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+        sizes = (C.c_size_t * n)()
+        self._chk(self.l.pf_jpeg_encode_batch_dev(self.h, n, srcs, cols, rows, pr, outs, C.c_size_t(cap), sizes))
+        return [bufs[k][:sizes[k]].tobytes() for k in range(n)]
+
+    def stitch_result_jpeg(self, params=None, shape=None, cap=None):
+        """the JPEG of the composite the last stitch_step left in HBM; shape = (rows, cols) of that step (default: the last stitch_step made
+        through this object), used only to size the buffer"""
+        rows, cols = shape if shape is not None else getattr(self, "_step_shape", (1, 1))
+        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_stitch_result_jpeg(self.h, pr, b, c, s), cap)
+
+    def stitch_batch_result_jpeg(self, frame, shape, params=None, cap=None):
+        """the JPEG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
+        rows, cols = shape
+        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_stitch_batch_result_jpeg(self.h, frame, pr, b, c, s), cap)
 
     # ---- TIFF files decoded on the device (pf_tiff_*): `data` = the file's bytes ----
     def tiff_set_inflate(self, on):

@@ -4,6 +4,7 @@
 //     Deflate / PackBits, predictor 1 or 2.  Tiles, 16-bit, palette and planar files are rejected with a message.
 //   * PNG reader/writer: 8-bit RGB/RGBA, non-interlaced (zlib).
 //   * write_png_device: the same pixels as a PNG the library makes on the GPU (pf_png_*); only the finished file comes to the host.
+//   * write_jpeg_device: a result as a baseline JPEG the library makes on the GPU (pf_jpeg_*).
 //   * imread_device / imread_to_device: a TIFF's strips decoded on the GPU (pf_tiff_*); only the file's bytes go up.  read_tiff stays
 //     the behaviour model and the fallback (deflate files, files of few strips).
 // Pixels are delivered as BGRA (CV_8UC4) like cv::imread(-1) followed by the reference's BGR->BGRA (main.cpp:58,68).
@@ -204,6 +205,38 @@ static inline void write_png_device(const std::string& path, pf_ctx* ctx, int co
 // frame slot `frame` of the last host-form pf_stitch_step_batch* call
 static inline void write_png_device(const std::string& path, pf_ctx* ctx, int frame, int cols, int rows) {
   write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_stitch_batch_result_png(ctx, frame, b, cap, n); });
+}
+// JPEG made on the device (include/panoflow.h, "JPEG files made on the device"): the same shape as write_png_bytes.  `encode(buf, cap,
+// &size)` is one of the pf_*_jpeg calls bound to its source image and parameters.  There is no host JPEG writer here.
+template <class Encode>
+static inline void write_jpeg_bytes(const std::string& path, pf_ctx* ctx, int cols, int rows, const pf_jpeg_params& params, Encode encode) {
+  const size_t cap = pf_jpeg_bound(cols, rows, &params);
+  if (!cap) throw VrCamException("a JPEG cannot hold this image (a side above 65535?): " + path);
+  std::unique_ptr<unsigned char[]> buf(new unsigned char[cap]);   // a worst case, never touched beyond the file's size
+  size_t size = 0;
+  if (encode(buf.get(), cap, &size) != 0) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) throw VrCamException("failed to write image: " + path);
+  const bool ok = fwrite(buf.get(), 1, size, f) == size;
+  if (fclose(f) != 0 || !ok) throw VrCamException("failed to write image: " + path);
+}
+// a host image (any row step): uploaded, encoded on the device
+static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const pf_jpeg_params& params, const Mat& bgra) {
+  if (bgra.type() != panocv::CV_8UC4) throw VrCamException("write_jpeg_device expects CV_8UC4");
+  write_jpeg_bytes(path, ctx, bgra.cols, bgra.rows, params,
+                   [&](unsigned char* b, size_t cap, size_t* n) { return pf_jpeg_encode(ctx, bgra.data, bgra.step, bgra.cols, bgra.rows, &params, b, cap, n); });
+}
+// the composite the last pf_stitch_step left in HBM (cols x rows: that step's size); no raw image crosses the link
+static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const pf_jpeg_params& params, int cols, int rows) {
+  write_jpeg_bytes(path, ctx, cols, rows, params, [&](unsigned char* b, size_t cap, size_t* n) { return pf_stitch_result_jpeg(ctx, &params, b, cap, n); });
+}
+// frame slot `frame` of the last host-form pf_stitch_step_batch* call
+static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const pf_jpeg_params& params, int frame, int cols, int rows) {
+  write_jpeg_bytes(path, ctx, cols, rows, params, [&](unsigned char* b, size_t cap, size_t* n) { return pf_stitch_batch_result_jpeg(ctx, frame, &params, b, cap, n); });
+}
+// a packed device image
+static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const pf_jpeg_params& params, const unsigned char* d_bgra, int cols, int rows) {
+  write_jpeg_bytes(path, ctx, cols, rows, params, [&](unsigned char* b, size_t cap, size_t* n) { return pf_jpeg_encode_dev(ctx, d_bgra, cols, rows, &params, b, cap, n); });
 }
 static inline Mat read_png(const std::string& path) {
   const std::vector<unsigned char> b = read_file(path);

@@ -25,6 +25,11 @@
 //   HBM (pf_stitch_result_png / pf_stitch_batch_result_png) and bring no raw composite down (-static_rig 1: only the first directory's,
 //   which the next plan is made from); -rig_chain 1, -inputs 4, -fused 0 and the -visualize panels hold their images on the host and
 //   send them up to be encoded (pf_png_encode).
+//   -jpeg_device 1 [-jpeg_quality Q] [-jpeg_subsampling 444|420] [-jpeg_gpano 1] (any mode; off by default): the results are written as
+//   ProcessResult{i}.jpg and FinalResult.jpg IN PLACE OF the .png, baseline JPEGs made on the GPU (pf_jpeg_*: quality 1..100, default 90;
+//   4:2:0 by default; -jpeg_gpano 1 adds the GPano XMP packet that makes a 2:1 result open as a sphere, and ends the run on any other
+//   shape), encoded where -png_device 1 would encode them: in HBM where the composite lies there, sent up from the host otherwise.  The
+//   -visualize panels stay PNG (by the default writer, or with -png_device 1 as well by the device PNG encoder).
 //   -tiff_device 1 (any mode; off by default): a .tif input is decoded on the GPU (pf_tiff_*) when the library can decode it there -- no
 //   compression, LZW or PackBits -- and it is uncompressed or has at least 64 strips (strips decode in parallel; a single LZW strip is one
 //   serial stream and stays with the host).  Every other file, deflate TIFFs included, goes through the host reader as before.  The
@@ -59,6 +64,13 @@ static bool g_png_device = false;   // -png_device 1
 static void writeImage(const std::string& path, const Mat& image) {
   if (g_png_device) pano_io::write_png_device(path, pano::context(), image);
   else pano_io::imwriteExceptionOnFail(path, image);
+}
+static bool g_jpeg_device = false;   // -jpeg_device 1: the results (not the panels) as JPEGs made on the device
+static pf_jpeg_params g_jpeg;
+// a host result image to <stem>.png, or with -jpeg_device 1 to <stem>.jpg
+static void writeResult(const std::string& stem, const Mat& image) {
+  if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, image);
+  else writeImage(stem + ".png", image);
 }
 static bool g_tiff_device = false;   // -tiff_device 1
 static bool g_tiff_inflate = false;  // -tiff_inflate 1
@@ -146,7 +158,7 @@ static int run4Input(const std::string& dir, const std::string& flow_alg) {
       colorImageR.ptr<unsigned char>(y)[x] = (unsigned char)(r > 255 ? 255 : r);
     }
   Mat FinalResult = stitchStep(colorImageL, &colorImageR, flow_alg);
-  writeImage(dir + "/FinalResult.png", FinalResult);
+  writeResult(dir + "/FinalResult", FinalResult);
   std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
   return EXIT_SUCCESS;
 }
@@ -186,7 +198,7 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
       if (!same(Ls[k]) || (i == 1 && !same(tops[k])))
         throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
       // -png_device: the composites stay in their frame slots and are encoded there; only the one the next plan needs comes down
-      const bool want = !g_png_device || (static_rig && k == 0);
+      const bool want = !(g_png_device || g_jpeg_device) || (static_rig && k == 0);
       outs[k] = want ? Mat(Ls[0].rows, Ls[0].cols, CV_8UC4) : Mat();
       l[k] = Ls[k].data; r[k] = tops[k].data; o[k] = want ? outs[k].data : nullptr;
     }
@@ -213,9 +225,10 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
                                      o.data(), ostep, in_flight));
     prev0 = outs[0];
     for (int k = 0; k < n; ++k) {
-      const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
-      if (g_png_device) pano_io::write_png_device(path, pano::context(), k, Ls[0].cols, Ls[0].rows);
-      else pano_io::imwriteExceptionOnFail(path, outs[k]);
+      const std::string stem = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
+      if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, k, Ls[0].cols, Ls[0].rows);
+      else if (g_png_device) pano_io::write_png_device(stem + ".png", pano::context(), k, Ls[0].cols, Ls[0].rows);
+      else pano_io::imwriteExceptionOnFail(stem + ".png", outs[k]);
     }
     std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
   }
@@ -269,8 +282,8 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
   for (int k = 0; k < n; ++k)
     for (int i = 1; i <= nsteps; ++i) {
       Mat& o_ki = outs[size_t(k) * nsteps + i - 1];
-      if (i == nsteps) writeImage(dirs[k] + "/" + "FinalResult.png", o_ki);
-      else writeImage(dirs[k] + "/" + "ProcessResult" + char(i + 48) + ".png", o_ki);
+      if (i == nsteps) writeResult(dirs[k] + "/" + "FinalResult", o_ki);
+      else writeResult(dirs[k] + "/" + "ProcessResult" + char(i + 48), o_ki);
       o_ki = Mat();
     }
   std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
@@ -331,7 +344,9 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
     for (int i = 1; i <= nsteps; ++i) {
       const uint8_t* d = o[size_t(k) * nsteps + i - 1];
       const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
-      if (g_png_device) {
+      if (g_jpeg_device) {
+        pano_io::write_jpeg_device(path.substr(0, path.size() - 4) + ".jpg", ctx, g_jpeg, d, cols, rows);
+      } else if (g_png_device) {
         pano_io::write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* size) { return pf_png_encode_dev(ctx, d, cols, rows, b, cap, size); });
       } else {
         Mat m(rows, cols, CV_8UC4);
@@ -347,6 +362,16 @@ int main(int argc, char** argv) {
   try {
     auto flags = parseFlags(argc, argv);
     g_png_device = flags.count("png_device") && atoi(flags["png_device"].c_str()) != 0;
+    g_jpeg_device = flags.count("jpeg_device") && atoi(flags["jpeg_device"].c_str()) != 0;
+    pf_jpeg_params_init(&g_jpeg);
+    if (g_jpeg_device) {   // every refusal before any device call
+      if (flags.count("jpeg_quality")) g_jpeg.quality = atoi(flags["jpeg_quality"].c_str());
+      if (g_jpeg.quality < 1 || g_jpeg.quality > 100) throw VrCamException("-jpeg_quality must be 1..100");
+      const std::string sub = flags.count("jpeg_subsampling") ? flags["jpeg_subsampling"] : "420";
+      if (sub != "444" && sub != "420") throw VrCamException("-jpeg_subsampling must be 444 or 420");
+      g_jpeg.subsampling = sub == "420";
+      g_jpeg.gpano = flags.count("jpeg_gpano") && atoi(flags["jpeg_gpano"].c_str()) != 0;
+    }
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
@@ -393,8 +418,8 @@ int main(int argc, char** argv) {
       if (i == 1) colorImageR = colorImageT; else colorImageR = FinalResult;
       colorImageL = readImage(FLAGS_test_dir + "/" + char(i + 48) + ".tif");
 
-      if (fused && g_png_device) {
-        // the composite stays in HBM (out_bgra = NULL) for the next step to chain on and for the encoder: only its PNG comes down
+      if (fused && (g_png_device || g_jpeg_device)) {
+        // the composite stays in HBM (out_bgra = NULL) for the next step to chain on and for the encoder: only its PNG or JPEG comes down
         const int maxPct = pf_max_percentage_by_name(FLAGS_flow_alg.c_str());
         if (maxPct < 0) throw VrCamException("unrecognized flow algorithm name: " + FLAGS_flow_alg);
         if (colorImageL.type() != CV_8UC4 || (i == 1 && (colorImageR.type() != CV_8UC4 || colorImageR.rows != colorImageL.rows ||
@@ -428,9 +453,10 @@ int main(int argc, char** argv) {
       delete novelViewGen;
       }
 
-      const std::string resultPath = FLAGS_test_dir + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
-      if (fused && g_png_device) pano_io::write_png_device(resultPath, pano::context(), colorImageL.cols, colorImageL.rows);
-      else writeImage(resultPath, FinalResult);
+      const std::string resultStem = FLAGS_test_dir + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
+      if (fused && g_jpeg_device) pano_io::write_jpeg_device(resultStem + ".jpg", pano::context(), g_jpeg, colorImageL.cols, colorImageL.rows);
+      else if (fused && g_png_device) pano_io::write_png_device(resultStem + ".png", pano::context(), colorImageL.cols, colorImageL.rows);
+      else writeResult(resultStem, FinalResult);
       std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
     }
     std::cout << "TotalRunTime (sec) = " << (getCurrTimeSec() - StartTime) << std::endl;
