@@ -557,6 +557,37 @@ int pf_tiff_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int
 int pf_tiff_decode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, int cols, int rows,
                              uint8_t* const* d_out_bgra);
 
+/* ---- Resize on the device --------------------------------------------------------------------
+ * A packed BGRA image at another size, byte for byte what Pillow's Image.resize(size, filter) gives for the same bytes as an RGBA
+ * image (the three colour channels are treated alike, so the channel order does not matter): an antialiased separable resample --
+ * horizontal pass, then vertical -- in 22-bit fixed point, over colour premultiplied by alpha and divided by it again at the end,
+ * so that transparent pixels do not bleed their colour into their neighbours.  An axis whose size stays runs no
+ * pass; out_cols == cols && out_rows == rows is a plain copy.  The coefficient tables are made on the host in double (HAMMING and
+ * LANCZOS through the host's sin / cos: their bytes are scoped to this libm, as the blend's are), kept in the context per (in, out,
+ * filter) and uploaded; the kernels are integer only.  Opt-in: no other entry point's behaviour depends on these.  A result stays
+ * in HBM between the stitch and pf_png_encode_dev / pf_jpeg_encode_dev: chain them.
+ *   filter    one of PF_RESIZE_* (Pillow's numbering); anything else is PF_ERR_ARG.
+ *   _dev      d_src_bgra: cols * rows * 4 bytes, d_dst_bgra: out_cols * out_rows * 4 bytes of this context's device, packed rows,
+ *             4-byte aligned.  A destination that overlaps a source is PF_ERR_ARG.
+ *   pf_resize HOST memory on both sides, row steps in bytes; bytes of a destination row beyond out_cols * 4 are left untouched.
+ *   batch     n same-size images -> the bytes of n single calls, their kernels enqueued together before one drain.
+ *   pf_stitch_result_resized_dev, pf_stitch_batch_result_resized_dev: from the composite the last pf_stitch_step left in HBM, or
+ *             frame slot `frame` of the last pf_stitch_step_batch; PF_ERR_ARG when none is resident, as pf_stitch_result_png.
+ * PF_ERR_ARG with a message also for: null pointers; sizes <= 0; more than 2e9 pixels on either side (or in the intermediate
+ * out_cols x rows plane); an axis whose table exceeds 16 777 216 coefficients, where the table of an axis holds
+ * (2 * ceil(support * max(in / out, 1)) + 1) * out of them (support: 3, 1, 2, 0.5, 1 in the order below) -- every axis up to 2.7
+ * million source or 2.3 million output samples fits.
+ * The scratch is the resize's own: these calls leave alone the chain state, the prefetch records, the frame slots, the plans and
+ * what pf_stitch_visualize reads.  Kernel families in pf_profile_*: resize_h, resize_v. */
+enum { PF_RESIZE_LANCZOS = 1, PF_RESIZE_BILINEAR = 2, PF_RESIZE_BICUBIC = 3, PF_RESIZE_BOX = 4, PF_RESIZE_HAMMING = 5 };
+int pf_resize_dev(pf_ctx* ctx, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* d_dst_bgra, int out_cols, int out_rows, int filter);
+int pf_resize(pf_ctx* ctx, const uint8_t* src_bgra, size_t src_step, int cols, int rows, uint8_t* dst_bgra, size_t dst_step, int out_cols, int out_rows,
+              int filter);
+int pf_resize_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows,
+                        int filter);
+int pf_stitch_result_resized_dev(pf_ctx* ctx, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
+int pf_stitch_batch_result_resized_dev(pf_ctx* ctx, int frame, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

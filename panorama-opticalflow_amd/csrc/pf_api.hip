@@ -20,11 +20,12 @@
 #include "png_frame.hpp"
 #include "jpeg_frame.hpp"
 #include "tiff_parse.hpp"
+#include "resize_table.hpp"
 
 using namespace pf;
 
 
-// One translation unit in ten parts (the anonymous namespace and the extern "C" block span several of them):
+// One translation unit in eleven parts (the anonymous namespace and the extern "C" block span several of them):
 #include "pf_api_ctx.inl"      // pf_ctx, errors / warnings, arena, profiling events, geometry, checks
 #include "pf_api_solve.inl"    // run_level, solve buffers, solve / solve_n (stream orchestration)
 #include "pf_api_life.inl"     // finish / CallGuard, pf_create* / pf_destroy, memory helpers            (opens extern "C")
@@ -35,5 +36,6 @@ using namespace pf;
 #include "pf_api_png.inl"      // pf_png_*, pf_stitch_result_png (PNG files made on the device)
 #include "pf_api_tiff.inl"     // pf_tiff_* (TIFF files decoded on the device)
 #include "pf_api_jpeg.inl"     // pf_jpeg_*, pf_stitch_result_jpeg (JPEG files made on the device)
+#include "pf_api_resize.inl"   // pf_resize*, pf_stitch_result_resized_dev (Pillow's resample on the device)
 }  // extern "C"
 

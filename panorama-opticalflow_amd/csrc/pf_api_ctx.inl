@@ -79,6 +79,9 @@ struct pf_ctx {
   unsigned* d_rig_diff = nullptr;       // pixels whose region code differs from the rig's (k_rig_maps adds, the host reads after a sync)
   size_t rig_diff_cap = 0;
   bool rig_overlap_uploads = true;   // pf_rig_stitch_batch: later waves' second upload beside the compute (pf_rig_set_upload_overlap)
+  // pf_resize*: the host's tables of the last few (in, out, filter) axes, and which of them sits in the arena's "rz_tab_h" / "rz_tab_v"
+  std::vector<resize_table::Table> rz_tables;
+  struct RzResident { const void* p = nullptr; size_t cap = 0; int in = 0, out = 0, filter = 0; } rz_dev[2];
   bool tiff_inflate = false;         // pf_tiff_decode*: deflate strips decode on the device (pf_tiff_set_inflate); off: they are refused
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;

@@ -1,0 +1,156 @@
+// Part of pf_api.hip (one translation unit): the resize entry points.  The host makes the two axes' tables (resize_table.hpp), keeps
+// the last few in the context and uploads them; the passes run in kernels_resize.hip, horizontal first, through an intermediate plane
+// of out_cols x rows.  An axis whose size stays runs no pass; a size that stays altogether is a copy.  The scratch ("rz_*") is the
+// resize's own: no entry point here touches the chain, the prefetch records, the batch slots, the plans or what pf_stitch_visualize reads.
+}  // extern "C"
+namespace {
+
+constexpr size_t kRzTablesKept = 8;   // host tables a context keeps (a run resizes to one or two sizes)
+
+const resize_table::Table* resize_table_of(pf_ctx* c, int in, int out, int filter) {
+  for (const auto& t : c->rz_tables) if (t.in == in && t.out == out && t.filter == filter) return &t;
+  if (c->rz_tables.size() >= kRzTablesKept) c->rz_tables.erase(c->rz_tables.begin());
+  c->rz_tables.emplace_back();
+  resize_table::make(in, out, filter, &c->rz_tables.back());
+  return &c->rz_tables.back();
+}
+
+// the table of one axis in the arena: bounds, then the coefficients.  Uploaded when the slot holds another table or has moved.
+int resize_table_dev(pf_ctx* c, int axis, int in, int out, int filter, const int** d_bounds, const int** d_k) {
+  const resize_table::Table* t = resize_table_of(c, in, out, filter);
+  const size_t nb = t->bounds.size() * 4, nk = t->k.size() * 4, at_k = (nb + 255) & ~size_t(255);
+  uint8_t* d = (uint8_t*)ensure(c, axis ? "rz_tab_v" : "rz_tab_h", at_k + nk);
+  if (!d) return PF_ERR_NOMEM;
+  pf_ctx::RzResident& r = c->rz_dev[axis];
+  const size_t cap = c->bufs[axis ? "rz_tab_v" : "rz_tab_h"].cap;   // (a slot that grew is a fresh allocation, wherever it landed)
+  if (r.p != d || r.cap != cap || r.in != in || r.out != out || r.filter != filter) {
+    r.p = nullptr;
+    HIPCHK(c, hipMemcpyAsync(d, t->bounds.data(), nb, hipMemcpyHostToDevice, c->s_main));
+    HIPCHK(c, hipMemcpyAsync(d + at_k, t->k.data(), nk, hipMemcpyHostToDevice, c->s_main));
+    HIPCHK(c, hipStreamSynchronize(c->s_main));   // the host table may leave the context's list before the next call
+    r.p = d; r.cap = cap; r.in = in; r.out = out; r.filter = filter;
+  }
+  *d_bounds = (const int*)d; *d_k = (const int*)(d + at_k);
+  return 0;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+// sizes, the filter and the tables' bound: everything known without a pointer
+int resize_check(pf_ctx* c, int cols, int rows, int out_cols, int out_rows, int filter) {
+  if (int e = check_image(c, cols, rows)) return e;
+  if (out_cols <= 0 || out_rows <= 0) return fail(c, PF_ERR_ARG, "resize: bad output size %dx%d", out_cols, out_rows);
+  if ((double)out_cols * out_rows > 2.0e9 || (double)out_cols * rows > 2.0e9) return fail(c, PF_ERR_ARG, "resize: output %dx%d too large", out_cols, out_rows);
+  if (!resize_table::known(filter)) return fail(c, PF_ERR_ARG, "resize: unknown filter %d (1 LANCZOS, 2 BILINEAR, 3 BICUBIC, 4 BOX, 5 HAMMING)", filter);
+  if (out_cols != cols && !resize_table::fits(cols, out_cols, filter)) return fail(c, PF_ERR_ARG, "resize: the table of %d -> %d columns exceeds %.0f coefficients", cols, out_cols, resize_table::kMaxCoefs);
+  if (out_rows != rows && !resize_table::fits(rows, out_rows, filter)) return fail(c, PF_ERR_ARG, "resize: the table of %d -> %d rows exceeds %.0f coefficients", rows, out_rows, resize_table::kMaxCoefs);
+  return 0;
+}
+
+// n device images of cols x rows -> n of out_cols x out_rows, enqueued on s_main in groups of kMaxBatch; the caller drains
+int resize_many(pf_ctx* c, int n, const uint8_t* const* d_src, int cols, int rows, uint8_t* const* d_dst, int out_cols, int out_rows, int filter) {
+  const size_t in_bytes = size_t(cols) * rows * 4, out_bytes = size_t(out_cols) * out_rows * 4;
+  for (int k = 0; k < n; ++k) {
+    if (!d_src[k] || !d_dst[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
+    if ((reinterpret_cast<uintptr_t>(d_src[k]) | reinterpret_cast<uintptr_t>(d_dst[k])) & 3) return fail(c, PF_ERR_ARG, "resize: device image %d is not 4-byte aligned", k);
+  }
+  for (int k = 0; k < n; ++k)
+    for (int q = 0; q < n; ++q)
+      if (ranges_overlap(d_dst[k], out_bytes, d_src[q], in_bytes)) return fail(c, PF_ERR_ARG, "resize: destination %d overlaps source %d", k, q);
+  hipStream_t sm = c->s_main;
+  const bool do_h = out_cols != cols, do_v = out_rows != rows;
+  if (!do_h && !do_v) {
+    for (int k = 0; k < n; ++k) HIPCHK(c, hipMemcpyAsync(d_dst[k], d_src[k], in_bytes, hipMemcpyDeviceToDevice, sm));
+    return 0;
+  }
+  const int *bh = nullptr, *kh = nullptr, *bv = nullptr, *kv = nullptr;
+  if (do_h) if (int e = resize_table_dev(c, 0, cols, out_cols, filter, &bh, &kh)) return e;
+  if (do_v) if (int e = resize_table_dev(c, 1, rows, out_rows, filter, &bv, &kv)) return e;
+  const size_t mid_bytes = (size_t(out_cols) * rows * 4 + 255) & ~size_t(255);
+  uint8_t* d_mid = nullptr;
+  if (do_h && do_v) { d_mid = (uint8_t*)ensure(c, "rz_mid", mid_bytes * std::min(n, kMaxBatch)); if (!d_mid) return PF_ERR_NOMEM; }
+  for (int first = 0; first < n; first += kMaxBatch) {
+    const int count = std::min(kMaxBatch, n - first);
+    ResizePtrs h, v;
+    memset(&h, 0, sizeof h); memset(&v, 0, sizeof v);
+    for (int k = 0; k < count; ++k) {
+      uint32_t* mid = (uint32_t*)(d_mid + k * mid_bytes);
+      h.src[k] = (const uint32_t*)d_src[first + k]; h.dst[k] = do_v ? mid : (uint32_t*)d_dst[first + k];
+      v.src[k] = do_h ? mid : (const uint32_t*)d_src[first + k]; v.dst[k] = (uint32_t*)d_dst[first + k];
+    }
+    if (do_h) { PROF(c, sm, "resize_h"); launch_resize_h(sm, count, h, cols, rows, out_cols, bh, kh, true, !do_v); }
+    if (do_v) { PROF(c, sm, "resize_v"); launch_resize_v(sm, count, v, out_cols, rows, out_rows, bv, kv, !do_h, true); }
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+extern "C" {
+
+int pf_resize_dev(pf_ctx* c, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* d_dst_bgra, int out_cols, int out_rows, int filter) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_src_bgra || !d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
+  if (int e = resize_many(c, 1, &d_src_bgra, cols, rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
+  return finish(c);
+}
+
+int pf_resize(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, int rows, uint8_t* dst_bgra, size_t dst_step, int out_cols, int out_rows, int filter) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!src_bgra || !dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
+  if (src_step < size_t(cols) * 4 || dst_step < size_t(out_cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
+  if (ranges_overlap(dst_bgra, size_t(out_rows - 1) * dst_step + size_t(out_cols) * 4, src_bgra, size_t(rows - 1) * src_step + size_t(cols) * 4))
+    return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
+  uint8_t* d_src = (uint8_t*)ensure(c, "rz_src", size_t(cols) * rows * 4);
+  uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", size_t(out_cols) * out_rows * 4);
+  if (!d_src || !d_dst) return PF_ERR_NOMEM;
+  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, src_step, size_t(cols) * 4, rows)) return e;
+  const uint8_t* dc = d_src;
+  if (int e = resize_many(c, 1, &dc, cols, rows, &d_dst, out_cols, out_rows, filter)) return e;
+  if (int e = down2d(c, dst_bgra, dst_step, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  return finish(c);
+}
+
+int pf_resize_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows, int filter) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (n < 0 || !d_src_bgra || !d_dst_bgra) return fail(c, PF_ERR_ARG, "bad argument");
+  if (n == 0) return 0;
+  if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
+  if (int e = resize_many(c, n, d_src_bgra, cols, rows, d_dst_bgra, out_cols, out_rows, filter)) return e;
+  return finish(c);
+}
+
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final"), read in place
+int pf_stitch_result_resized_dev(pf_ctx* c, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_resized_dev: no stitch step result in HBM");
+  if (int e = resize_check(c, c->chain_cols, c->chain_rows, out_cols, out_rows, filter)) return e;
+  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
+  if (int e = resize_many(c, 1, &d, c->chain_cols, c->chain_rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
+  return finish(c);
+}
+
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+int pf_stitch_batch_result_resized_dev(pf_ctx* c, int frame, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_resized_dev: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
+  char name[32];
+  snprintf(name, sizeof name, "sb_fin%d", frame);
+  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
+  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_resized_dev: no batch result in frame slot %d", frame);
+  if (int e = resize_check(c, c->sb_cols, c->sb_rows, out_cols, out_rows, filter)) return e;
+  if (int e = resize_many(c, 1, &d, c->sb_cols, c->sb_rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
+  return finish(c);
+}

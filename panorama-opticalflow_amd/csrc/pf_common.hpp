@@ -261,6 +261,12 @@ void launch_jpeg_blocks(hipStream_t st, const uint8_t* bgra /* packed, 4-byte al
 void launch_jpeg_sizes(hipStream_t st, int cols, int rows, int subsampling, int restart, const JpegWork& w);                                          // coef -> sizes, offs
 void launch_jpeg_write(hipStream_t st, int cols, int rows, int subsampling, int restart, const JpegWork& w, uint8_t* packed /* offs[intervals] bytes */);
 
+// ---- resize (kernels_resize.hip): Pillow's antialiased resample of an RGBA image, a horizontal and a vertical pass; the host makes the tables ----
+struct ResizePtrs { const uint32_t* src[kMaxBatch]; uint32_t* dst[kMaxBatch]; };   // blockIdx.z = image, n <= kMaxBatch same-size images per launch
+// bounds: per output index {first source index, taps}; k: 22-bit fixed-point coefficients, tap-major (k[t * out + index])
+void launch_resize_h(hipStream_t st, int n, const ResizePtrs& io, int cols, int rows, int out_cols, const int* bounds, const int* k, bool premul, bool unpremul);   // cols x rows -> out_cols x rows
+void launch_resize_v(hipStream_t st, int n, const ResizePtrs& io, int cols, int rows, int out_rows, const int* bounds, const int* k, bool premul, bool unpremul);   // cols x rows -> cols x out_rows
+
 // ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits, deflate), then predictor + RGB(A) -> BGRA per row ----
 // A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled
 // the strip; the strip is good when the low half equals its expected bytes).

@@ -127,6 +127,11 @@ def lib(exp=False):
         _lib.pf_tiff_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         _lib.pf_tiff_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         _lib.pf_tiff_decode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_resize_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        _lib.pf_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]
+        _lib.pf_resize_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        _lib.pf_stitch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_stitch_batch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     return _lib
 
 
@@ -150,6 +155,7 @@ EXPORTS = [
     "pf_jpeg_params_init", "pf_jpeg_bound", "pf_jpeg_restart_interval", "pf_jpeg_encode_dev", "pf_jpeg_encode", "pf_jpeg_encode_batch_dev",
     "pf_stitch_result_jpeg", "pf_stitch_batch_result_jpeg",
     "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
+    "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -200,6 +206,10 @@ def jpeg_bound(cols, rows, params=None):
 def jpeg_restart_interval(subsampling):
     """MCUs per restart interval of the device JPEG encoder (pf_jpeg_restart_interval)"""
     return int(lib().pf_jpeg_restart_interval(subsampling))
+
+
+# PF_RESIZE_* (Pillow's numbering of its resampling filters)
+RESIZE_LANCZOS, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_BOX, RESIZE_HAMMING = 1, 2, 3, 4, 5
 
 
 def tiff_probe(data):
@@ -699,6 +709,35 @@ class Context:
         files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)(*[b.size for b in bufs])
         outs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_outs])
         self._chk(self.l.pf_tiff_decode_batch_dev(self.h, n, files, sizes, cols, rows, outs))
+
+    # ---- resize on the device (pf_resize*): Pillow's Image.resize of an RGBA image, byte for byte; filter = one of RESIZE_* ----
+    def resize(self, image, out_cols, out_rows, filter=RESIZE_LANCZOS, out=None):
+        """host BGRA (rows, cols, 4) array, any row stride -> host (out_rows, out_cols, 4); out: a destination array (its row stride is kept)"""
+        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+        if a.strides[2] != 1 or a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        if out is None:
+            out = np.empty((max(out_rows, 0), max(out_cols, 0), 4), np.uint8)
+        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(out_cols, 0) * 4
+        self._chk(self.l.pf_resize(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, _p(out), C.c_size_t(step), out_cols, out_rows, int(filter)))
+        return out
+
+    def resize_dev(self, d_src, cols, rows, d_dst, out_cols, out_rows, filter=RESIZE_LANCZOS):
+        self._chk(self.l.pf_resize_dev(self.h, C.c_void_p(d_src), cols, rows, C.c_void_p(d_dst), out_cols, out_rows, int(filter)))
+
+    def resize_batch_dev(self, d_srcs, cols, rows, d_dsts, out_cols, out_rows, filter=RESIZE_LANCZOS):
+        """n same-size device images -> n device images of out_cols x out_rows, one drain"""
+        n = len(d_srcs)
+        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_srcs]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_dsts])
+        self._chk(self.l.pf_resize_batch_dev(self.h, n, srcs, cols, rows, dsts, out_cols, out_rows, int(filter)))
+
+    def stitch_result_resized_dev(self, out_cols, out_rows, d_dst, filter=RESIZE_LANCZOS):
+        """the composite the last stitch_step left in HBM, resized into d_dst (out_cols * out_rows * 4 bytes of device memory)"""
+        self._chk(self.l.pf_stitch_result_resized_dev(self.h, out_cols, out_rows, int(filter), C.c_void_p(d_dst)))
+
+    def stitch_batch_result_resized_dev(self, frame, out_cols, out_rows, d_dst, filter=RESIZE_LANCZOS):
+        """frame slot `frame` of the last stitch_step_batch, resized into d_dst"""
+        self._chk(self.l.pf_stitch_batch_result_resized_dev(self.h, frame, out_cols, out_rows, int(filter), C.c_void_p(d_dst)))
 
     # ---- device-resident entry points (raw device pointers as ints) ----
     def dev_alloc(self, nbytes):

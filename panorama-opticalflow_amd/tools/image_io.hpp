@@ -5,6 +5,7 @@
 //   * PNG reader/writer: 8-bit RGB/RGBA, non-interlaced (zlib).
 //   * write_png_device: the same pixels as a PNG the library makes on the GPU (pf_png_*); only the finished file comes to the host.
 //   * write_jpeg_device: a result as a baseline JPEG the library makes on the GPU (pf_jpeg_*).
+//   * DeviceImage, resize_host_image: a result at another size, resized on the GPU (pf_resize_*).
 //   * imread_device / imread_to_device: a TIFF's strips decoded on the GPU (pf_tiff_*); only the file's bytes go up.  read_tiff stays
 //     the behaviour model and the fallback (deflate files, files of few strips).
 // Pixels are delivered as BGRA (CV_8UC4) like cv::imread(-1) followed by the reference's BGR->BGRA (main.cpp:58,68).
@@ -237,6 +238,25 @@ static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const
 // a packed device image
 static inline void write_jpeg_device(const std::string& path, pf_ctx* ctx, const pf_jpeg_params& params, const unsigned char* d_bgra, int cols, int rows) {
   write_jpeg_bytes(path, ctx, cols, rows, params, [&](unsigned char* b, size_t cap, size_t* n) { return pf_jpeg_encode_dev(ctx, d_bgra, cols, rows, &params, b, cap, n); });
+}
+// A result at another size (include/panoflow.h, "Resize on the device"): a packed device image that frees itself however the run ends,
+// and the one wrapper the CLI needs beside the library's own calls: a host image sent up once and resized there.
+struct DeviceImage {
+  pf_ctx* ctx; unsigned char* p; int cols, rows;
+  DeviceImage(pf_ctx* ctx_, int cols_, int rows_) : ctx(ctx_), p((unsigned char*)pf_dev_alloc(ctx_, size_t(cols_) * rows_ * 4)), cols(cols_), rows(rows_) {
+    if (!p) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+  }
+  ~DeviceImage() { pf_dev_free(ctx, p); }
+  DeviceImage(const DeviceImage&) = delete;
+  DeviceImage& operator=(const DeviceImage&) = delete;
+};
+static inline int resize_host_image(pf_ctx* ctx, const Mat& bgra, int out_cols, int out_rows, int filter, unsigned char* d_dst) {
+  if (bgra.type() != panocv::CV_8UC4) throw VrCamException("resize_host_image expects CV_8UC4");
+  DeviceImage src(ctx, bgra.cols, bgra.rows);
+  const size_t row = size_t(bgra.cols) * 4;
+  if (bgra.step == row) { if (int rc = pf_upload(ctx, src.p, bgra.data, row * bgra.rows)) return rc; }
+  else for (int y = 0; y < bgra.rows; ++y) if (int rc = pf_upload(ctx, src.p + y * row, bgra.data + size_t(y) * bgra.step, row)) return rc;
+  return pf_resize_dev(ctx, src.p, bgra.cols, bgra.rows, d_dst, out_cols, out_rows, filter);
 }
 static inline Mat read_png(const std::string& path) {
   const std::vector<unsigned char> b = read_file(path);

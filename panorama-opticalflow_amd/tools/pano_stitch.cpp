@@ -41,9 +41,15 @@
 //   -tiff_inflate 1 (with -tiff_device 1; off by default): deflate TIFFs (compression 8 / 32946) fall under the same rule as LZW ones --
 //   at least 64 strips -- through the library's inflate switch (pf_tiff_set_inflate).  A strip is accepted exactly when zlib's uncompress
 //   into the strip's size succeeds or ends with Z_BUF_ERROR and the strip full; a short or malformed strip ends the run.
+//   -result_size WxH [-result_filter lanczos|bicubic|bilinear|hamming|box] (any mode; needs -png_device 1 or -jpeg_device 1): every result
+//   file of the run -- ProcessResult{i}, FinalResult, in every directory of -test_dirs -- is written at W x H, resized on the GPU between
+//   the composite and the encoder (pf_resize_*: Pillow's Image.resize of the RGBA image, byte for byte; lanczos by default).  The chain
+//   itself stays at full size.  Where the composite lies in HBM it is resized from there; where the mode holds it on the host it is sent
+//   up once and resized there.  The -visualize panels are not scaled.  With -jpeg_gpano 1 it is W x H that must be 2:1.
 #include <sys/stat.h>
 
 #include <cerrno>
+#include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <map>
@@ -67,8 +73,19 @@ static void writeImage(const std::string& path, const Mat& image) {
 }
 static bool g_jpeg_device = false;   // -jpeg_device 1: the results (not the panels) as JPEGs made on the device
 static pf_jpeg_params g_jpeg;
-// a host result image to <stem>.png, or with -jpeg_device 1 to <stem>.jpg
+static int g_result_cols = 0, g_result_rows = 0, g_result_filter = PF_RESIZE_LANCZOS;   // -result_size WxH (0: the canvas's size) -result_filter
+// <stem>.jpg or <stem>.png of the result-size image that resize(d_dst) -- a pf_*resize* call bound to its source -- makes in device memory
+template <class Resize>
+static void writeResized(const std::string& stem, Resize resize) {
+  pf_ctx* ctx = pano::context();
+  pano_io::DeviceImage d(ctx, g_result_cols, g_result_rows);
+  pano::check(resize(d.p));
+  if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", ctx, g_jpeg, d.p, d.cols, d.rows);
+  else pano_io::write_png_bytes(stem + ".png", ctx, d.cols, d.rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_png_encode_dev(ctx, d.p, d.cols, d.rows, b, cap, n); });
+}
+// a host result image to <stem>.png, or with -jpeg_device 1 to <stem>.jpg; with -result_size sent up once and resized there
 static void writeResult(const std::string& stem, const Mat& image) {
+  if (g_result_cols) return writeResized(stem, [&](unsigned char* d) { return pano_io::resize_host_image(pano::context(), image, g_result_cols, g_result_rows, g_result_filter, d); });
   if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, image);
   else writeImage(stem + ".png", image);
 }
@@ -226,7 +243,8 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
     prev0 = outs[0];
     for (int k = 0; k < n; ++k) {
       const std::string stem = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
-      if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, k, Ls[0].cols, Ls[0].rows);
+      if (g_result_cols) writeResized(stem, [&](unsigned char* d) { return pf_stitch_batch_result_resized_dev(pano::context(), k, g_result_cols, g_result_rows, g_result_filter, d); });
+      else if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, k, Ls[0].cols, Ls[0].rows);
       else if (g_png_device) pano_io::write_png_device(stem + ".png", pano::context(), k, Ls[0].cols, Ls[0].rows);
       else pano_io::imwriteExceptionOnFail(stem + ".png", outs[k]);
     }
@@ -344,7 +362,9 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
     for (int i = 1; i <= nsteps; ++i) {
       const uint8_t* d = o[size_t(k) * nsteps + i - 1];
       const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
-      if (g_jpeg_device) {
+      if (g_result_cols) {
+        writeResized(path.substr(0, path.size() - 4), [&](unsigned char* dst) { return pf_resize_dev(ctx, d, cols, rows, dst, g_result_cols, g_result_rows, g_result_filter); });
+      } else if (g_jpeg_device) {
         pano_io::write_jpeg_device(path.substr(0, path.size() - 4) + ".jpg", ctx, g_jpeg, d, cols, rows);
       } else if (g_png_device) {
         pano_io::write_png_bytes(path, ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* size) { return pf_png_encode_dev(ctx, d, cols, rows, b, cap, size); });
@@ -372,6 +392,18 @@ int main(int argc, char** argv) {
       g_jpeg.subsampling = sub == "420";
       g_jpeg.gpano = flags.count("jpeg_gpano") && atoi(flags["jpeg_gpano"].c_str()) != 0;
     }
+    if (flags.count("result_size")) {   // every refusal before any device call
+      char tail = 0;
+      if (sscanf(flags["result_size"].c_str(), "%dx%d%c", &g_result_cols, &g_result_rows, &tail) != 2 || g_result_cols <= 0 || g_result_rows <= 0)
+        throw VrCamException("-result_size must be WxH with both positive, e.g. 4096x2048");
+      if (!g_png_device && !g_jpeg_device) throw VrCamException("-result_size needs -png_device 1 or -jpeg_device 1 (the results are resized and encoded on the GPU)");
+      const std::string name = flags.count("result_filter") ? flags["result_filter"] : "lanczos";
+      const std::map<std::string, int> filters = {{"lanczos", PF_RESIZE_LANCZOS}, {"bicubic", PF_RESIZE_BICUBIC}, {"bilinear", PF_RESIZE_BILINEAR},
+                                                  {"hamming", PF_RESIZE_HAMMING}, {"box", PF_RESIZE_BOX}};
+      if (!filters.count(name)) throw VrCamException("-result_filter must be lanczos, bicubic, bilinear, hamming or box");
+      g_result_filter = filters.at(name);
+      if (g_jpeg_device && g_jpeg.gpano && g_result_cols != 2 * g_result_rows) throw VrCamException("-jpeg_gpano 1 declares a full sphere, which -result_size " + flags["result_size"] + " (not 2:1) is not");
+    } else if (flags.count("result_filter")) throw VrCamException("-result_filter needs -result_size WxH");
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
@@ -454,7 +486,8 @@ int main(int argc, char** argv) {
       }
 
       const std::string resultStem = FLAGS_test_dir + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
-      if (fused && g_jpeg_device) pano_io::write_jpeg_device(resultStem + ".jpg", pano::context(), g_jpeg, colorImageL.cols, colorImageL.rows);
+      if (fused && g_result_cols) writeResized(resultStem, [&](unsigned char* d) { return pf_stitch_result_resized_dev(pano::context(), g_result_cols, g_result_rows, g_result_filter, d); });
+      else if (fused && g_jpeg_device) pano_io::write_jpeg_device(resultStem + ".jpg", pano::context(), g_jpeg, colorImageL.cols, colorImageL.rows);
       else if (fused && g_png_device) pano_io::write_png_device(resultStem + ".png", pano::context(), colorImageL.cols, colorImageL.rows);
       else writeResult(resultStem, FinalResult);
       std::cout << "Part" << i << " Finished!" << "RUNTIME (sec) = " << (getCurrTimeSec() - StepStart) << std::endl;
