@@ -46,12 +46,15 @@ using std::min;
 // one workgroup after the other, `block` host threads each
 template <class Kernel, class... Args>
 void host_shim_launch(Kernel kernel, unsigned grid, unsigned block, Args... args) {
-  for (unsigned b = 0; b < grid; ++b) {
-    std::barrier<> bar(block);
-    host_shim_barrier = &bar;
-    std::vector<std::thread> threads;
-    for (unsigned t = 0; t < block; ++t)
-      threads.emplace_back([=]() { threadIdx = dim3(t); blockIdx = dim3(b); gridDim = dim3(grid); kernel(args...); });
-    for (auto& th : threads) th.join();
-  }
+  std::barrier<> bar(block);
+  host_shim_barrier = &bar;
+  std::vector<std::thread> threads;
+  for (unsigned t = 0; t < block; ++t)
+    threads.emplace_back([=, &bar]() {
+      threadIdx = dim3(t); gridDim = dim3(grid);
+      // the same host threads run workgroup after workgroup (a grid of a thousand small workgroups would otherwise spend its time starting
+      // threads); the barrier between two keeps a workgroup's __shared__ statics its own until its last thread is done
+      for (unsigned b = 0; b < grid; ++b) { blockIdx = dim3(b); kernel(args...); bar.arrive_and_wait(); }
+    });
+  for (auto& th : threads) th.join();
 }

@@ -2,8 +2,9 @@
 // sanitizers: every buffer has exactly the size the library gives it, so an index past a segment, a slot or the stream is caught here,
 // without a GPU.  Each file is then framed (csrc/png_frame.hpp), inflated with zlib, unfiltered and compared with the image.
 // With arguments, groups of `IN.bgra cols rows OUT.png`: each raw BGRA file is encoded by the same kernels and the framed file written,
-// for the byte comparison with the serial model (tests/png_model.py).  Without: the shapes below, and build_code on frequency tables
-// that reach both of its length limits.
+// for the byte comparison with the serial model (tests/png_model.py).  The one argument `scan`: k_png_scan alone, on size arrays of
+// up to five elements per thread.  Without arguments: the shapes below, and build_code on frequency tables that reach both of its
+// length limits.
 // Built and run by tests/test_png_kernels_host.py:  g++ -std=c++20 -fsanitize=address,undefined -Itests/cpp/hip_host_shim ... -lz -pthread
 #include <stdio.h>
 
@@ -197,6 +198,24 @@ static void check_build_code() {
   CHECK(limited7 > 0 && limited15 > 0);
 }
 
+// k_png_scan on n sizes with values up to 2^32 - 1, buffers at their exact lengths, against a serial prefix sum: a thread sums
+// ceil(n / 1024) of them (no image of a size the host can run has more than 1024 segments)
+static void check_scan() {
+  for (int n : {1, 1023, 1024, 1025, 2048, 2049, 5000}) {
+    uint32_t seed = 99u + (uint32_t)n;
+    std::vector<unsigned> sizes(n);
+    for (int i = 0; i < n; ++i) sizes[i] = i % 5 == 0 ? 0xffffffffu : i % 7 == 0 ? 0u : rnd(seed) << 8 | (rnd(seed) & 0xff);
+    std::vector<unsigned long long> offs(n + 1, 0xA5A5A5A5A5A5A5A5ull);
+    host_shim_launch(k_png_scan, 1u, 1024u, (const unsigned*)sizes.data(), n, offs.data());
+    unsigned long long acc = 0;
+    int bad = 0;
+    for (int i = 0; i < n; ++i) { bad += offs[i] != acc; acc += sizes[i]; }
+    bad += offs[n] != acc;
+    CHECK(bad == 0);
+    printf("  k_png_scan n = %d (%d per thread): total %llu, %d of %d offsets differ\n", n, (n + 1023) / 1024, acc, bad, n + 1);
+  }
+}
+
 static std::vector<uint8_t> read_file(const char* path) {
   std::vector<uint8_t> v;
   FILE* f = fopen(path, "rb");
@@ -226,6 +245,12 @@ static int encode_files(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
+  if (argc == 2 && !strcmp(argv[1], "scan")) {
+    check_scan();
+    if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
+    printf("ok\n");
+    return 0;
+  }
   if (argc > 1) return encode_files(argc, argv);
   // (a barrier of 256 host threads is slow: few rows, and only the shapes at which an index can go wrong)
   const int cases[][3] = {{1, 1, 0}, {1, 5, 1}, {7, 1, 1}, {65, 3, 0}, {65, 3, 1},   // no neighbours; a row around 256 bytes

@@ -1,6 +1,9 @@
 """The device JPEG encoder's specification as a serial numpy program: libjpeg's integer path, restated.  encode() gives
 the whole file, byte for byte what libjpeg(-turbo) writes for the same image, quality, subsampling and restart interval (held to that by
 tests/test_jpeg_model.py), and a trace of the symbols it sent, which the branch cases (tests/jpeg_cases.py) are checked against.
+Per restart interval the trace also gives the coder's geometry before stuffing: the bit count, the padded bytes, the byte offsets of
+every 0xFF, and where each code word starts and how long it is (a code word as the device coder sends it: a Huffman code and the
+value's bits as one word of up to 26 bits).
 Input is packed BGRA (rows, cols, 4) uint8; alpha is dropped and the colour bytes are encoded as stored."""
 import numpy as np
 
@@ -193,15 +196,17 @@ def entropy(blocks, subsampling, restart, info=None):
     comp = [0, 1, 2] if bpm == 3 else [0, 0, 0, 0, 1, 2]
     out = bytearray()
     tr = dict(zrl=0, zrl_pairs=0, no_eob=0, all_zero=0, max_dc_cat=0, max_ac_cat=0, ff_inside=0, ff_last=0, exact_byte=0, max_block_bits=0,
-              intervals=0, interval_bytes=[])
+              intervals=0, interval_bytes=[], interval_bits=[], interval_raw=[], ff_offsets=[], word_starts=[], word_lens=[])
     nint = _ceil(n, restart)
     for i in range(nint):
         bits = _Bits(); pred = [0, 0, 0]
+        starts = []          # the bit at which every code word starts, and (a sentinel) the interval's bit count
         for m in range(i * restart, min(n, (i + 1) * restart)):
             for j in range(bpm):
                 c = blocks[m, j]; k = comp[j]; t = min(k, 1); start = bits.n
                 d = int(c[0]) - pred[k]; pred[k] = int(c[0])
                 s = _category(d)
+                starts.append(bits.n)
                 bits.put(*dc_tab[t][s])
                 if s:
                     bits.put((d if d >= 0 else d - 1) & ((1 << s) - 1), s)
@@ -212,19 +217,27 @@ def entropy(blocks, subsampling, restart, info=None):
                     v = int(c[z]); run = z - last - 1; last = z
                     nzrl = run // 16
                     for _ in range(nzrl):
+                        starts.append(bits.n)
                         bits.put(*ac_tab[t][0xF0])
                     tr["zrl"] += nzrl; tr["zrl_pairs"] += nzrl >= 2
                     s = _category(v)
+                    starts.append(bits.n)
                     bits.put(*ac_tab[t][((run & 15) << 4) | s])
                     bits.put((v if v >= 0 else v - 1) & ((1 << s) - 1), s)
                     tr["max_ac_cat"] = max(tr["max_ac_cat"], s)
                 if last != 63:
+                    starts.append(bits.n)
                     bits.put(*ac_tab[t][0])
                 else:
                     tr["no_eob"] += 1
                 tr["all_zero"] += (d == 0 and len(nz) == 0)
                 tr["max_block_bits"] = max(tr["max_block_bits"], bits.n - start)
+        starts.append(bits.n)
+        tr["interval_bits"].append(bits.n)
+        tr["word_starts"].append(np.array(starts[:-1], np.int64)); tr["word_lens"].append(np.diff(np.array(starts, np.int64)))
         raw, pad = bits.flush()
+        tr["interval_raw"].append(raw)
+        tr["ff_offsets"].append(np.flatnonzero(np.frombuffer(raw, np.uint8) == 0xFF))
         tr["exact_byte"] += pad == 0
         tr["ff_inside"] += raw[:-1].count(0xFF)
         tr["ff_last"] += raw[-1:] == b"\xff"

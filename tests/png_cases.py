@@ -68,6 +68,29 @@ def small_cases(segment_bytes):
     return out
 
 
+# ---- more than 1024 segments: the compaction scan sums two sizes per thread ----
+MANY_COLS, MANY_ROWS, MANY_BAND, MANY_PERIOD = 341, 12300, 12, 84
+
+
+def many_segments(segment_bytes):
+    """341 x 12300: a scanline is 1365 bytes, 12 of them are exactly one segment, and there are 1025 segments.  The image repeats every
+    84 rows: seven 12-row bands of different compressibility (flat, a gradient, noise that must be stored, and mixtures with a little
+    noise in them), so that the segments' sizes differ, the filtered stream repeats with that period from segment 1 on (row 0 alone has
+    no row above it) and tests/png_model.py has nine distinct segments to encode; 1025 is no multiple of 7."""
+    cols, band = MANY_COLS, MANY_BAND
+    assert (4 * cols + 1) * band == segment_bytes and MANY_ROWS * (4 * cols + 1) == 1025 * segment_bytes
+    rng = _rng(31)
+    flat = constant(cols, band, (40, 90, 200, 255))
+    bands = [flat.copy(), smooth(cols, band), rng.integers(0, 256, (band, cols, 4), dtype=np.uint8)]
+    b = flat.copy(); b[5] = rng.integers(0, 256, (cols, 4), dtype=np.uint8); bands.append(b)                       # one row of noise in flat colour
+    b = smooth(cols, band); b[:, 100:120] = rng.integers(0, 256, (band, 20, 4), dtype=np.uint8); bands.append(b)    # a stripe of noise down a gradient
+    b = smooth(cols, band); b[3:5] = rng.integers(0, 256, (2, cols, 4), dtype=np.uint8); bands.append(b)           # two rows of noise in a gradient
+    b = constant(cols, band, (7, 7, 7, 0)); b[2:5, ::16] = rng.integers(0, 256, (3, len(range(0, cols, 16)), 4), dtype=np.uint8); bands.append(b)   # sparse noise pixels
+    period = np.concatenate(bands)
+    assert period.shape[0] == MANY_PERIOD
+    return np.ascontiguousarray(np.tile(period, (MANY_ROWS // MANY_PERIOD + 1, 1, 1))[:MANY_ROWS])
+
+
 # ---- cases that reach one branch each of the encoder (tests/test_png_decode_ref.py shows from tests/png_model.py that they do) ----
 def gray(rows):
     """rows of one value per pixel -> an image with that value in all four channels"""

@@ -127,6 +127,12 @@ def _decoder(lens, what, may_be_lone=False):
     return table
 
 
+def copy_match(out, length, dist):
+    """append `length` bytes from `dist` back, a byte at a time in effect: the bytes a match appends may be ones it has just appended"""
+    tail = bytes(out[-dist:])
+    out += (tail * (length // dist + 1))[:length]
+
+
 class _BitReader:
     def __init__(self, data):
         self.d = data; self.pos = 0
@@ -228,8 +234,7 @@ def inflate_trace(z):
                     if dist > len(out):
                         raise PngError("distance %d beyond the output (%d bytes)" % (dist, len(out)))
                     toks.append((length, dist))
-                    for _ in range(length):
-                        out.append(out[-dist])
+                    copy_match(out, length, dist)
         blk["end_bit"] = r.pos
         blocks.append(blk)
         if blk["bfinal"]:

@@ -2,7 +2,9 @@
 csrc/png_frame.hpp.  encode(img) gives the file the encoder must give, byte for byte, and says how it got there.
 
 Nothing here is parallel: the filter sums are whole planes, a segment's tokens come from one left-to-right scan, the Huffman code from
-one two-queue merge.  It is slow (pure-Python bit packing); the tests keep it to images of 300 x 200 and below.
+one two-queue merge.  It is slow (pure-Python token and bit loops), so the images whose every segment it encodes stay small (a few
+dozen segments at the most).  Byte equality with the device is not limited to them: a stream of more than a thousand segments is
+within the model's reach where the segments repeat, and encode(img, cache={}) encodes each distinct (segment, last) once.
 """
 import heapq
 import zlib
@@ -284,8 +286,12 @@ def encode_segment(seg, last):
     return out, info
 
 
-def encode(img):
-    """BGRA (rows, cols, 4) -> (the PNG file, info).  info["types"]: the filter type per row, info["sums"]: the five sums per row,
+ADLER_BY_DEFINITION_MAX = 1 << 20   # stream bytes up to which encode() also sums the Adler-32 by its definition, byte by byte in Python
+
+
+def encode(img, cache=None):
+    """BGRA (rows, cols, 4) -> (the PNG file, info).  cache: a dict that keeps encode_segment's result per (segment bytes, last), for
+    streams whose segments repeat.  info["types"]: the filter type per row, info["sums"]: the five sums per row,
     info["segments"]: per segment n, stored, tokens, coded_bytes, limited15 / limited7 (the two-queue tree went beyond the limit),
     depth_litlen / depth_cl (the deepest leaf of a plain heapq Huffman tree), the two length vectors and the histograms."""
     img = np.asarray(img, np.uint8)
@@ -294,12 +300,20 @@ def encode(img):
     deflate, segs = bytearray(), []
     for at in range(0, len(stream), SEG):
         seg = stream[at:at + SEG]
-        data, info = encode_segment(seg, at + SEG >= len(stream))
+        key = (seg, at + SEG >= len(stream))
+        if cache is None:
+            data, info = encode_segment(*key)
+        else:
+            if key not in cache:
+                cache[key] = encode_segment(*key)
+            data, info = cache[key]
         deflate += data; segs.append(info)
-    a = (1 + sum(stream)) % 65521                    # Adler-32 by its definition, over the whole stream
-    b = (len(stream) + sum((len(stream) - p) * v for p, v in enumerate(stream))) % 65521
-    z = b"\x78\x01" + bytes(deflate) + ((b << 16) | a).to_bytes(4, "big")
-    assert zlib.adler32(stream) == (b << 16) | a
+    adler = zlib.adler32(stream)
+    if len(stream) <= ADLER_BY_DEFINITION_MAX:       # Adler-32 by its definition, over the whole stream
+        a = (1 + sum(stream)) % 65521
+        b = (len(stream) + sum((len(stream) - p) * v for p, v in enumerate(stream))) % 65521
+        assert adler == (b << 16) | a
+    z = b"\x78\x01" + bytes(deflate) + adler.to_bytes(4, "big")
     return R.frame(cols, rows, z), {"types": types, "sums": sums, "segments": segs, "stream": stream}
 
 
@@ -328,8 +342,7 @@ def check_stream(data):
                 out.append(t)
             else:
                 assert t[1] in (1, 4) and 3 <= t[0] <= PIECE and t[1] <= len(out)      # no match reaches back before the segment
-                for _ in range(t[0]):
-                    out.append(out[-t[1]])
+                R.copy_match(out, t[0], t[1])
         assert bytes(out) == raw[at:at + n]
         if blk["btype"] == 0:
             assert size == n + OVERHEAD

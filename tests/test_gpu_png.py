@@ -303,3 +303,20 @@ def test_synth_image_filter_types_equal_the_models(ctx, synth):
     want = M.filter_image(img)[1]
     print("filter types %s" % np.bincount(want, minlength=5).tolist())
     assert np.array_equal(types, want), "rows %s" % np.flatnonzero(types != want).tolist()[:10]
+
+
+def test_more_than_1024_segments_equal_the_serial_model(pf, ctx):
+    """341 x 12300 is 1025 segments of 12 rows: k_png_scan's threads sum two sizes each and the last of them none (every other image
+    of the suite has at most 352 segments, one per thread).  The image repeats every seven segments, of sizes from 76 bytes to a stored
+    16390, so an offset that is wrong anywhere moves bytes; the model encodes the nine distinct segments once each."""
+    img = png_cases.many_segments(SEG)
+    cache = {}
+    want, info = M.encode(img, cache=cache)
+    sizes = [s["n"] + M.OVERHEAD if s["stored"] else s["coded_bytes"] for s in info["segments"]]
+    assert len(sizes) == 1025 and len(cache) == 9 and len(set(sizes)) >= 7 and len(set(sizes[1:8])) == 7
+    assert sum(sizes) + 2 + 4 == len(R.zlib_stream(want))
+    got = ctx.png_encode(img)
+    assert got == want, _first_difference(got, want)
+    M.check_against_model(got, info)                         # check_stream, and the model's account of every segment
+    assert np.array_equal(R.decode(got), img)
+    assert len(got) <= pf.png_bound(img.shape[1], img.shape[0])

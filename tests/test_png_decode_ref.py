@@ -405,3 +405,26 @@ def test_threshold_cases_straddle_the_stored_rule():
     for name, (img, diff) in png_cases.threshold_cases().items():
         seg = _model(name)[1]["segments"][0]
         assert seg["coded_bytes"] - (seg["n"] + M.OVERHEAD) == diff and seg["stored"] == (diff >= 0)
+
+
+# ---- the model's segment cache and the 1025-segment image (tests/test_gpu_png.py sends it to the device) ----
+def test_segment_cache_changes_nothing():
+    """a periodic image of 15 segments: with the cache the model encodes the distinct (segment, last) pairs only, and writes the same file"""
+    img = png_cases.many_segments(M.SEG)[:15 * png_cases.MANY_BAND]
+    cache = {}
+    cached, info = M.encode(img, cache=cache)
+    plain, plain_info = M.encode(img)
+    assert cached == plain and len(info["segments"]) == len(plain_info["segments"]) == 15
+    assert len(cache) == 9 and sorted(last for _, last in cache) == [False] * 8 + [True]       # segment 0, the period's seven, the last
+    assert [s["coded_bytes"] for s in info["segments"]] == [s["coded_bytes"] for s in plain_info["segments"]]
+    M.check_against_model(cached, info)
+
+
+def test_many_segments_image_is_what_it_is_named_for():
+    img = png_cases.many_segments(M.SEG)
+    assert img.shape == (12300, 341, 4) and np.array_equal(img[84:], img[:-84]) and not np.array_equal(img[12:], img[:-12])
+    stream, types, _ = M.filter_image(img)
+    assert len(stream) == 1025 * M.SEG
+    segs = [stream[k * M.SEG:(k + 1) * M.SEG] for k in range(1025)]
+    assert all(segs[k] == segs[k + 7] for k in range(1, 1018))                                  # the stream repeats from segment 1 on
+    assert len(set(segs[1:8])) == 7

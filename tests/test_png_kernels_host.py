@@ -1,7 +1,8 @@
 """CPU tier: the PNG encoder's kernels (csrc/kernels_png.hip) compiled as host code over a stand-in for the HIP runtime header
 (tests/cpp/hip_host_shim), run thread for thread by the stand-alone program tests/cpp/png_kernels_host.cpp under the address and
 undefined-behaviour sanitizers, every buffer at its exact size, every file inflated with zlib and compared with its image; build_code
-on frequency tables that reach both length limits; and the kernels' files against the serial model's (tests/png_model.py), byte for byte."""
+on frequency tables that reach both length limits; the compaction scan with up to five sizes per thread against a serial prefix sum;
+and the kernels' files against the serial model's (tests/png_model.py), byte for byte."""
 import os
 import subprocess
 
@@ -25,6 +26,13 @@ def test_png_kernels_on_the_host(exe):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-3000:] + out.stderr[-3000:]
     assert "limit 7: longest 7" in out.stdout and "limit 15: longest 15" in out.stdout
+
+
+def test_scan_with_several_elements_per_thread(exe):
+    out = subprocess.run([exe, "scan"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-3000:] + out.stderr[-3000:]
+    for n, per in ((1, 1), (1023, 1), (1024, 1), (1025, 2), (2048, 2), (2049, 3), (5000, 5)):
+        assert "k_png_scan n = %d (%d per thread)" % (n, per) in out.stdout
 
 
 def host_cases():
