@@ -588,6 +588,62 @@ int pf_resize_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_src_bgra, in
 int pf_stitch_result_resized_dev(pf_ctx* ctx, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
 int pf_stitch_batch_result_resized_dev(pf_ctx* ctx, int frame, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
 
+/* ---- Reprojection on the device --------------------------------------------------------------
+ * A packed BGRA equirectangular sphere in HBM -> a cube face, a rectilinear view, or the sphere turned (re-levelled), without the
+ * image leaving the device.  For every output pixel: a ray, rotated by `rot`, its longitude and latitude, the source
+ * position, quantised to 1/256 pixel, and a bilinear (2 x 2) or Catmull-Rom (4 x 4) sample in integer arithmetic over colour
+ * premultiplied by alpha (as pf_resize premultiplies) and divided by it again.  The geometry is fp64 add, subtract, multiply, divide
+ * and sqrt with a polynomial arctangent, in a fixed order: the bytes are a function of the image, the sizes and the parameters.
+ *   frame     right-handed: x forward (the source's centre column), y to the right (increasing columns), z up.
+ *   source    cols x rows, 360 degrees across with square angular pixels, centred on the horizon: rows * 360 / cols degrees tall.
+ *             Columns wrap, rows clamp; a ray beyond half a pixel past the first or last row gives four zero bytes.
+ *   PF_PROJ_CUBE         out_cols == out_rows; face = PF_FACE_*.  The up face's bottom edge and the down face's top edge meet the front face.
+ *   PF_PROJ_RECTILINEAR  a view along +x of hfov_deg degrees across (0 < hfov_deg < 180), square pixels.
+ *   PF_PROJ_EQUIRECT     a sphere of out_cols x out_rows with the source's conventions: with a rotation, the source re-levelled.
+ *   rot       s = rot * d, row-major, passed as it is (it need not be a rotation).  pf_reproject_rotation makes
+ *             Rz(yaw) Ry(-pitch) Rx(roll) with the host's sin / cos: yaw turns the view to the right, pitch up, roll lifts its right side.
+ *   _dev      d_src_bgra: cols * rows * 4 bytes, d_dst_bgra: out_cols * out_rows * 4 bytes of this context's device, packed rows,
+ *             4-byte aligned.
+ *   pf_reproject  HOST memory on both sides, row steps in bytes; bytes of a destination row beyond out_cols * 4 are left untouched.
+ *   batch     n same-size images, one set of parameters -> the bytes of n single calls, their kernels enqueued together before one drain.
+ *   pf_reproject_cube_dev  the six faces (PF_FACE_* order) of face_size x face_size into six destinations, one launch; params'
+ *             projection and face are not read.
+ *   pf_stitch_result_reprojected_dev, pf_stitch_batch_result_reprojected_dev: from the composite the last pf_stitch_step left in
+ *             HBM, or frame slot `frame` of the last pf_stitch_step_batch; PF_ERR_ARG when none is resident, as pf_stitch_result_png.
+ *   pf_stage_reproject_coords  the quantised source coordinates (256 * position, rounded) of every output pixel as the device
+ *             computes them: two int32 planes of out_cols x out_rows in host memory.
+ * There is no antialiasing: an output that samples the source more coarsely than about one source pixel per output pixel aliases.
+ * Make a face of about cols / 4 (or any view near the source's scale) and shrink it with pf_resize_dev.  A result stays in HBM for
+ * pf_resize_dev, pf_png_encode_dev and pf_jpeg_encode_dev: chain them.  Opt-in: no other entry point's behaviour depends on these.
+ * PF_ERR_ARG with a message, before any device work, for: null pointers; sizes <= 0 or a side above 65535; more than 2e9 pixels
+ * on either side; an unknown projection, face (cube) or filter; a cube with out_cols != out_rows; hfov_deg outside (0, 180)
+ * (rectilinear); a non-finite entry of rot; a destination that overlaps a source.
+ * The scratch is the reprojection's own: these calls leave alone the chain state, the prefetch records, the frame slots, the plans
+ * and what pf_stitch_visualize reads.  Kernel family in pf_profile_*: reproject. */
+enum { PF_PROJ_CUBE = 0, PF_PROJ_RECTILINEAR = 1, PF_PROJ_EQUIRECT = 2 };
+enum { PF_FACE_FRONT = 0, PF_FACE_RIGHT = 1, PF_FACE_BACK = 2, PF_FACE_LEFT = 3, PF_FACE_UP = 4, PF_FACE_DOWN = 5 };
+enum { PF_REPROJECT_BILINEAR = 2, PF_REPROJECT_BICUBIC = 3 };   /* PF_RESIZE_*'s numbers */
+typedef struct pf_reproject_params {
+  int projection;   /* PF_PROJ_* */
+  int face;         /* cube only */
+  int filter;       /* PF_REPROJECT_* */
+  double hfov_deg;  /* rectilinear only */
+  double rot[9];
+} pf_reproject_params;
+void pf_reproject_params_init(pf_reproject_params* params);   /* the front face, bicubic, hfov 90, the identity rotation */
+void pf_reproject_rotation(double yaw_deg, double pitch_deg, double roll_deg, double* rot_out /* 9 */);   /* host only */
+int pf_reproject_dev(pf_ctx* ctx, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* d_dst_bgra, int out_cols, int out_rows,
+                     const pf_reproject_params* params);
+int pf_reproject(pf_ctx* ctx, const uint8_t* src_bgra, size_t src_step, int cols, int rows, uint8_t* dst_bgra, size_t dst_step, int out_cols, int out_rows,
+                 const pf_reproject_params* params);
+int pf_reproject_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows,
+                           const pf_reproject_params* params);
+int pf_reproject_cube_dev(pf_ctx* ctx, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* const* d_faces_bgra /* 6 */, int face_size,
+                          const pf_reproject_params* params);
+int pf_stitch_result_reprojected_dev(pf_ctx* ctx, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra);
+int pf_stitch_batch_result_reprojected_dev(pf_ctx* ctx, int frame, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra);
+int pf_stage_reproject_coords(pf_ctx* ctx, int cols, int rows, int out_cols, int out_rows, const pf_reproject_params* params, int32_t* fx_out, int32_t* fy_out);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

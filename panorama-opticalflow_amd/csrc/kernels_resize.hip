@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "pf_common.hpp"
+#include "premul.hpp"   // rz_premultiply, rz_unpremultiply
 
 namespace pf {
 namespace {
@@ -20,26 +21,6 @@ constexpr int kRzThreads = 256;
 constexpr int kRzTileX = 64, kRzTileY = 4;   // output pixels of a workgroup: a wave per row
 constexpr int kRzPiece = 256;                // source columns of the horizontal pass staged at a time (4 rows x 256 dwords = 4 KB of LDS)
 constexpr int kRzPrecBits = 22;
-
-// colour * alpha / 255, rounded, as Pillow's MULDIV255; alpha stays
-__device__ __forceinline__ uint32_t rz_premultiply(uint32_t v) {
-  const uint32_t a = v >> 24;
-  uint32_t out = v & 0xff000000u;
-  for (int s = 0; s < 24; s += 8) {
-    const uint32_t t = ((v >> s) & 0xffu) * a + 128u;
-    out |= (((t >> 8) + t) >> 8) << s;
-  }
-  return out;
-}
-
-// the inverse as Pillow's rgbA2rgba: a true integer division (c <= 255 and 1 <= a <= 254 here, so 255 * c fits easily)
-__device__ __forceinline__ uint32_t rz_unpremultiply(uint32_t v) {
-  const uint32_t a = v >> 24;
-  if (a == 0u || a == 255u) return v;
-  uint32_t out = v & 0xff000000u;
-  for (int s = 0; s < 24; s += 8) out |= min(255u, (255u * ((v >> s) & 0xffu)) / a) << s;
-  return out;
-}
 
 // Pillow accumulates in a 32-bit int; unsigned here, so that a table past the issue's bound wraps as the hardware does instead of being undefined
 struct RzAcc {

@@ -82,6 +82,8 @@ struct pf_ctx {
   // pf_resize*: the host's tables of the last few (in, out, filter) axes, and which of them sits in the arena's "rz_tab_h" / "rz_tab_v"
   std::vector<resize_table::Table> rz_tables;
   struct RzResident { const void* p = nullptr; size_t cap = 0; int in = 0, out = 0, filter = 0; } rz_dev[2];
+  // pf_reproject*: which tables sit in the arena's "rp_cubic" (the Catmull-Rom phases) and "rp_eq" (an equirect output's sines and cosines)
+  struct RpResident { const void* p = nullptr; size_t cap = 0; int out_cols = 0, out_rows = 0; } rp_cubic, rp_eq;
   bool tiff_inflate = false;         // pf_tiff_decode*: deflate strips decode on the device (pf_tiff_set_inflate); off: they are refused
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;

@@ -1,0 +1,220 @@
+// Part of pf_api.hip (one translation unit): the reprojection entry points.  The host checks the arguments, makes the tables a launch
+// reads (reproject_math.hpp: the Catmull-Rom phases once per context, the equirect output's sines and cosines per output size) and
+// launches k_reproject (kernels_reproject.hip); all geometry and sampling runs there.  The scratch ("rp_*") is the reprojection's own:
+// no entry point here touches the chain, the prefetch records, the batch slots, the plans or what pf_stitch_visualize reads.
+}  // extern "C"
+namespace {
+
+constexpr int kRpMaxSide = 65535;
+
+// everything known without an image pointer; on success *g holds the launch's geometry
+int reproject_check(pf_ctx* c, int cols, int rows, int out_cols, int out_rows, const pf_reproject_params* p, reproject::Geometry* g) {
+  if (!p) return fail(c, PF_ERR_ARG, "null pointer (params)");
+  if (int e = check_image(c, cols, rows)) return e;
+  if (out_cols <= 0 || out_rows <= 0) return fail(c, PF_ERR_ARG, "reproject: bad output size %dx%d", out_cols, out_rows);
+  if (cols > kRpMaxSide || rows > kRpMaxSide || out_cols > kRpMaxSide || out_rows > kRpMaxSide)
+    return fail(c, PF_ERR_ARG, "reproject: a side of %dx%d -> %dx%d is above %d", cols, rows, out_cols, out_rows, kRpMaxSide);
+  if ((double)out_cols * out_rows > 2.0e9) return fail(c, PF_ERR_ARG, "reproject: output %dx%d too large", out_cols, out_rows);
+  if (p->projection != PF_PROJ_CUBE && p->projection != PF_PROJ_RECTILINEAR && p->projection != PF_PROJ_EQUIRECT)
+    return fail(c, PF_ERR_ARG, "reproject: unknown projection %d (0 CUBE, 1 RECTILINEAR, 2 EQUIRECT)", p->projection);
+  if (p->filter != PF_REPROJECT_BILINEAR && p->filter != PF_REPROJECT_BICUBIC) return fail(c, PF_ERR_ARG, "reproject: unknown filter %d (2 BILINEAR, 3 BICUBIC)", p->filter);
+  g->t = 0.0;
+  if (p->projection == PF_PROJ_CUBE) {
+    if (p->face < PF_FACE_FRONT || p->face > PF_FACE_DOWN) return fail(c, PF_ERR_ARG, "reproject: unknown face %d (0 front, right, back, left, up, 5 down)", p->face);
+    if (out_cols != out_rows) return fail(c, PF_ERR_ARG, "reproject: a cube face is square, not %dx%d", out_cols, out_rows);
+  }
+  if (p->projection == PF_PROJ_RECTILINEAR) {
+    if (!(p->hfov_deg > 0.0 && p->hfov_deg < 180.0)) return fail(c, PF_ERR_ARG, "reproject: hfov %g outside (0, 180) degrees", p->hfov_deg);
+    g->t = reproject::tan_half_fov(p->hfov_deg);
+  }
+  for (int k = 0; k < 9; ++k) {
+    if (!std::isfinite(p->rot[k])) return fail(c, PF_ERR_ARG, "reproject: rot[%d] is not finite", k);
+    g->rot[k] = p->rot[k];
+  }
+  g->projection = p->projection; g->filter = p->filter;
+  g->cols = cols; g->rows = rows; g->out_cols = out_cols; g->out_rows = out_rows;
+  return 0;
+}
+
+// the tables in the arena: uploaded when the slot holds another size's or has moved
+int reproject_tables(pf_ctx* c, const reproject::Geometry& g, const double** d_eq, const int** d_cubic) {
+  *d_eq = nullptr; *d_cubic = nullptr;
+  if (g.filter == PF_REPROJECT_BICUBIC) {
+    int* d = (int*)ensure(c, "rp_cubic", 1024 * sizeof(int));
+    if (!d) return PF_ERR_NOMEM;
+    if (c->rp_cubic.p != d) {
+      int tab[1024];
+      reproject::make_cubic_table(tab);
+      HIPCHK(c, hipMemcpyAsync(d, tab, sizeof tab, hipMemcpyHostToDevice, c->s_main));
+      HIPCHK(c, hipStreamSynchronize(c->s_main));   // the table is on this frame
+      c->rp_cubic.p = d;
+    }
+    *d_cubic = d;
+  }
+  if (g.projection == PF_PROJ_EQUIRECT) {
+    const size_t count = 2 * (size_t(g.out_cols) + g.out_rows);
+    double* d = (double*)ensure(c, "rp_eq", count * sizeof(double));
+    if (!d) return PF_ERR_NOMEM;
+    pf_ctx::RpResident& r = c->rp_eq;
+    const size_t cap = c->bufs["rp_eq"].cap;   // (a slot that grew is a fresh allocation, wherever it landed)
+    if (r.p != d || r.cap != cap || r.out_cols != g.out_cols || r.out_rows != g.out_rows) {
+      r.p = nullptr;
+      std::vector<double> eq(count);
+      reproject::make_equirect_tables(g.out_cols, g.out_rows, eq.data());
+      HIPCHK(c, hipMemcpyAsync(d, eq.data(), count * sizeof(double), hipMemcpyHostToDevice, c->s_main));
+      HIPCHK(c, hipStreamSynchronize(c->s_main));
+      r.p = d; r.cap = cap; r.out_cols = g.out_cols; r.out_rows = g.out_rows;
+    }
+    *d_eq = d;
+  }
+  return 0;
+}
+
+// n device images of g.cols x g.rows -> n of g.out_cols x g.out_rows, enqueued on s_main in groups of kMaxBatch; the caller drains.
+// faces: null (every image takes `face`), or the face of each image.
+int reproject_many(pf_ctx* c, int n, const uint8_t* const* d_src, uint8_t* const* d_dst, const reproject::Geometry& g, int face, const int* faces) {
+  const size_t in_bytes = size_t(g.cols) * g.rows * 4, out_bytes = size_t(g.out_cols) * g.out_rows * 4;
+  for (int k = 0; k < n; ++k) {
+    if (!d_src[k] || !d_dst[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
+    if ((reinterpret_cast<uintptr_t>(d_src[k]) | reinterpret_cast<uintptr_t>(d_dst[k])) & 3) return fail(c, PF_ERR_ARG, "reproject: device image %d is not 4-byte aligned", k);
+  }
+  for (int k = 0; k < n; ++k)
+    for (int q = 0; q < n; ++q)
+      if (ranges_overlap(d_dst[k], out_bytes, d_src[q], in_bytes)) return fail(c, PF_ERR_ARG, "reproject: destination %d overlaps source %d", k, q);
+  ReprojectArgs a;
+  memset(&a, 0, sizeof a);
+  a.g = g;
+  if (int e = reproject_tables(c, g, &a.eq, &a.cubic)) return e;
+  for (int first = 0; first < n; first += kMaxBatch) {
+    const int count = std::min(kMaxBatch, n - first);
+    for (int k = 0; k < count; ++k) {
+      a.src[k] = (const uint32_t*)d_src[first + k]; a.dst[k] = (uint32_t*)d_dst[first + k];
+      a.face[k] = faces ? faces[first + k] : face;
+    }
+    PROF(c, c->s_main, "reproject");
+    launch_reproject(c->s_main, count, a);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+extern "C" {
+
+void pf_reproject_params_init(pf_reproject_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->projection = PF_PROJ_CUBE; p->face = PF_FACE_FRONT; p->filter = PF_REPROJECT_BICUBIC; p->hfov_deg = 90.0;
+  p->rot[0] = p->rot[4] = p->rot[8] = 1.0;
+}
+
+void pf_reproject_rotation(double yaw_deg, double pitch_deg, double roll_deg, double* rot_out) {
+  if (rot_out) reproject::rotation(yaw_deg, pitch_deg, roll_deg, rot_out);
+}
+
+int pf_reproject_dev(pf_ctx* c, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* d_dst_bgra, int out_cols, int out_rows, const pf_reproject_params* params) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_src_bgra || !d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  reproject::Geometry g;
+  if (int e = reproject_check(c, cols, rows, out_cols, out_rows, params, &g)) return e;
+  if (int e = reproject_many(c, 1, &d_src_bgra, &d_dst_bgra, g, params->face, nullptr)) return e;
+  return finish(c);
+}
+
+int pf_reproject(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, int rows, uint8_t* dst_bgra, size_t dst_step, int out_cols, int out_rows,
+                 const pf_reproject_params* params) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!src_bgra || !dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  reproject::Geometry g;
+  if (int e = reproject_check(c, cols, rows, out_cols, out_rows, params, &g)) return e;
+  if (src_step < size_t(cols) * 4 || dst_step < size_t(out_cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
+  if (ranges_overlap(dst_bgra, size_t(out_rows - 1) * dst_step + size_t(out_cols) * 4, src_bgra, size_t(rows - 1) * src_step + size_t(cols) * 4))
+    return fail(c, PF_ERR_ARG, "reproject: the destination overlaps the source");
+  uint8_t* d_src = (uint8_t*)ensure(c, "rp_src", size_t(cols) * rows * 4);
+  uint8_t* d_dst = (uint8_t*)ensure(c, "rp_dst", size_t(out_cols) * out_rows * 4);
+  if (!d_src || !d_dst) return PF_ERR_NOMEM;
+  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, src_step, size_t(cols) * 4, rows)) return e;
+  const uint8_t* dc = d_src;
+  if (int e = reproject_many(c, 1, &dc, &d_dst, g, params->face, nullptr)) return e;
+  if (int e = down2d(c, dst_bgra, dst_step, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  return finish(c);
+}
+
+int pf_reproject_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows,
+                           const pf_reproject_params* params) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (n < 0 || !d_src_bgra || !d_dst_bgra) return fail(c, PF_ERR_ARG, "bad argument");
+  reproject::Geometry g;
+  if (int e = reproject_check(c, cols, rows, out_cols, out_rows, params, &g)) return e;
+  if (n == 0) return 0;
+  if (int e = reproject_many(c, n, d_src_bgra, d_dst_bgra, g, params->face, nullptr)) return e;
+  return finish(c);
+}
+
+// the six faces of one source in one launch (blockIdx.z = face); params->projection and params->face are not read
+int pf_reproject_cube_dev(pf_ctx* c, const uint8_t* d_src_bgra, int cols, int rows, uint8_t* const* d_faces_bgra, int face_size, const pf_reproject_params* params) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_src_bgra || !d_faces_bgra || !params) return fail(c, PF_ERR_ARG, "null pointer");
+  pf_reproject_params p = *params;
+  p.projection = PF_PROJ_CUBE; p.face = PF_FACE_FRONT;
+  reproject::Geometry g;
+  if (int e = reproject_check(c, cols, rows, face_size, face_size, &p, &g)) return e;
+  const uint8_t* srcs[6];
+  int faces[6];
+  for (int k = 0; k < 6; ++k) { srcs[k] = d_src_bgra; faces[k] = k; }
+  if (int e = reproject_many(c, 6, srcs, d_faces_bgra, g, 0, faces)) return e;
+  return finish(c);
+}
+
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final"), read in place
+int pf_stitch_result_reprojected_dev(pf_ctx* c, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_reprojected_dev: no stitch step result in HBM");
+  reproject::Geometry g;
+  if (int e = reproject_check(c, c->chain_cols, c->chain_rows, out_cols, out_rows, params, &g)) return e;
+  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
+  if (int e = reproject_many(c, 1, &d, &d_dst_bgra, g, params->face, nullptr)) return e;
+  return finish(c);
+}
+
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+int pf_stitch_batch_result_reprojected_dev(pf_ctx* c, int frame, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_reprojected_dev: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
+  char name[32];
+  snprintf(name, sizeof name, "sb_fin%d", frame);
+  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
+  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_reprojected_dev: no batch result in frame slot %d", frame);
+  reproject::Geometry g;
+  if (int e = reproject_check(c, c->sb_cols, c->sb_rows, out_cols, out_rows, params, &g)) return e;
+  if (int e = reproject_many(c, 1, &d, &d_dst_bgra, g, params->face, nullptr)) return e;
+  return finish(c);
+}
+
+// stage entry: the quantised source coordinates of every output pixel as the DEVICE computes them, int32 planes of out_cols x out_rows
+int pf_stage_reproject_coords(pf_ctx* c, int cols, int rows, int out_cols, int out_rows, const pf_reproject_params* params, int32_t* fx_out, int32_t* fy_out) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!fx_out || !fy_out) return fail(c, PF_ERR_ARG, "null pointer");
+  ReprojectArgs a;
+  memset(&a, 0, sizeof a);
+  if (int e = reproject_check(c, cols, rows, out_cols, out_rows, params, &a.g)) return e;
+  const size_t bytes = size_t(out_cols) * out_rows * 4;
+  a.fx_out = (int*)ensure(c, "rp_fx", bytes); a.fy_out = (int*)ensure(c, "rp_fy", bytes);
+  if (!a.fx_out || !a.fy_out) return PF_ERR_NOMEM;
+  if (int e = reproject_tables(c, a.g, &a.eq, &a.cubic)) return e;
+  a.face[0] = params->face;
+  { PROF(c, c->s_main, "reproject"); launch_reproject(c->s_main, 1, a); }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(fx_out, a.fx_out, bytes, hipMemcpyDeviceToHost, c->s_main));
+  HIPCHK(c, hipMemcpyAsync(fy_out, a.fy_out, bytes, hipMemcpyDeviceToHost, c->s_main));
+  return finish(c);
+}

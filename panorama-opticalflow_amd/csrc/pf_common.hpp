@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "tile_stream_plan.hpp"
+#include "reproject_math.hpp"
 
 namespace pf {
 
@@ -266,6 +267,17 @@ struct ResizePtrs { const uint32_t* src[kMaxBatch]; uint32_t* dst[kMaxBatch]; };
 // bounds: per output index {first source index, taps}; k: 22-bit fixed-point coefficients, tap-major (k[t * out + index])
 void launch_resize_h(hipStream_t st, int n, const ResizePtrs& io, int cols, int rows, int out_cols, const int* bounds, const int* k, bool premul, bool unpremul);   // cols x rows -> out_cols x rows
 void launch_resize_v(hipStream_t st, int n, const ResizePtrs& io, int cols, int rows, int out_rows, const int* bounds, const int* k, bool premul, bool unpremul);   // cols x rows -> cols x out_rows
+
+// ---- reprojection (kernels_reproject.hip): an equirectangular sphere -> cube faces, a rectilinear view, a turned sphere; the host makes the tables ----
+struct ReprojectArgs {
+  const uint32_t* src[kMaxBatch]; uint32_t* dst[kMaxBatch];   // blockIdx.z = image, n <= kMaxBatch per launch; dst null: coordinates only
+  int face[kMaxBatch];                                        // cube: the face of image z
+  reproject::Geometry g;
+  const double* eq;      // equirect output: cos lon, sin lon (out_cols each), cos lat, sin lat (out_rows each)
+  const int* cubic;      // bicubic: 256 phases x 4 taps (reproject::make_cubic_table)
+  int* fx_out; int* fy_out;   // null, or out_cols x out_rows planes that take the quantised coordinates (pf_stage_reproject_coords, n = 1)
+};
+void launch_reproject(hipStream_t st, int n, const ReprojectArgs& a);
 
 // ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits, deflate), then predictor + RGB(A) -> BGRA per row ----
 // A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled

@@ -59,6 +59,11 @@ class JpegParams(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("quality", C.c_int), ("subsampling", C.c_int), ("gpano", C.c_int)]
 
 
+class ReprojectParams(C.Structure):
+    """pf_reproject_params (include/panoflow.h)"""
+    _fields_ = [("projection", C.c_int), ("face", C.c_int), ("filter", C.c_int), ("hfov_deg", C.c_double), ("rot", C.c_double * 9)]
+
+
 class TiffInfo(C.Structure):
     """pf_tiff_info (include/panoflow.h)"""
     _fields_ = [(n, C.c_int) for n in ("struct_size", "cols", "rows", "samples", "compression", "predictor", "rows_per_strip", "n_strips", "big_endian",
@@ -132,6 +137,18 @@ def lib(exp=False):
         _lib.pf_resize_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _lib.pf_stitch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.pf_stitch_batch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        rp = C.POINTER(ReprojectParams)
+        _lib.pf_reproject_params_init.restype = None
+        _lib.pf_reproject_params_init.argtypes = [rp]
+        _lib.pf_reproject_rotation.restype = None
+        _lib.pf_reproject_rotation.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+        _lib.pf_reproject_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, rp]
+        _lib.pf_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, rp]
+        _lib.pf_reproject_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, rp]
+        _lib.pf_reproject_cube_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, rp]
+        _lib.pf_stitch_result_reprojected_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, rp, C.c_void_p]
+        _lib.pf_stitch_batch_result_reprojected_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, rp, C.c_void_p]
+        _lib.pf_stage_reproject_coords.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, rp, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -156,6 +173,8 @@ EXPORTS = [
     "pf_stitch_result_jpeg", "pf_stitch_batch_result_jpeg",
     "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
     "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev",
+    "pf_reproject_params_init", "pf_reproject_rotation", "pf_reproject_dev", "pf_reproject", "pf_reproject_batch_dev", "pf_reproject_cube_dev",
+    "pf_stitch_result_reprojected_dev", "pf_stitch_batch_result_reprojected_dev", "pf_stage_reproject_coords",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -210,6 +229,35 @@ def jpeg_restart_interval(subsampling):
 
 # PF_RESIZE_* (Pillow's numbering of its resampling filters)
 RESIZE_LANCZOS, RESIZE_BILINEAR, RESIZE_BICUBIC, RESIZE_BOX, RESIZE_HAMMING = 1, 2, 3, 4, 5
+
+
+# PF_PROJ_*, PF_FACE_*, PF_REPROJECT_*
+PROJ_CUBE, PROJ_RECTILINEAR, PROJ_EQUIRECT = 0, 1, 2
+FACE_FRONT, FACE_RIGHT, FACE_BACK, FACE_LEFT, FACE_UP, FACE_DOWN = range(6)
+FACE_NAMES = ("front", "right", "back", "left", "up", "down")
+REPROJECT_BILINEAR, REPROJECT_BICUBIC = 2, 3
+
+
+def reproject_rotation(yaw_deg=0.0, pitch_deg=0.0, roll_deg=0.0):
+    """the nine doubles of Rz(yaw) Ry(-pitch) Rx(roll), row-major (pf_reproject_rotation: host only)"""
+    r = (C.c_double * 9)()
+    lib().pf_reproject_rotation(float(yaw_deg), float(pitch_deg), float(roll_deg), r)
+    return list(r)
+
+
+def reproject_params(projection=None, face=None, filter=None, hfov_deg=None, rot=None):
+    """a ReprojectParams with the library's defaults (pf_reproject_params_init) and the given fields over them"""
+    p = ReprojectParams()
+    lib().pf_reproject_params_init(C.byref(p))
+    for name, v in (("projection", projection), ("face", face), ("filter", filter)):
+        if v is not None:
+            setattr(p, name, int(v))
+    if hfov_deg is not None:
+        p.hfov_deg = float(hfov_deg)
+    if rot is not None:
+        for k, v in enumerate(rot):
+            p.rot[k] = float(v)
+    return p
 
 
 def tiff_probe(data):
@@ -738,6 +786,46 @@ class Context:
     def stitch_batch_result_resized_dev(self, frame, out_cols, out_rows, d_dst, filter=RESIZE_LANCZOS):
         """frame slot `frame` of the last stitch_step_batch, resized into d_dst"""
         self._chk(self.l.pf_stitch_batch_result_resized_dev(self.h, frame, out_cols, out_rows, int(filter), C.c_void_p(d_dst)))
+
+    # ---- reprojection on the device (pf_reproject*): params = a ReprojectParams (reproject_params()) ----
+    def reproject(self, image, out_cols, out_rows, params, out=None):
+        """host BGRA (rows, cols, 4) equirectangular sphere, any row stride -> host (out_rows, out_cols, 4); out: a destination array (its row stride is kept)"""
+        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+        if a.strides[2] != 1 or a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        if out is None:
+            out = np.empty((max(out_rows, 0), max(out_cols, 0), 4), np.uint8)
+        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(out_cols, 0) * 4
+        self._chk(self.l.pf_reproject(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, _p(out), C.c_size_t(step), out_cols, out_rows, C.byref(params)))
+        return out
+
+    def reproject_dev(self, d_src, cols, rows, d_dst, out_cols, out_rows, params):
+        self._chk(self.l.pf_reproject_dev(self.h, C.c_void_p(d_src), cols, rows, C.c_void_p(d_dst), out_cols, out_rows, C.byref(params)))
+
+    def reproject_batch_dev(self, d_srcs, cols, rows, d_dsts, out_cols, out_rows, params):
+        """n same-size device images -> n device images of out_cols x out_rows, one drain"""
+        n = len(d_srcs)
+        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_srcs]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_dsts])
+        self._chk(self.l.pf_reproject_batch_dev(self.h, n, srcs, cols, rows, dsts, out_cols, out_rows, C.byref(params)))
+
+    def reproject_cube_dev(self, d_src, cols, rows, d_faces, face_size, params):
+        """one device sphere -> six device faces of face_size x face_size (FACE_* order), one launch"""
+        dsts = (C.c_void_p * 6)(*[C.c_void_p(int(x)) for x in d_faces])
+        self._chk(self.l.pf_reproject_cube_dev(self.h, C.c_void_p(d_src), cols, rows, dsts, face_size, C.byref(params)))
+
+    def stitch_result_reprojected_dev(self, out_cols, out_rows, params, d_dst):
+        """the composite the last stitch_step left in HBM, reprojected into d_dst (out_cols * out_rows * 4 bytes of device memory)"""
+        self._chk(self.l.pf_stitch_result_reprojected_dev(self.h, out_cols, out_rows, C.byref(params), C.c_void_p(d_dst)))
+
+    def stitch_batch_result_reprojected_dev(self, frame, out_cols, out_rows, params, d_dst):
+        """frame slot `frame` of the last stitch_step_batch, reprojected into d_dst"""
+        self._chk(self.l.pf_stitch_batch_result_reprojected_dev(self.h, frame, out_cols, out_rows, C.byref(params), C.c_void_p(d_dst)))
+
+    def stage_reproject_coords(self, cols, rows, out_cols, out_rows, params):
+        """(fx, fy): the device's quantised source coordinates of every output pixel, int32 (out_rows, out_cols)"""
+        fx = np.empty((out_rows, out_cols), np.int32); fy = np.empty((out_rows, out_cols), np.int32)
+        self._chk(self.l.pf_stage_reproject_coords(self.h, cols, rows, out_cols, out_rows, C.byref(params), _p(fx), _p(fy)))
+        return fx, fy
 
     # ---- device-resident entry points (raw device pointers as ints) ----
     def dev_alloc(self, nbytes):

@@ -250,13 +250,34 @@ struct DeviceImage {
   DeviceImage(const DeviceImage&) = delete;
   DeviceImage& operator=(const DeviceImage&) = delete;
 };
-static inline int resize_host_image(pf_ctx* ctx, const Mat& bgra, int out_cols, int out_rows, int filter, unsigned char* d_dst) {
-  if (bgra.type() != panocv::CV_8UC4) throw VrCamException("resize_host_image expects CV_8UC4");
-  DeviceImage src(ctx, bgra.cols, bgra.rows);
+// a host image (any row step) into a packed device image of its size
+static inline int upload_host_image(pf_ctx* ctx, const Mat& bgra, unsigned char* d_dst) {
+  if (bgra.type() != panocv::CV_8UC4) throw VrCamException("upload_host_image expects CV_8UC4");
   const size_t row = size_t(bgra.cols) * 4;
-  if (bgra.step == row) { if (int rc = pf_upload(ctx, src.p, bgra.data, row * bgra.rows)) return rc; }
-  else for (int y = 0; y < bgra.rows; ++y) if (int rc = pf_upload(ctx, src.p + y * row, bgra.data + size_t(y) * bgra.step, row)) return rc;
+  if (bgra.step == row) return pf_upload(ctx, d_dst, bgra.data, row * bgra.rows);
+  for (int y = 0; y < bgra.rows; ++y) if (int rc = pf_upload(ctx, d_dst + y * row, bgra.data + size_t(y) * bgra.step, row)) return rc;
+  return 0;
+}
+static inline int resize_host_image(pf_ctx* ctx, const Mat& bgra, int out_cols, int out_rows, int filter, unsigned char* d_dst) {
+  DeviceImage src(ctx, bgra.cols, bgra.rows);
+  if (int rc = upload_host_image(ctx, bgra, src.p)) return rc;
   return pf_resize_dev(ctx, src.p, bgra.cols, bgra.rows, d_dst, out_cols, out_rows, filter);
+}
+// A result wherever the mode left it (include/panoflow.h, "Reprojection on the device"): the composite the last pf_stitch_step left in
+// HBM, a frame slot of the last batched step, or a packed device image; reproject_result turns, views or cuts a cube face from it there.
+struct ResultSource {
+  enum Kind { kResident, kSlot, kDevice } kind;
+  int frame;                 // kSlot
+  const unsigned char* d;    // kDevice
+  int cols, rows;
+  static ResultSource resident(int cols, int rows) { return ResultSource{kResident, 0, nullptr, cols, rows}; }
+  static ResultSource slot(int frame, int cols, int rows) { return ResultSource{kSlot, frame, nullptr, cols, rows}; }
+  static ResultSource device(const unsigned char* d, int cols, int rows) { return ResultSource{kDevice, 0, d, cols, rows}; }
+};
+static inline int reproject_result(pf_ctx* ctx, const ResultSource& s, int out_cols, int out_rows, const pf_reproject_params& params, unsigned char* d_dst) {
+  if (s.kind == ResultSource::kResident) return pf_stitch_result_reprojected_dev(ctx, out_cols, out_rows, &params, d_dst);
+  if (s.kind == ResultSource::kSlot) return pf_stitch_batch_result_reprojected_dev(ctx, s.frame, out_cols, out_rows, &params, d_dst);
+  return pf_reproject_dev(ctx, s.d, s.cols, s.rows, d_dst, out_cols, out_rows, &params);
 }
 static inline Mat read_png(const std::string& path) {
   const std::vector<unsigned char> b = read_file(path);

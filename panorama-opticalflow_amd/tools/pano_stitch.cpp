@@ -46,13 +46,23 @@
 //   the composite and the encoder (pf_resize_*: Pillow's Image.resize of the RGBA image, byte for byte; lanczos by default).  The chain
 //   itself stays at full size.  Where the composite lies in HBM it is resized from there; where the mode holds it on the host it is sent
 //   up once and resized there.  The -visualize panels are not scaled.  With -jpeg_gpano 1 it is W x H that must be 2:1.
+//   -level yaw,pitch,roll (degrees; any mode; needs -png_device 1 or -jpeg_device 1): every result file of the run is the composite turned
+//   on the GPU at the canvas's size (pf_reproject_*: equirect to equirect, bicubic; yaw turns the view to the right, pitch up, roll lifts
+//   its right side), before -result_size and before the encoder.  The chain itself runs on the unturned composites.  The shape does not
+//   change, so the -jpeg_gpano rules are the same.
+//   -cube N [-cube_filter bicubic|bilinear] (any mode; needs -png_device 1 or -jpeg_device 1): beside every result file <stem>.(png|jpg) six
+//   cube faces <stem>_front|right|back|left|up|down.(png|jpg) of N x N are written, cut on the GPU from the result at the canvas's size
+//   (the levelled one with -level) and encoded where they lie; -result_size does not apply to them, nor does -jpeg_gpano.  There is no
+//   antialiasing: choose N near a quarter of the canvas's width.
 #include <sys/stat.h>
 
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -83,8 +93,52 @@ static void writeResized(const std::string& stem, Resize resize) {
   if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", ctx, g_jpeg, d.p, d.cols, d.rows);
   else pano_io::write_png_bytes(stem + ".png", ctx, d.cols, d.rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_png_encode_dev(ctx, d.p, d.cols, d.rows, b, cap, n); });
 }
+static bool g_level = false;         // -level yaw,pitch,roll
+static double g_level_rot[9];
+static int g_cube = 0, g_cube_filter = PF_REPROJECT_BICUBIC;   // -cube N -cube_filter
+// <stem>.jpg or <stem>.png of a packed device image
+static void writeDeviceImage(const std::string& stem, const unsigned char* d, int cols, int rows, const pf_jpeg_params& jpeg) {
+  pf_ctx* ctx = pano::context();
+  if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", ctx, jpeg, d, cols, rows);
+  else pano_io::write_png_bytes(stem + ".png", ctx, cols, rows, [&](unsigned char* b, size_t cap, size_t* n) { return pf_png_encode_dev(ctx, d, cols, rows, b, cap, n); });
+}
+// -level and -cube: with -level the result file itself, from the composite turned at its own size (then -result_size, then the encoder); with
+// -cube the six faces beside it, from the turned composite if there is one.  Nothing but the encoded files comes down.
+static void writeReprojected(const std::string& stem, pano_io::ResultSource src) {
+  pf_ctx* ctx = pano::context();
+  std::unique_ptr<pano_io::DeviceImage> level;
+  pf_reproject_params p;
+  pf_reproject_params_init(&p);
+  if (g_level) {
+    level.reset(new pano_io::DeviceImage(ctx, src.cols, src.rows));
+    p.projection = PF_PROJ_EQUIRECT;
+    for (int k = 0; k < 9; ++k) p.rot[k] = g_level_rot[k];
+    pano::check(pano_io::reproject_result(ctx, src, src.cols, src.rows, p, level->p));
+    src = pano_io::ResultSource::device(level->p, src.cols, src.rows);
+    if (g_result_cols) writeResized(stem, [&](unsigned char* d) { return pf_resize_dev(ctx, src.d, src.cols, src.rows, d, g_result_cols, g_result_rows, g_result_filter); });
+    else writeDeviceImage(stem, src.d, src.cols, src.rows, g_jpeg);
+  }
+  if (!g_cube) return;
+  static const char* const names[6] = {"front", "right", "back", "left", "up", "down"};
+  std::unique_ptr<pano_io::DeviceImage> faces[6];
+  unsigned char* d_faces[6];
+  for (int f = 0; f < 6; ++f) { faces[f].reset(new pano_io::DeviceImage(ctx, g_cube, g_cube)); d_faces[f] = faces[f]->p; }
+  pf_reproject_params_init(&p);   // the identity: a turn is in the source already
+  p.filter = g_cube_filter;
+  if (src.kind == pano_io::ResultSource::kDevice) pano::check(pf_reproject_cube_dev(ctx, src.d, src.cols, src.rows, d_faces, g_cube, &p));
+  else for (int f = 0; f < 6; ++f) { p.face = f; pano::check(pano_io::reproject_result(ctx, src, g_cube, g_cube, p, d_faces[f])); }
+  pf_jpeg_params plain = g_jpeg;
+  plain.gpano = 0;
+  for (int f = 0; f < 6; ++f) writeDeviceImage(stem + "_" + names[f], d_faces[f], g_cube, g_cube, plain);
+}
 // a host result image to <stem>.png, or with -jpeg_device 1 to <stem>.jpg; with -result_size sent up once and resized there
 static void writeResult(const std::string& stem, const Mat& image) {
+  if (g_level || g_cube) {
+    pano_io::DeviceImage up(pano::context(), image.cols, image.rows);
+    pano::check(pano_io::upload_host_image(pano::context(), image, up.p));
+    writeReprojected(stem, pano_io::ResultSource::device(up.p, image.cols, image.rows));
+    if (g_level) return;
+  }
   if (g_result_cols) return writeResized(stem, [&](unsigned char* d) { return pano_io::resize_host_image(pano::context(), image, g_result_cols, g_result_rows, g_result_filter, d); });
   if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, image);
   else writeImage(stem + ".png", image);
@@ -243,6 +297,8 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
     prev0 = outs[0];
     for (int k = 0; k < n; ++k) {
       const std::string stem = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
+      if (g_level || g_cube) writeReprojected(stem, pano_io::ResultSource::slot(k, Ls[0].cols, Ls[0].rows));
+      if (g_level) continue;
       if (g_result_cols) writeResized(stem, [&](unsigned char* d) { return pf_stitch_batch_result_resized_dev(pano::context(), k, g_result_cols, g_result_rows, g_result_filter, d); });
       else if (g_jpeg_device) pano_io::write_jpeg_device(stem + ".jpg", pano::context(), g_jpeg, k, Ls[0].cols, Ls[0].rows);
       else if (g_png_device) pano_io::write_png_device(stem + ".png", pano::context(), k, Ls[0].cols, Ls[0].rows);
@@ -362,6 +418,8 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
     for (int i = 1; i <= nsteps; ++i) {
       const uint8_t* d = o[size_t(k) * nsteps + i - 1];
       const std::string path = dirs[k] + "/" + (i == nsteps ? std::string("FinalResult.png") : std::string("ProcessResult") + char(i + 48) + ".png");
+      if (g_level || g_cube) writeReprojected(path.substr(0, path.size() - 4), pano_io::ResultSource::device(d, cols, rows));
+      if (g_level) continue;
       if (g_result_cols) {
         writeResized(path.substr(0, path.size() - 4), [&](unsigned char* dst) { return pf_resize_dev(ctx, d, cols, rows, dst, g_result_cols, g_result_rows, g_result_filter); });
       } else if (g_jpeg_device) {
@@ -404,6 +462,23 @@ int main(int argc, char** argv) {
       g_result_filter = filters.at(name);
       if (g_jpeg_device && g_jpeg.gpano && g_result_cols != 2 * g_result_rows) throw VrCamException("-jpeg_gpano 1 declares a full sphere, which -result_size " + flags["result_size"] + " (not 2:1) is not");
     } else if (flags.count("result_filter")) throw VrCamException("-result_filter needs -result_size WxH");
+    if (flags.count("level")) {   // every refusal before any device call
+      double ypr[3];
+      char tail = 0;
+      if (sscanf(flags["level"].c_str(), "%lf,%lf,%lf%c", &ypr[0], &ypr[1], &ypr[2], &tail) != 3 || !std::isfinite(ypr[0]) || !std::isfinite(ypr[1]) || !std::isfinite(ypr[2]))
+        throw VrCamException("-level must be yaw,pitch,roll in degrees, e.g. 0,-2.5,1");
+      if (!g_png_device && !g_jpeg_device) throw VrCamException("-level needs -png_device 1 or -jpeg_device 1 (the results are turned and encoded on the GPU)");
+      pf_reproject_rotation(ypr[0], ypr[1], ypr[2], g_level_rot);
+      g_level = true;
+    }
+    if (flags.count("cube")) {
+      char tail = 0;
+      if (sscanf(flags["cube"].c_str(), "%d%c", &g_cube, &tail) != 1 || g_cube <= 0 || g_cube > 65535) throw VrCamException("-cube must be the faces' size N, 1..65535");
+      if (!g_png_device && !g_jpeg_device) throw VrCamException("-cube needs -png_device 1 or -jpeg_device 1 (the faces are cut and encoded on the GPU)");
+      const std::string name = flags.count("cube_filter") ? flags["cube_filter"] : "bicubic";
+      if (name != "bicubic" && name != "bilinear") throw VrCamException("-cube_filter must be bicubic or bilinear");
+      g_cube_filter = name == "bicubic" ? PF_REPROJECT_BICUBIC : PF_REPROJECT_BILINEAR;
+    } else if (flags.count("cube_filter")) throw VrCamException("-cube_filter needs -cube N");
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
@@ -486,7 +561,10 @@ int main(int argc, char** argv) {
       }
 
       const std::string resultStem = FLAGS_test_dir + "/" + (i == nsteps ? std::string("FinalResult") : std::string("ProcessResult") + char(i + 48));
-      if (fused && g_result_cols) writeResized(resultStem, [&](unsigned char* d) { return pf_stitch_result_resized_dev(pano::context(), g_result_cols, g_result_rows, g_result_filter, d); });
+      const bool resident = fused && (g_png_device || g_jpeg_device);   // the composite lies in HBM, not in FinalResult
+      if (resident && (g_level || g_cube)) writeReprojected(resultStem, pano_io::ResultSource::resident(colorImageL.cols, colorImageL.rows));
+      if (resident && g_level) {}   // written above: the turned composite is the result
+      else if (fused && g_result_cols) writeResized(resultStem, [&](unsigned char* d) { return pf_stitch_result_resized_dev(pano::context(), g_result_cols, g_result_rows, g_result_filter, d); });
       else if (fused && g_jpeg_device) pano_io::write_jpeg_device(resultStem + ".jpg", pano::context(), g_jpeg, colorImageL.cols, colorImageL.rows);
       else if (fused && g_png_device) pano_io::write_png_device(resultStem + ".png", pano::context(), colorImageL.cols, colorImageL.rows);
       else writeResult(resultStem, FinalResult);
