@@ -644,6 +644,61 @@ int pf_stitch_result_reprojected_dev(pf_ctx* ctx, int out_cols, int out_rows, co
 int pf_stitch_batch_result_reprojected_dev(pf_ctx* ctx, int frame, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra);
 int pf_stage_reproject_coords(pf_ctx* ctx, int cols, int rows, int out_cols, int out_rows, const pf_reproject_params* params, int32_t* fx_out, int32_t* fy_out);
 
+/* ---- Lens remap on the device ------------------------------------------------------------------
+ * Raw photos of a camera rig in HBM -> each camera's equirectangular canvas, the warp the stitcher's inputs have been through
+ * (DESIGN.md 8.7): the inverse of the reprojection above.  For every canvas pixel: its ray, rotated into the camera by `rot`, the
+ * lens model's radius, the radial polynomial, the position in the photo, quantised to 1/256 pixel, and the reprojection's bilinear
+ * or Catmull-Rom sample over premultiplied colour (a photo's alpha channel, its mask, is kept).  The geometry is fp64 add, subtract,
+ * multiply, divide and sqrt with the reprojection's polynomial arctangent, in a fixed order: the bytes are a function of the photo,
+ * the sizes and the lens.
+ *   canvas    cols x rows BGRA with the reprojection's source conventions: 360 degrees across, square angular pixels, centred on
+ *             the horizon; frame x forward, y right, z up.
+ *   camera    c = rot * d, row-major, used as passed.  The optical axis is +x, image right +y, image up +z.  A camera posed by
+ *             pf_reproject_rotation(yaw, pitch, roll) = R takes rot = R transposed: pf_lens_rotation writes that.
+ *   outside   four zero bytes: |c| == 0; c.x <= min_cos * |c| (pf_lens_init: 0 for rectilinear, -0.5 for the fisheyes); for the
+ *             stereographic and equisolid models |c| + c.x <= 0; a position that is no number within +-1e9; a position more than
+ *             half a pixel off the photo; with crop_r256 > 0 a position outside the circle (crop_cx256, crop_cy256, crop_r256),
+ *             integers in 1/256 pixel: the image circle of a circular fisheye.  Taps clamp to the photo in both axes.
+ *   model     the ideal radius r = focal_px * g with rho = sqrt(c.y^2 + c.z^2), n = |c|:
+ *             PF_LENS_RECTILINEAR rho / c.x;  PF_LENS_FISHEYE_EQUIDISTANT atan2(rho, c.x);
+ *             PF_LENS_FISHEYE_STEREOGRAPHIC 2 rho / (n + c.x);  PF_LENS_FISHEYE_EQUISOLID 2 rho / sqrt(2 n (n + c.x)).
+ *             pf_lens_focal makes focal_px from the photo's width and its horizontal field of view in degrees (host libm).
+ *   polynomial  the panotools convention, applied canvas -> photo: rn = r / (min(photo_cols, photo_rows) / 2),
+ *             r_src = r * (((a rn + b) rn + c) rn + dd); pf_lens_init sets a = b = c = 0 and dd = 1.
+ *   position  px = photo_cols / 2 - 1/2 + shift_x + (r_src / rho) c.y,  py = photo_rows / 2 - 1/2 + shift_y - (r_src / rho) c.z.
+ *   _dev      d_photo: photo_cols * photo_rows * 4 bytes, d_canvas: cols * rows * 4 bytes of this context's device, packed rows,
+ *             4-byte aligned.
+ *   pf_lens_remap  HOST memory on both sides, row steps in bytes; bytes of a canvas row beyond cols * 4 are left untouched.
+ *   batch     n same-size photos -> n same-size canvases, image k under lenses[k] (its filter included): the bytes of n single
+ *             calls, up to 16 images per launch, one drain.  A rig's photos become its canvases in one launch.
+ *   pf_stage_lens_coords  the quantised photo coordinates (256 * position, rounded) of every canvas pixel as the device computes
+ *             them, two int32 planes of cols x rows in host memory; a pixel with no position has fx = 0, fy = INT32_MIN.
+ * There is no antialiasing: use a canvas near the photo's angular resolution.  No vignetting, exposure or white-balance correction,
+ * no tangential or shear terms.  Opt-in: no other entry point's behaviour depends on these.
+ * PF_ERR_ARG with a message, before any device work, for: null pointers; sizes <= 0 or a side above 65535; more than 2e9 pixels on
+ * either side; an unknown model or filter; a focal_px, polynomial coefficient, shift, min_cos or rot entry that is not finite;
+ * focal_px <= 0; min_cos outside [-1, 1), or below 0 for rectilinear; a negative crop_r256; a canvas that overlaps a photo; device
+ * pointers that are not 4-byte aligned.
+ * The scratch is the remap's own: these calls leave alone the chain state, the frame slots, the plans and the reprojection's
+ * scratch.  Kernel family in pf_profile_*: lens. */
+enum { PF_LENS_RECTILINEAR = 0, PF_LENS_FISHEYE_EQUIDISTANT = 1, PF_LENS_FISHEYE_STEREOGRAPHIC = 2, PF_LENS_FISHEYE_EQUISOLID = 3 };
+typedef struct pf_lens {
+  int model;    /* PF_LENS_* */
+  int filter;   /* PF_REPROJECT_* */
+  double focal_px, a, b, c, dd, shift_x, shift_y, min_cos;
+  int crop_cx256, crop_cy256, crop_r256;
+  double rot[9];
+} pf_lens;
+void pf_lens_init(pf_lens* lens, int model);   /* bicubic, dd = 1, the model's min_cos, the identity rotation; focal_px = 0: set it (pf_lens_focal) */
+double pf_lens_focal(int model, int photo_cols, double hfov_deg);   /* host only; 0 for an unknown model */
+void pf_lens_rotation(double yaw_deg, double pitch_deg, double roll_deg, double* rot_out /* 9 */);   /* host only */
+int pf_lens_remap_dev(pf_ctx* ctx, const uint8_t* d_photo_bgra, int photo_cols, int photo_rows, uint8_t* d_canvas_bgra, int cols, int rows, const pf_lens* lens);
+int pf_lens_remap(pf_ctx* ctx, const uint8_t* photo_bgra, size_t photo_step, int photo_cols, int photo_rows, uint8_t* canvas_bgra, size_t canvas_step, int cols, int rows,
+                  const pf_lens* lens);
+int pf_lens_remap_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_photos_bgra, int photo_cols, int photo_rows, uint8_t* const* d_canvases_bgra, int cols, int rows,
+                            const pf_lens* lenses /* n */);
+int pf_stage_lens_coords(pf_ctx* ctx, int photo_cols, int photo_rows, int cols, int rows, const pf_lens* lens, int32_t* fx_out, int32_t* fy_out);
+
 /* ---- per-kernel-family timing (HIP events on the streams the kernels run on) ---------------- */
 int pf_profile_enable(pf_ctx* ctx, int on);   /* 0 off, 1 all kernel families, 2 only the sweep kernels */
 int pf_profile_reset(pf_ctx* ctx);

@@ -2,7 +2,7 @@
 // turned sphere.  One kernel, k_reproject<filter>, one thread per output pixel: the pixel's ray, the rotation, the source position
 // in fp64 (reproject_math.hpp: add, subtract, multiply, divide, sqrt and a polynomial arctangent, nothing fused, no libm), quantised to
 // 8 fractional bits; then 2 x 2 (bilinear) or 4 x 4 (Catmull-Rom) taps in integer arithmetic over alpha-premultiplied colour
-// (premul.hpp, the resize's own functions), columns wrapped modulo the width, rows clamped, and one dword store.
+// (reproject_sample.hpp over premul.hpp, the resize's own functions), columns wrapped modulo the width, rows clamped, and one dword store.
 // A wave owns a 16 x 4 tile of the output and a workgroup 32 x 8, so that the footprints of a wave's taps share cache lines; the taps
 // are direct dword loads.  blockIdx.z is the image of a batch (or the face of a cube set: each image has its own face index); the
 // tiles of an image are walked with a grid stride.  No LDS, no barrier.
@@ -10,7 +10,7 @@
 #include <algorithm>
 
 #include "pf_common.hpp"
-#include "premul.hpp"
+#include "reproject_sample.hpp"
 
 namespace pf {
 namespace {
@@ -18,50 +18,6 @@ namespace {
 constexpr int kRpThreads = 256;
 constexpr int kRpWaveX = 16, kRpWaveY = 4;    // output pixels of a wave
 constexpr int kRpTileX = 32, kRpTileY = 8;    // ... of a workgroup: 2 x 2 waves
-
-__device__ __forceinline__ int rp_wrap(int x, int n) {   // a true modulo; the taps of a pixel reach at most two columns past either edge
-  while (x < 0) x += n;
-  while (x >= n) x -= n;
-  return x;
-}
-
-__device__ __forceinline__ uint32_t rp_bilinear(const uint32_t* __restrict__ src, int cols, int rows, int fx, int fy) {
-  const int x0 = fx >> 8, y0 = fy >> 8;
-  const uint32_t wx[2] = {256u - uint32_t(fx & 255), uint32_t(fx & 255)}, wy[2] = {256u - uint32_t(fy & 255), uint32_t(fy & 255)};
-  uint32_t acc[4] = {32768u, 32768u, 32768u, 32768u};
-  for (int j = 0; j < 2; ++j) {
-    const uint32_t* row = src + size_t(min(max(y0 + j, 0), rows - 1)) * cols;
-    for (int i = 0; i < 2; ++i) {
-      const uint32_t p = rz_premultiply(row[rp_wrap(x0 + i, cols)]), w = wx[i] * wy[j];
-      for (int c = 0; c < 4; ++c) acc[c] += w * ((p >> (8 * c)) & 0xffu);
-    }
-  }
-  uint32_t out = 0;
-  for (int c = 0; c < 4; ++c) out |= (acc[c] >> 16) << (8 * c);
-  return rz_unpremultiply(out);
-}
-
-// tab: 256 phases x 4 taps, each phase summing to 2048.  |sum of wx wy| <= 1.5625 * 2^22, times 255 and plus 2^21 stays below 2^31
-__device__ __forceinline__ uint32_t rp_bicubic(const uint32_t* __restrict__ src, int cols, int rows, int fx, int fy, const int* __restrict__ tab) {
-  const int x0 = fx >> 8, y0 = fy >> 8;
-  const int* wx = tab + 4 * (fx & 255);
-  const int* wy = tab + 4 * (fy & 255);
-  int cx[4];
-  for (int i = 0; i < 4; ++i) cx[i] = rp_wrap(x0 - 1 + i, cols);
-  int acc[4] = {0, 0, 0, 0};
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t* row = src + size_t(min(max(y0 - 1 + j, 0), rows - 1)) * cols;
-    int r[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t p = rz_premultiply(row[cx[i]]);
-      for (int c = 0; c < 4; ++c) r[c] += wx[i] * int((p >> (8 * c)) & 0xffu);
-    }
-    for (int c = 0; c < 4; ++c) acc[c] += wy[j] * r[c];
-  }
-  uint32_t out = 0;
-  for (int c = 0; c < 4; ++c) out |= uint32_t(min(255, max(0, (acc[c] + (1 << 21)) >> 22))) << (8 * c);
-  return rz_unpremultiply(out);
-}
 
 template <int FILTER>
 __global__ __launch_bounds__(kRpThreads) void k_reproject(ReprojectArgs a) {
@@ -83,7 +39,7 @@ __global__ __launch_bounds__(kRpThreads) void k_reproject(ReprojectArgs a) {
     if (a.fx_out) { a.fx_out[at] = fx; a.fy_out[at] = fy; }
     if (!dst) continue;
     uint32_t px = 0;
-    if (reproject::inside(g, fy)) px = FILTER == reproject::kBicubic ? rp_bicubic(src, g.cols, g.rows, fx, fy, a.cubic) : rp_bilinear(src, g.cols, g.rows, fx, fy);
+    if (reproject::inside(g, fy)) px = FILTER == reproject::kBicubic ? rp_bicubic<true>(src, g.cols, g.rows, fx, fy, a.cubic) : rp_bilinear<true>(src, g.cols, g.rows, fx, fy);
     dst[at] = px;
   }
 }

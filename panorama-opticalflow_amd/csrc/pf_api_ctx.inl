@@ -84,6 +84,8 @@ struct pf_ctx {
   struct RzResident { const void* p = nullptr; size_t cap = 0; int in = 0, out = 0, filter = 0; } rz_dev[2];
   // pf_reproject*: which tables sit in the arena's "rp_cubic" (the Catmull-Rom phases) and "rp_eq" (an equirect output's sines and cosines)
   struct RpResident { const void* p = nullptr; size_t cap = 0; int out_cols = 0, out_rows = 0; } rp_cubic, rp_eq;
+  // pf_lens_*: the same for the remap's own "ln_cubic" and "ln_eq" (the canvas's sines and cosines)
+  RpResident ln_cubic, ln_eq;
   bool tiff_inflate = false;         // pf_tiff_decode*: deflate strips decode on the device (pf_tiff_set_inflate); off: they are refused
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "tile_stream_plan.hpp"
 #include "reproject_math.hpp"
+#include "lens_math.hpp"
 
 namespace pf {
 
@@ -278,6 +279,17 @@ struct ReprojectArgs {
   int* fx_out; int* fy_out;   // null, or out_cols x out_rows planes that take the quantised coordinates (pf_stage_reproject_coords, n = 1)
 };
 void launch_reproject(hipStream_t st, int n, const ReprojectArgs& a);
+
+// ---- lens remap (kernels_lens.hip): raw photos of a camera rig -> the equirectangular canvas, the inverse of the reprojection; the host makes the tables ----
+struct LensArgs {
+  const uint32_t* src[kMaxBatch]; uint32_t* dst[kMaxBatch];   // blockIdx.z = image, n <= kMaxBatch per launch; dst null: coordinates only
+  lens::Lens lens[kMaxBatch];                                 // the camera of image z
+  lens::Geometry g;
+  const double* eq;      // the canvas's tables: cos lon, sin lon (cols each), cos lat, sin lat (rows each)
+  const int* cubic;      // bicubic: 256 phases x 4 taps (reproject::make_cubic_table)
+  int* fx_out; int* fy_out;   // null, or cols x rows planes that take the quantised coordinates (pf_stage_lens_coords, n = 1)
+};
+void launch_lens_remap(hipStream_t st, int n, const LensArgs& a);
 
 // ---- TIFF decoder (kernels_tiff.hip): strips in parallel (LZW, PackBits, deflate), then predictor + RGB(A) -> BGRA per row ----
 // A strip's status word: the bytes it produced in the low half, a reason in the high half (0 = the stream ended by itself or filled

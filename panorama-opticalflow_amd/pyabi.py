@@ -64,6 +64,12 @@ class ReprojectParams(C.Structure):
     _fields_ = [("projection", C.c_int), ("face", C.c_int), ("filter", C.c_int), ("hfov_deg", C.c_double), ("rot", C.c_double * 9)]
 
 
+class Lens(C.Structure):
+    """pf_lens (include/panoflow.h)"""
+    _fields_ = [("model", C.c_int), ("filter", C.c_int)] + [(n, C.c_double) for n in ("focal_px", "a", "b", "c", "dd", "shift_x", "shift_y", "min_cos")] + \
+               [("crop_cx256", C.c_int), ("crop_cy256", C.c_int), ("crop_r256", C.c_int), ("rot", C.c_double * 9)]
+
+
 class TiffInfo(C.Structure):
     """pf_tiff_info (include/panoflow.h)"""
     _fields_ = [(n, C.c_int) for n in ("struct_size", "cols", "rows", "samples", "compression", "predictor", "rows_per_strip", "n_strips", "big_endian",
@@ -149,6 +155,17 @@ def lib(exp=False):
         _lib.pf_stitch_result_reprojected_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, rp, C.c_void_p]
         _lib.pf_stitch_batch_result_reprojected_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, rp, C.c_void_p]
         _lib.pf_stage_reproject_coords.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, rp, C.c_void_p, C.c_void_p]
+        ln = C.POINTER(Lens)
+        _lib.pf_lens_init.restype = None
+        _lib.pf_lens_init.argtypes = [ln, C.c_int]
+        _lib.pf_lens_focal.restype = C.c_double
+        _lib.pf_lens_focal.argtypes = [C.c_int, C.c_int, C.c_double]
+        _lib.pf_lens_rotation.restype = None
+        _lib.pf_lens_rotation.argtypes = [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]
+        _lib.pf_lens_remap_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, ln]
+        _lib.pf_lens_remap.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, ln]
+        _lib.pf_lens_remap_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, ln]
+        _lib.pf_stage_lens_coords.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, ln, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -175,6 +192,7 @@ EXPORTS = [
     "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev",
     "pf_reproject_params_init", "pf_reproject_rotation", "pf_reproject_dev", "pf_reproject", "pf_reproject_batch_dev", "pf_reproject_cube_dev",
     "pf_stitch_result_reprojected_dev", "pf_stitch_batch_result_reprojected_dev", "pf_stage_reproject_coords",
+    "pf_lens_init", "pf_lens_focal", "pf_lens_rotation", "pf_lens_remap_dev", "pf_lens_remap", "pf_lens_remap_batch_dev", "pf_stage_lens_coords",
     "pf_profile_enable", "pf_profile_reset", "pf_profile_count", "pf_profile_get", "pf_algorithmic_bytes", "pf_level_pixels", "pf_last_swept_steps",
     "pf_dist_unique_id", "pf_dist_init", "pf_dist_destroy", "pf_dist_last_error", "pf_dist_gather_async", "pf_dist_wait", "pf_dist_max", "pf_dist_barrier",
 ]
@@ -254,6 +272,36 @@ def reproject_params(projection=None, face=None, filter=None, hfov_deg=None, rot
             setattr(p, name, int(v))
     if hfov_deg is not None:
         p.hfov_deg = float(hfov_deg)
+    if rot is not None:
+        for k, v in enumerate(rot):
+            p.rot[k] = float(v)
+    return p
+
+
+# PF_LENS_*
+LENS_RECTILINEAR, LENS_FISHEYE_EQUIDISTANT, LENS_FISHEYE_STEREOGRAPHIC, LENS_FISHEYE_EQUISOLID = range(4)
+
+
+def lens_focal(model, photo_cols, hfov_deg):
+    """focal_px of a photo photo_cols wide spanning hfov_deg degrees across (pf_lens_focal: host only)"""
+    return lib().pf_lens_focal(int(model), int(photo_cols), float(hfov_deg))
+
+
+def lens_rotation(yaw_deg=0.0, pitch_deg=0.0, roll_deg=0.0):
+    """the rot of a camera posed by reproject_rotation(yaw, pitch, roll): its transpose (pf_lens_rotation: host only)"""
+    r = (C.c_double * 9)()
+    lib().pf_lens_rotation(float(yaw_deg), float(pitch_deg), float(roll_deg), r)
+    return list(r)
+
+
+def lens(model, filter=None, rot=None, **fields):
+    """a Lens with the library's defaults for the model (pf_lens_init) and the given fields over them"""
+    p = Lens()
+    lib().pf_lens_init(C.byref(p), int(model))
+    if filter is not None:
+        p.filter = int(filter)
+    for name, v in fields.items():
+        setattr(p, name, int(v) if name.startswith("crop_") else float(v))
     if rot is not None:
         for k, v in enumerate(rot):
             p.rot[k] = float(v)
@@ -825,6 +873,34 @@ class Context:
         """(fx, fy): the device's quantised source coordinates of every output pixel, int32 (out_rows, out_cols)"""
         fx = np.empty((out_rows, out_cols), np.int32); fy = np.empty((out_rows, out_cols), np.int32)
         self._chk(self.l.pf_stage_reproject_coords(self.h, cols, rows, out_cols, out_rows, C.byref(params), _p(fx), _p(fy)))
+        return fx, fy
+
+    # ---- lens remap on the device (pf_lens_*): lens = a Lens (lens()) ----
+    def lens_remap(self, photo, cols, rows, lens, out=None):
+        """host BGRA photo (photo_rows, photo_cols, 4), any row stride -> host canvas (rows, cols, 4); out: a destination array (its row stride is kept)"""
+        a = np.asarray(photo, dtype=np.uint8); photo_rows, photo_cols, _ = a.shape
+        if a.strides[2] != 1 or a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        if out is None:
+            out = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8)
+        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(cols, 0) * 4
+        self._chk(self.l.pf_lens_remap(self.h, _p(a), C.c_size_t(a.strides[0]), photo_cols, photo_rows, _p(out), C.c_size_t(step), cols, rows, C.byref(lens)))
+        return out
+
+    def lens_remap_dev(self, d_photo, photo_cols, photo_rows, d_canvas, cols, rows, lens):
+        self._chk(self.l.pf_lens_remap_dev(self.h, C.c_void_p(d_photo), photo_cols, photo_rows, C.c_void_p(d_canvas), cols, rows, C.byref(lens)))
+
+    def lens_remap_batch_dev(self, d_photos, photo_cols, photo_rows, d_canvases, cols, rows, lenses):
+        """n same-size device photos -> n device canvases of cols x rows, image k under lenses[k], one drain"""
+        n = len(d_photos)
+        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_photos]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_canvases])
+        arr = (Lens * n)(*lenses)
+        self._chk(self.l.pf_lens_remap_batch_dev(self.h, n, srcs, photo_cols, photo_rows, dsts, cols, rows, arr))
+
+    def stage_lens_coords(self, photo_cols, photo_rows, cols, rows, lens):
+        """(fx, fy): the device's quantised photo coordinates of every canvas pixel, int32 (rows, cols)"""
+        fx = np.empty((rows, cols), np.int32); fy = np.empty((rows, cols), np.int32)
+        self._chk(self.l.pf_stage_lens_coords(self.h, photo_cols, photo_rows, cols, rows, C.byref(lens), _p(fx), _p(fy)))
         return fx, fy
 
     # ---- device-resident entry points (raw device pointers as ints) ----

@@ -54,6 +54,14 @@
 //   cube faces <stem>_front|right|back|left|up|down.(png|jpg) of N x N are written, cut on the GPU from the result at the canvas's size
 //   (the levelled one with -level) and encoded where they lie; -result_size does not apply to them, nor does -jpeg_gpano.  There is no
 //   antialiasing: choose N near a quarter of the canvas's width.
+//   -lens_rig FILE -canvas WxH (any mode; both or neither): every input the run reads -- 1.tif .. 5.tif, the top image, in every directory of
+//   -test_dirs -- is a RAW PHOTO of a camera that FILE describes (tools/lens_rig.hpp: a subset of Hugin's .pto; rectilinear and fisheye
+//   lenses, pose, radial polynomial, shift, image circle), matched by file name, and is remapped on the GPU onto a W x H equirectangular
+//   canvas (pf_lens_*; bicubic) before anything else sees it: the warp that otherwise has to be done by another program
+//   beforehand.  The host-image modes remap inside the image read (pf_lens_remap); -rig_chain 1 -tiff_device 1 decodes a directory's
+//   photos into device buffers and remaps them there (pf_lens_remap_batch_dev, one launch per directory when the photos have one size), so
+//   that no raw image crosses the link.  The canvas is 360 degrees across with square angular pixels, centred on the horizon.  Agreement
+//   with Hugin's nona is not claimed.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -69,6 +77,7 @@
 #include "../include/OpticalFlow.hpp"
 #include "../include/StitchTool.hpp"
 #include "image_io.hpp"
+#include "lens_rig.hpp"
 
 using namespace panocv;
 using namespace util;
@@ -153,9 +162,27 @@ static pf_ctx* tiffContext() {
   if (!set) { pano::check(pf_tiff_set_inflate(ctx, g_tiff_inflate ? 1 : 0)); set = true; }
   return ctx;
 }
-// an image file to a host image, by the host readers or (a .tif under the device rule, see the usage note) through the device decoder
+static std::vector<lens_rig::Image> g_lens_rig;   // -lens_rig FILE: the cameras; empty: the inputs are canvases already
+static std::string g_lens_rig_file;
+static int g_canvas_cols = 0, g_canvas_rows = 0;   // -canvas WxH
+// the lens of the photo read from `path`, which must have the size its description gives
+static pf_lens lensOf(const std::string& path, int cols, int rows) {
+  const lens_rig::Image* im = lens_rig::find(g_lens_rig, path);
+  if (!im) throw VrCamException("-lens_rig: " + g_lens_rig_file + " describes no image named " + lens_rig::base_name(path));
+  if (im->w() != cols || im->h() != rows)
+    throw VrCamException("-lens_rig: " + path + " is " + std::to_string(cols) + "x" + std::to_string(rows) + ", not the " + std::to_string(im->w()) + "x" + std::to_string(im->h()) + " of its description");
+  return lens_rig::to_lens(*im, PF_REPROJECT_BICUBIC);
+}
+// an image file to a host image, by the host readers or (a .tif under the device rule, see the usage note) through the device decoder;
+// with -lens_rig the file is a raw photo and the image its canvas
 static Mat readImage(const std::string& path) {
-  return g_tiff_device ? pano_io::imread_device(path, tiffContext()) : pano_io::imreadExceptionOnFail(path);
+  Mat raw = g_tiff_device ? pano_io::imread_device(path, tiffContext()) : pano_io::imreadExceptionOnFail(path);
+  if (g_lens_rig.empty()) return raw;
+  if (raw.type() != CV_8UC4) throw VrCamException("-lens_rig: " + path + " is not a CV_8UC4 image");
+  const pf_lens lens = lensOf(path, raw.cols, raw.rows);
+  Mat canvas(g_canvas_rows, g_canvas_cols, CV_8UC4);
+  pano::check(pf_lens_remap(pano::context(), raw.data, raw.step, raw.cols, raw.rows, canvas.data, canvas.step, canvas.cols, canvas.rows, &lens));
+  return canvas;
 }
 
 static std::map<std::string, std::string> parseFlags(int argc, char** argv) {   // gflags syntax: -name value | --name=value
@@ -381,16 +408,43 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
   std::vector<const uint8_t*> t(n), l(size_t(n) * nsteps);
   std::vector<uint8_t*> o(size_t(n) * nsteps);
   int cols = 0, rows = 0;
+  // -lens_rig: a directory's raw photos wait in device buffers of their own until remapRaws() has made their canvases
+  struct Raw { uint8_t* d; int cols, rows; pf_lens lens; uint8_t* canvas; };
+  std::vector<Raw> raws;
+  DevImages raw_dev{ctx, {}};
   auto load = [&](const std::string& path) {
     int c = 0, r = 0;
+    if (!g_lens_rig.empty()) {
+      raw_dev.p.push_back(pano_io::imread_to_device(path, ctx, &c, &r));
+      cols = g_canvas_cols; rows = g_canvas_rows;
+      uint8_t* canvas = (uint8_t*)pf_dev_alloc(ctx, size_t(cols) * rows * 4);
+      if (!canvas) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+      dev.p.push_back(canvas);
+      raws.push_back(Raw{raw_dev.p.back(), c, r, lensOf(path, c, r), canvas});
+      return canvas;
+    }
     dev.p.push_back(pano_io::imread_to_device(path, ctx, &c, &r));
     if (cols == 0) { cols = c; rows = r; }
     if (c != cols || r != rows) throw VrCamException("-test_dirs: every directory's images must be CV_8UC4 images of one size");
     return dev.p.back();
   };
+  // the waiting photos onto their canvases, the photos of one size in one call (a rig's cameras: one launch), then the photos freed
+  auto remapRaws = [&]() {
+    std::vector<bool> done(raws.size(), false);
+    for (size_t a = 0; a < raws.size(); ++a) {
+      if (done[a]) continue;
+      std::vector<const uint8_t*> src; std::vector<uint8_t*> dst; std::vector<pf_lens> lenses;
+      for (size_t b = a; b < raws.size(); ++b)
+        if (!done[b] && raws[b].cols == raws[a].cols && raws[b].rows == raws[a].rows) { src.push_back(raws[b].d); dst.push_back(raws[b].canvas); lenses.push_back(raws[b].lens); done[b] = true; }
+      pano::check(pf_lens_remap_batch_dev(ctx, (int)src.size(), src.data(), raws[a].cols, raws[a].rows, dst.data(), cols, rows, lenses.data()));
+    }
+    for (uint8_t*& q : raw_dev.p) { pf_dev_free(ctx, q); q = nullptr; }
+    raw_dev.p.clear(); raws.clear();
+  };
   for (int k = 0; k < n; ++k) {
     t[k] = load(dirs[k] + "/" + top_img);
     for (int i = 0; i < nsteps; ++i) l[size_t(k) * nsteps + i] = load(dirs[k] + "/" + char(i + 49) + ".tif");
+    remapRaws();
   }
   for (size_t at = 0; at < o.size(); ++at) {
     o[at] = (uint8_t*)pf_dev_alloc(ctx, size_t(cols) * rows * 4);
@@ -479,6 +533,22 @@ int main(int argc, char** argv) {
       if (name != "bicubic" && name != "bilinear") throw VrCamException("-cube_filter must be bicubic or bilinear");
       g_cube_filter = name == "bicubic" ? PF_REPROJECT_BICUBIC : PF_REPROJECT_BILINEAR;
     } else if (flags.count("cube_filter")) throw VrCamException("-cube_filter needs -cube N");
+    if (flags.count("lens_rig") || flags.count("canvas")) {   // every refusal before any device call
+      if (!flags.count("lens_rig") || !flags.count("canvas")) throw VrCamException("-lens_rig FILE and -canvas WxH go together");
+      char tail = 0;
+      if (sscanf(flags["canvas"].c_str(), "%dx%d%c", &g_canvas_cols, &g_canvas_rows, &tail) != 2 || g_canvas_cols <= 0 || g_canvas_rows <= 0 || g_canvas_cols > 65535 || g_canvas_rows > 65535)
+        throw VrCamException("-canvas must be WxH with both 1..65535, e.g. 9000x4000");
+      g_lens_rig_file = flags["lens_rig"];
+      FILE* f = fopen(g_lens_rig_file.c_str(), "rb");
+      if (!f) throw VrCamException("-lens_rig: cannot read " + g_lens_rig_file);
+      std::string text;
+      char buf[4096];
+      for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, got);
+      fclose(f);
+      try { g_lens_rig = lens_rig::parse(text); }
+      catch (const lens_rig::ParseError& e) { throw VrCamException("-lens_rig: " + g_lens_rig_file + ": " + e.what()); }
+      if (g_lens_rig.empty()) throw VrCamException("-lens_rig: " + g_lens_rig_file + " describes no image (no `i` line)");
+    }
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
