@@ -587,6 +587,12 @@ int pf_resize_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* d_src_bgra, in
                         int filter);
 int pf_stitch_result_resized_dev(pf_ctx* ctx, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
 int pf_stitch_batch_result_resized_dev(pf_ctx* ctx, int frame, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra);
+/* Stage entry (tests): ONE pass of the resize on packed HOST images, exactly one launch of the horizontal (axis 0: cols -> n_out
+ * columns, dst n_out x rows) or the vertical kernel (axis 1: rows -> n_out rows, dst cols x n_out) with the library's own table of
+ * that axis and the two fusions as given: premul != 0 premultiplies what the pass loads, unpremul != 0 divides what it stores.
+ * An n_out equal to the axis still runs the pass.  Refuses what pf_resize refuses, and an axis other than 0 or 1. */
+int pf_stage_resize_pass(pf_ctx* ctx, const uint8_t* src_bgra, int cols, int rows, int axis, int n_out, int filter, int premul, int unpremul,
+                         uint8_t* dst_bgra);
 
 /* ---- Reprojection on the device --------------------------------------------------------------
  * A packed BGRA equirectangular sphere in HBM -> a cube face, a rectilinear view, or the sphere turned (re-levelled), without the

@@ -29,9 +29,13 @@ struct RzAcc {
   __device__ __forceinline__ void tap(uint32_t v, int k) {
     for (int i = 0; i < 4; ++i) c[i] += ((v >> (8 * i)) & 0xffu) * (uint32_t)k;
   }
+  // min(255, max(0, (int)c >> 22)) per channel, written as a clamp of the sum and then the shift: shift first and hipcc packs two channels
+  // with gfx950's v_ashr_pk_u8_i32, whose upper half the hardware does not clear (reproject_sample.hpp).  The bytes are the
+  // same for every accumulator (tests/cpp/resize_pack_check.cpp); tests/test_pack_isa.py keeps the instruction out of every kernel.
   __device__ __forceinline__ uint32_t pack() const {
+    constexpr int kTop = (255 << kRzPrecBits) | ((1 << kRzPrecBits) - 1);
     uint32_t out = 0;
-    for (int i = 0; i < 4; ++i) out |= (uint32_t)min(255, max(0, (int)c[i] >> kRzPrecBits)) << (8 * i);
+    for (int i = 0; i < 4; ++i) out |= (uint32_t(min(kTop, max(0, (int)c[i]))) >> kRzPrecBits) << (8 * i);
     return out;
   }
 };

@@ -118,7 +118,36 @@ int pf_resize(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, int
   return finish(c);
 }
 
-int pf_resize_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows, int filter) {
+// stage entry: ONE pass of the resize on host images, its two fusions as the caller says.  axis 0: k_resize_h, cols -> n_out columns;
+// axis 1: k_resize_v, rows -> n_out rows.  The table is the library's own for that axis; an n_out that equals the axis still runs the pass.
+int pf_stage_resize_pass(pf_ctx* c, const uint8_t* src_bgra, int cols, int rows, int axis, int n_out, int filter, int premul, int unpremul, uint8_t* dst_bgra) {
+  if (int e = use(c)) return e;
+  CallGuard guard_(c);
+  if (!src_bgra || !dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
+  if (axis != 0 && axis != 1) return fail(c, PF_ERR_ARG, "resize pass: bad axis %d (0 horizontal, 1 vertical)", axis);
+  const int out_cols = axis ? cols : n_out, out_rows = axis ? n_out : rows;
+  if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
+  const int in = axis ? rows : cols;
+  if (!resize_table::fits(in, n_out, filter)) return fail(c, PF_ERR_ARG, "resize: the table of %d -> %d %s exceeds %.0f coefficients", in, n_out, axis ? "rows" : "columns", resize_table::kMaxCoefs);
+  const size_t in_bytes = size_t(cols) * rows * 4, out_bytes = size_t(out_cols) * out_rows * 4;
+  if (ranges_overlap(dst_bgra, out_bytes, src_bgra, in_bytes)) return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
+  uint8_t* d_src = (uint8_t*)ensure(c, "rz_src", in_bytes);
+  uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", out_bytes);
+  if (!d_src || !d_dst) return PF_ERR_NOMEM;
+  const int *bounds = nullptr, *k = nullptr;
+  if (int e = resize_table_dev(c, axis, in, n_out, filter, &bounds, &k)) return e;
+  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  ResizePtrs io;
+  memset(&io, 0, sizeof io);
+  io.src[0] = (const uint32_t*)d_src; io.dst[0] = (uint32_t*)d_dst;
+  if (axis) { PROF(c, c->s_main, "resize_v"); launch_resize_v(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
+  else { PROF(c, c->s_main, "resize_h"); launch_resize_h(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
+  HIPCHK(c, hipGetLastError());
+  if (int e = down2d(c, dst_bgra, size_t(out_cols) * 4, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  return finish(c);
+}
+
+int pf_resize_batch_dev(pf_ctx* c, int n,const uint8_t* const* d_src_bgra, int cols, int rows, uint8_t* const* d_dst_bgra, int out_cols, int out_rows, int filter) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (n < 0 || !d_src_bgra || !d_dst_bgra) return fail(c, PF_ERR_ARG, "bad argument");

@@ -143,6 +143,7 @@ def lib(exp=False):
         _lib.pf_resize_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _lib.pf_stitch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib.pf_stitch_batch_result_resized_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_stage_resize_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         rp = C.POINTER(ReprojectParams)
         _lib.pf_reproject_params_init.restype = None
         _lib.pf_reproject_params_init.argtypes = [rp]
@@ -189,7 +190,7 @@ EXPORTS = [
     "pf_jpeg_params_init", "pf_jpeg_bound", "pf_jpeg_restart_interval", "pf_jpeg_encode_dev", "pf_jpeg_encode", "pf_jpeg_encode_batch_dev",
     "pf_stitch_result_jpeg", "pf_stitch_batch_result_jpeg",
     "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
-    "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev",
+    "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev", "pf_stage_resize_pass",
     "pf_reproject_params_init", "pf_reproject_rotation", "pf_reproject_dev", "pf_reproject", "pf_reproject_batch_dev", "pf_reproject_cube_dev",
     "pf_stitch_result_reprojected_dev", "pf_stitch_batch_result_reprojected_dev", "pf_stage_reproject_coords",
     "pf_lens_init", "pf_lens_focal", "pf_lens_rotation", "pf_lens_remap_dev", "pf_lens_remap", "pf_lens_remap_batch_dev", "pf_stage_lens_coords",
@@ -834,6 +835,13 @@ class Context:
     def stitch_batch_result_resized_dev(self, frame, out_cols, out_rows, d_dst, filter=RESIZE_LANCZOS):
         """frame slot `frame` of the last stitch_step_batch, resized into d_dst"""
         self._chk(self.l.pf_stitch_batch_result_resized_dev(self.h, frame, out_cols, out_rows, int(filter), C.c_void_p(d_dst)))
+
+    def stage_resize_pass(self, image, axis, n_out, filter, premul, unpremul):
+        """one pass of the resize alone (axis 0: k_resize_h to n_out columns, 1: k_resize_v to n_out rows) with its two fusions as given"""
+        a = np.ascontiguousarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+        out = np.empty((max(n_out, 0), cols, 4) if axis else (rows, max(n_out, 0), 4), np.uint8)
+        self._chk(self.l.pf_stage_resize_pass(self.h, _p(a), cols, rows, int(axis), int(n_out), int(filter), int(premul), int(unpremul), _p(out)))
+        return out
 
     # ---- reprojection on the device (pf_reproject*): params = a ReprojectParams (reproject_params()) ----
     def reproject(self, image, out_cols, out_rows, params, out=None):

@@ -4,6 +4,8 @@
 // Arguments, in groups of `IN.bgra cols rows out_cols out_rows filter OUT.bgra`: each raw image is resized as pf_resize_dev does it
 // (an axis whose size stays runs no pass), for the byte comparison with the serial model (tests/resize_model.py).  Every launch has
 // fewer workgroups than tiles, so the grid-stride walk runs; an image pair is launched as a batch of two (blockIdx.z).
+// A group `pass IN.bgra cols rows axis n_out filter premul unpremul OUT.bgra` runs one pass alone, as pf_stage_resize_pass does: axis 0
+// k_resize_h to n_out columns, axis 1 k_resize_v to n_out rows, with the two fusions as given.
 // Built and run by tests/test_resize_kernels_host.py:  g++ -std=c++20 -fsanitize=address,undefined -Itests/cpp/hip_host_shim ... -pthread
 #include <stdio.h>
 #include <string.h>
@@ -68,9 +70,51 @@ static std::vector<uint32_t> resize(const std::vector<uint32_t>& img, int cols, 
   return out[0];
 }
 
+// one pass alone, a batch of one
+static std::vector<uint32_t> one_pass(const std::vector<uint32_t>& img, int cols, int rows, int axis, int n_out, int filter, int premul, int unpremul) {
+  std::vector<uint32_t> out(axis ? size_t(cols) * n_out : size_t(n_out) * rows);
+  ResizePtrs io;
+  memset(&io, 0, sizeof io);
+  io.src[0] = img.data(); io.dst[0] = out.data();
+  resize_table::Table t;
+  resize_table::make(axis ? rows : cols, n_out, filter, &t);
+  const std::vector<int> bounds(t.bounds), k(t.k);
+  if (axis) launch_xz(k_resize_v, few(rz_grid(cols, n_out)), 1u, (unsigned)kRzThreads, io, cols, rows, n_out, bounds.data(), k.data(), premul, unpremul);
+  else launch_xz(k_resize_h, few(rz_grid(n_out, rows)), 1u, (unsigned)kRzThreads, io, cols, rows, n_out, bounds.data(), k.data(), premul, unpremul);
+  return out;
+}
+
+static bool write_file(const char* path, const std::vector<uint32_t>& out) {
+  FILE* f = fopen(path, "wb");
+  const bool ok = f && fwrite(out.data(), 4, out.size(), f) == out.size();
+  if (f) fclose(f);
+  if (!ok) printf("cannot write %s\n", path);
+  return ok;
+}
+
+static int run_pass(char** a) {   // a[0] = "pass"
+  const int cols = atoi(a[2]), rows = atoi(a[3]), axis = atoi(a[4]), n_out = atoi(a[5]), filter = atoi(a[6]), premul = atoi(a[7]), unpremul = atoi(a[8]);
+  const std::vector<uint8_t> raw = read_file(a[1]);
+  if (cols <= 0 || rows <= 0 || n_out <= 0 || (axis != 0 && axis != 1) || !resize_table::known(filter) || raw.size() != size_t(cols) * rows * 4) {
+    printf("%s is not %d x %d BGRA, or a bad axis, size or filter\n", a[1], cols, rows);
+    return 2;
+  }
+  std::vector<uint32_t> img(size_t(cols) * rows);
+  memcpy(img.data(), raw.data(), raw.size());
+  return write_file(a[9], one_pass(img, cols, rows, axis, n_out, filter, premul, unpremul)) ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
-  if (argc < 2 || (argc - 1) % 7) { printf("usage: %s [IN.bgra cols rows out_cols out_rows filter OUT.bgra]...\n", argv[0]); return 2; }
+  const char* usage = "usage: %s [IN.bgra cols rows out_cols out_rows filter OUT.bgra | pass IN.bgra cols rows axis n_out filter premul unpremul OUT.bgra]...\n";
+  if (argc < 2) { printf(usage, argv[0]); return 2; }
   for (int i = 1; i < argc; i += 7) {
+    if (!strcmp(argv[i], "pass")) {
+      if (i + 10 > argc) { printf(usage, argv[0]); return 2; }
+      if (int e = run_pass(argv + i)) return e;
+      i += 3;
+      continue;
+    }
+    if (i + 7 > argc) { printf(usage, argv[0]); return 2; }
     const int cols = atoi(argv[i + 1]), rows = atoi(argv[i + 2]), out_cols = atoi(argv[i + 3]), out_rows = atoi(argv[i + 4]), filter = atoi(argv[i + 5]);
     const std::vector<uint8_t> raw = read_file(argv[i]);
     if (cols <= 0 || rows <= 0 || out_cols <= 0 || out_rows <= 0 || !resize_table::known(filter) || raw.size() != size_t(cols) * rows * 4) {
@@ -81,9 +125,7 @@ int main(int argc, char** argv) {
     memcpy(img.data(), raw.data(), raw.size());
     const std::vector<uint32_t> out = resize(img, cols, rows, out_cols, out_rows, filter);
     if (out.empty()) return 1;
-    FILE* f = fopen(argv[i + 6], "wb");
-    if (!f || fwrite(out.data(), 4, out.size(), f) != out.size()) { printf("cannot write %s\n", argv[i + 6]); return 2; }
-    fclose(f);
+    if (!write_file(argv[i + 6], out)) return 2;
   }
   printf("ok\n");
   return 0;

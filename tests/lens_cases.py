@@ -39,7 +39,15 @@ L4 = [(0, 0, 0), (0, 1, 1), (1, 0, 1), (1, 1, 0)]   # (polynomial, shift, crop)
 MIN_INSIDE = MIN_OUTSIDE = 0.10
 
 
+# a fourth photo for a few BICUBIC cases: the opaque ringing image (resize_cases.ringing, 64 x 32, blocks of 2 x 2), whose taps overshoot in
+# every channel, so that the sample's clamp to a byte works in both directions in all four byte positions.  Not in PHOTOS: it rides on
+# ringing_cases() only
+RINGING_MIN_CLAMPED = 10
+
+
 def photo(name):
+    if name == "ringing":
+        return resize_cases.ringing(64, 32, 2, 2)
     if name == "pairs":
         rows = list(range(0, 248, 8)) + [255]   # 64 x 32: alphas 0, 8, .. 240 and 255 against colours 0, 4, .. 252
         return np.ascontiguousarray(resize_cases.all_pairs()[rows][:, :256:4])
@@ -118,6 +126,27 @@ def candidates():
                             key = (p, w, h, model, hfov, r, poly, shift, crop)
                             out.append(Case(name, p, w, h, make_lens(pc, pr, model, hfov, r, poly, shift, crop, flt), key))
     return out
+
+
+def ringing_cases():
+    """one equidistant and one rectilinear case of the list (canvas, lens model, pose and options), with the ringing photo in place of theirs"""
+    out = []
+    for name in ("64x48_130x65_equidistant190_generic_p1s1c0_cubic", "64x48_130x65_rectilinear120_pitch90_p1s1c0_cubic"):
+        base = [c for c in cases() if c.name == name]
+        assert len(base) == 1, name
+        _, w, h, model, hfov, r, poly, shift, crop = base[0].key
+        pr, pc = photo_cached("ringing").shape[:2]
+        out.append(Case("ringing" + name[len("64x48"):], "ringing", w, h, make_lens(pc, pr, model, hfov, r, poly, shift, crop, M.BICUBIC), ("ringing",) + base[0].key[1:]))
+    return out
+
+
+def clamp_counts(case):
+    """(low, high): per channel (B, G, R, A) how many inside pixels of the case the model's sample clamps from below 0 and from above 255"""
+    img = photo_cached(case.photo)
+    fx, fy = model_coords(case)
+    ok = M.inside(fx, fy, img.shape[1], img.shape[0], case.lens)
+    raw = M.sample_raw(img, np.where(ok, fx, 0), np.where(ok, fy, 0), case.lens.filter)
+    return [int(((raw[..., c] < 0) & ok).sum()) for c in range(4)], [int(((raw[..., c] > 255) & ok).sum()) for c in range(4)]
 
 
 def all_outside_cases():

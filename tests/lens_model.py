@@ -108,9 +108,8 @@ def inside(fx, fy, photo_cols, photo_rows, lens):
     return ok
 
 
-def sample(img, fx, fy, filter):
-    """R.sample with columns clamped: (rows, cols, 4) uint8 with alpha last, int planes fx, fy -> (out_rows, out_cols, 4); every
-    position is taken as inside"""
+def sample_raw(img, fx, fy, filter):
+    """R.sample_raw with columns clamped: the sample before its clamp to a byte and the un-premultiply, (out_rows, out_cols, 4) int64"""
     rows, cols = img.shape[:2]
     pre = premultiply(np.ascontiguousarray(img)).astype(np.int64)
     fx, fy = fx.astype(np.int64), fy.astype(np.int64)
@@ -130,7 +129,13 @@ def sample(img, fx, fy, filter):
             xx = np.clip(x0 + first + i, 0, cols - 1)
             acc += (wx[..., i] * wy[..., j])[..., None] * pre[yy, xx]
     assert np.abs(acc).max(initial=0) + half < 2 ** 31   # the device accumulates in 32 bits
-    return unpremultiply(np.clip((acc + half) >> shift, 0, 255).astype(np.uint8))
+    return (acc + half) >> shift
+
+
+def sample(img, fx, fy, filter):
+    """R.sample with columns clamped: (rows, cols, 4) uint8 with alpha last, int planes fx, fy -> (out_rows, out_cols, 4); every
+    position is taken as inside"""
+    return unpremultiply(np.clip(sample_raw(img, fx, fy, filter), 0, 255).astype(np.uint8))
 
 
 def remap_from_coords(photo, fx, fy, lens):

@@ -11,7 +11,15 @@ FILTERS = [M.BILINEAR, M.BICUBIC]
 SOURCES = ["64x32", "90x40", "67x33", "pairs"]
 
 
+# a fifth source for a few BICUBIC cases: the opaque ringing image (resize_cases.ringing, 64 x 32, blocks of 2 x 2), whose taps overshoot in
+# every channel, so that the sample's clamp to a byte works in both directions in all four byte positions.  Not in SOURCES: it rides on
+# the cases below only.  The up face sees the pole, where the image's four bands meet (the side faces see two of them)
+RINGING_MIN_CLAMPED = 10
+
+
 def source(name):
+    if name == "ringing":
+        return resize_cases.ringing(64, 32, 2, 2)
     if name == "pairs":
         rows = list(range(0, 248, 8)) + [255]   # 64 x 32: alphas 0, 8, .. 240 and 255 against colours 0, 4, .. 252
         return np.ascontiguousarray(resize_cases.all_pairs()[rows][:, :256:4])
@@ -50,6 +58,21 @@ def cases():
                     name = "%s_p%d_%dx%d_f%d_h%g_%s_%s" % (s, proj, w, h, face, hfov, r, "cubic" if f == M.BICUBIC else "linear")
                     out.append((name, s, proj, w, h, face, hfov, r, f))
     return out
+
+
+def ringing_cases():
+    """the sphere at 130 x 65 and the up face at 65, both under the generic rotation, BICUBIC"""
+    return [("ringing_p%d_%dx%d_f%d_h0_generic_cubic" % (proj, w, h, face), "ringing", proj, w, h, face, 0.0, "generic", M.BICUBIC)
+            for (proj, w, h, face) in ((M.EQUIRECT, 130, 65, 0), (M.CUBE, 65, 65, M.UP))]
+
+
+def clamp_counts(case):
+    """(low, high): per channel (B, G, R, A) how many inside pixels of the case the model's sample clamps from below 0 and from above 255"""
+    fx, fy = model_coords(case)
+    img = source_cached(case[1])
+    ok = M.inside(fy, img.shape[0])
+    raw = M.sample_raw(img, fx, np.where(ok, fy, 0), case[8])
+    return [int(((raw[..., c] < 0) & ok).sum()) for c in range(4)], [int(((raw[..., c] > 255) & ok).sum()) for c in range(4)]
 
 
 _SOURCES = {}

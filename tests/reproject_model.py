@@ -136,8 +136,8 @@ def cubic_table():
 _CUBIC = cubic_table()
 
 
-def sample(img, fx, fy, filter):
-    """(rows, cols, 4) uint8 with alpha last, int planes fx, fy -> (out_rows, out_cols, 4)"""
+def sample_raw(img, fx, fy, filter):
+    """the sample before its clamp to a byte and the un-premultiply: (out_rows, out_cols, 4) int64, the rounded sum shifted down"""
     rows, cols = img.shape[:2]
     pre = premultiply(np.ascontiguousarray(img)).astype(np.int64)
     fx, fy = fx.astype(np.int64), fy.astype(np.int64)
@@ -157,9 +157,13 @@ def sample(img, fx, fy, filter):
             xx = np.mod(x0 + first + i, cols)
             acc += (wx[..., i] * wy[..., j])[..., None] * pre[yy, xx]
     assert np.abs(acc).max(initial=0) + half < 2 ** 31   # the device accumulates in 32 bits
-    out = np.clip((acc + half) >> shift, 0, 255).astype(np.uint8)
-    out = unpremultiply(out)
-    out[~inside(fy, rows)] = 0
+    return (acc + half) >> shift
+
+
+def sample(img, fx, fy, filter):
+    """(rows, cols, 4) uint8 with alpha last, int planes fx, fy -> (out_rows, out_cols, 4)"""
+    out = unpremultiply(np.clip(sample_raw(img, fx, fy, filter), 0, 255).astype(np.uint8))
+    out[~inside(fy, img.shape[0])] = 0
     return out
 
 

@@ -23,12 +23,112 @@ def image(cols, rows, seed=0):
     return img
 
 
+def ringing(cols, rows, bx, by, rest_alpha=255):
+    """(rows, cols, 4) uint8 that makes the negative lobes of LANCZOS and BICUBIC overshoot in every channel: four vertical bands; in band q
+    channel q (B, G, R, A) is a checkerboard of bx x by blocks of 0 and 255, the other colour channels rest at 128 and alpha, outside its
+    own band, at rest_alpha.  255: opaque; 128: translucent, whose overshoot is colour above alpha for the un-premultiply"""
+    img = np.empty((rows, cols, 4), dtype=np.uint8)
+    img[..., :3] = 128
+    img[..., 3] = rest_alpha
+    board = (((np.arange(cols)[None, :] // bx) + (np.arange(rows)[:, None] // by)) & 1).astype(np.uint8) * 255
+    for q in range(4):
+        x0, x1 = q * cols // 4, (q + 1) * cols // 4
+        img[:, x0:x1, q] = board[:, x0:x1]
+    return img
+
+
+# (cols, rows, out_cols, out_rows, bx, by) of the ringing image: with LANCZOS and BICUBIC the model clamps at least 10 outputs from below 0
+# and 10 from above 255 in each of the four channels in each pass that runs (tests assert it through ringing_case); up- and downscaling,
+# and one axis alone, where a single pass carries both fusions
+RINGING_SHAPES = [(50, 33, 77, 47, 2, 2), (97, 41, 31, 17, 6, 5), (180, 24, 65, 9, 6, 5), (50, 33, 50, 47, 2, 2), (97, 41, 31, 41, 6, 5)]
+RINGING_FILTERS = [resize_model.LANCZOS, resize_model.BICUBIC]
+RINGING_MIN_CLAMPED = 10
+
+
+def ringing_case(shape, f, rest_alpha=255):
+    """(image, the model's result, the class of every output byte in the last pass: -1 clamped from below 0, 1 from above 255, 0 neither);
+    asserts the condition on the inputs first: the opaque image of the shape clamps often enough in every channel and pass"""
+    cols, rows, out_cols, out_rows, bx, by = shape
+    key = ("ringing", shape, f)
+    if key not in _MODEL_CACHE:
+        _MODEL_CACHE[key] = resize_model.clamp_counts(ringing(cols, rows, bx, by), out_cols, out_rows, f)
+    counts = _MODEL_CACHE[key]
+    assert counts and all(min(low + high) >= RINGING_MIN_CLAMPED for low, high in counts.values()), (shape, f, counts)
+    img = ringing(cols, rows, bx, by, rest_alpha)
+    want = model(("ringing", shape, rest_alpha), img, out_cols, out_rows, f)
+    raw = resize_model.passes_raw(img, out_cols, out_rows, f)[-1][1]
+    return img, want, np.where(raw < 0, -1, np.where(raw > 255, 1, 0))
+
+
+def differing_by_class(got, want, cls):
+    """the differing bytes per channel and per clamped class of the model's last pass, for an assertion's message"""
+    parts = []
+    for c, name in enumerate("BGRA"):
+        d = got[..., c] != want[..., c]
+        parts.append("%s: %d low, %d high, %d unclamped" % (name, int((d & (cls[..., c] < 0)).sum()), int((d & (cls[..., c] > 0)).sum()), int((d & (cls[..., c] == 0)).sum())))
+    return "%d of %d bytes differ (%s)" % (int((got != want).sum()), want.size, "; ".join(parts))
+
+
 def all_pairs():
     """256 x 256: colour = column, alpha = row: every (colour, alpha) pair once"""
     img = np.empty((256, 256, 4), dtype=np.uint8)
     img[..., :3] = np.arange(256, dtype=np.uint8)[None, :, None]
     img[..., 3] = np.arange(256, dtype=np.uint8)[:, None]
     return img
+
+
+def all_pairs_distinct():
+    """256 x 256: alpha = row; B, G and R three different bijections of the column, so that every (colour, alpha) pair stands once in each
+    of the three byte positions and a byte that landed in another position would show"""
+    c = np.arange(256)
+    img = np.empty((256, 256, 4), dtype=np.uint8)
+    for q, col in enumerate((c, 255 - c, (7 * c + 3) & 255)):
+        img[..., q] = col.astype(np.uint8)[None, :]
+    img[..., 3] = c.astype(np.uint8)[:, None]
+    return img
+
+
+def model_pass(img, axis, n_out, f, premul, unpremul):
+    """one pass of the model alone: axis 0 along the columns (the horizontal kernel), axis 1 along the rows, with the two fusions as given"""
+    cur = resize_model.premultiply(img) if premul else np.ascontiguousarray(img)
+    if axis == 0:
+        cur = resize_model.resample_rows(cur.transpose(1, 0, 2), n_out, f).transpose(1, 0, 2)
+    else:
+        cur = resize_model.resample_rows(cur, n_out, f)
+    cur = np.ascontiguousarray(cur)
+    return resize_model.unpremultiply(cur) if unpremul else cur
+
+
+def pass_cases():
+    """(name, image, axis, n_out, filter, premul, unpremul, the model's image, class of every output byte as in ringing_case) of one pass alone,
+    for each of the two kernels.  A BOX pass that doubles the axis has one tap of exactly 2^22, so the accumulator returns the byte: with one
+    fusion on, the all-pairs image puts all 65536 (colour, alpha) pairs through it in all three byte positions, colour above alpha included.
+    With neither, a LANCZOS pass over the opaque ringing image leaves the clamp's raw bytes with nothing after it to hide a wrong one; the
+    condition on the inputs (10 outputs clamped low and 10 high per channel) is asserted here, on the model."""
+    key = "pass_cases"
+    if key in _MODEL_CACHE:
+        return _MODEL_CACHE[key]
+    out = []
+    pairs = all_pairs_distinct()
+    for axis in (0, 1):
+        doubled = np.repeat(pairs, 2, axis=1 - axis)
+        assert np.array_equal(model_pass(pairs, axis, 512, resize_model.BOX, 0, 0), doubled)
+        none = np.zeros(doubled.shape, np.int64)
+        out.append(("unpremultiply_axis%d" % axis, pairs, axis, 512, resize_model.BOX, 0, 1, resize_model.unpremultiply(doubled), none))
+        out.append(("premultiply_axis%d" % axis, pairs, axis, 512, resize_model.BOX, 1, 0, resize_model.premultiply(doubled), none))
+    for cols, rows, axis, n_out, bx, by in [(97, 41, 0, 31, 6, 5), (50, 33, 0, 77, 2, 2), (50, 33, 1, 47, 2, 2), (97, 41, 1, 17, 6, 5)]:
+        img = ringing(cols, rows, bx, by)
+        src = img.transpose(1, 0, 2) if axis == 0 else img
+        raw = resize_model.resample_rows_raw(src, n_out, resize_model.LANCZOS)
+        raw = raw.transpose(1, 0, 2) if axis == 0 else raw
+        low, high = [int((raw[..., c] < 0).sum()) for c in range(4)], [int((raw[..., c] > 255).sum()) for c in range(4)]
+        assert min(low + high) >= RINGING_MIN_CLAMPED, (cols, rows, axis, n_out, low, high)
+        want = model_pass(img, axis, n_out, resize_model.LANCZOS, 0, 0)
+        out.append(("raw_%dx%d_axis%d_to_%d" % (cols, rows, axis, n_out), img, axis, n_out, resize_model.LANCZOS, 0, 0, want, np.where(raw < 0, -1, np.where(raw > 255, 1, 0))))
+    for case in out:
+        case[7].setflags(write=False)
+    _MODEL_CACHE[key] = out
+    return out
 
 
 def edge_shapes():

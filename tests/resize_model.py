@@ -86,16 +86,41 @@ def unpremultiply(img):
     return out
 
 
-def resample_rows(img, n_out, f):
-    """the pass along axis 0 of an (n, m, 4) uint8 array: every channel alike"""
+def resample_rows_raw(img, n_out, f):
+    """the pass along axis 0 of an (n, m, 4) uint8 array before its clamp: int64, the 32-bit accumulator shifted down by PREC"""
     n_in = img.shape[0]
-    out = np.empty((n_out,) + img.shape[1:], dtype=np.uint8)
+    out = np.empty((n_out,) + img.shape[1:], dtype=np.int64)
     p = img.astype(np.int64)
     for yy, (ymin, k) in enumerate(table(n_in, n_out, f)):
         acc = (1 << (PREC - 1)) + np.tensordot(k, p[ymin:ymin + len(k)], axes=(0, 0))
         acc = ((acc + (1 << 31)) % (1 << 32)) - (1 << 31)   # the accumulator has 32 bits
-        out[yy] = np.clip(acc >> PREC, 0, 255).astype(np.uint8)
+        out[yy] = acc >> PREC
     return out
+
+
+def resample_rows(img, n_out, f):
+    """the pass along axis 0 of an (n, m, 4) uint8 array: every channel alike"""
+    return np.clip(resample_rows_raw(img, n_out, f), 0, 255).astype(np.uint8)
+
+
+def passes_raw(img, out_cols, out_rows, f):
+    """[(pass, raw)] for the passes resize() runs, "h" and / or "v": the pass's outputs before the clamp, (rows, cols, 4) int64"""
+    img = np.ascontiguousarray(img)
+    rows, cols = img.shape[:2]
+    cur, out = premultiply(img), []
+    if out_cols != cols:
+        raw = resample_rows_raw(cur.transpose(1, 0, 2), out_cols, f).transpose(1, 0, 2)
+        out.append(("h", raw))
+        cur = np.clip(raw, 0, 255).astype(np.uint8)
+    if out_rows != rows:
+        out.append(("v", resample_rows_raw(np.ascontiguousarray(cur), out_rows, f)))
+    return out
+
+
+def clamp_counts(img, out_cols, out_rows, f):
+    """{pass: (low, high)}: per channel (B, G, R, A) how many outputs of the pass the clamp raises from below 0 and lowers from above 255"""
+    return {name: ([int((raw[..., c] < 0).sum()) for c in range(4)], [int((raw[..., c] > 255).sum()) for c in range(4)])
+            for name, raw in passes_raw(img, out_cols, out_rows, f)}
 
 
 def resize(img, out_cols, out_rows, f):

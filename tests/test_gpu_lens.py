@@ -89,6 +89,26 @@ def test_cases_host_form_device_form_and_coordinates(pf, ctx, photo, canvas):
     assert not bad, "%d mismatches: %s" % (len(bad), bad[:10])
 
 
+@pytest.mark.parametrize("k", range(2), ids=["equidistant", "rectilinear"])
+def test_ringing_photo_clamps_in_every_channel(pf, ctx, k):
+    case = lens_cases.ringing_cases()[k]
+    low, high = lens_cases.clamp_counts(case)   # a condition on the inputs, on the model alone
+    assert min(low + high) >= lens_cases.RINGING_MIN_CLAMPED, (low, high)
+    img = lens_cases.photo_cached(case.photo)
+    want = lens_cases.model_image(case)
+    got = ctx.lens_remap(img, case.cols, case.rows, _lens(pf, case.lens))
+    assert np.array_equal(got, want), "host form: " + _differing(got, want)
+    out = np.empty_like(want)
+    d_src, d_dst = ctx.dev_alloc(img.nbytes), ctx.dev_alloc(out.nbytes)
+    try:
+        ctx.upload(d_src, np.ascontiguousarray(img))
+        ctx.lens_remap_dev(d_src, img.shape[1], img.shape[0], d_dst, case.cols, case.rows, _lens(pf, case.lens))
+        ctx.download(out, d_dst)
+    finally:
+        ctx.dev_free(d_src); ctx.dev_free(d_dst)
+    assert np.array_equal(out, want), "device form: " + _differing(out, want)
+
+
 def _batch(ctx, pf, img, w, h, cases):
     outs = [np.empty((h, w, 4), np.uint8) for _ in cases]
     rows, cols = img.shape[:2]

@@ -83,6 +83,19 @@ def test_cases_host_form_device_form_and_coordinates(pf, ctx, src, rot):
     assert not bad, "%d mismatches: %s" % (len(bad), bad[:10])
 
 
+@pytest.mark.parametrize("case", reproject_cases.ringing_cases(), ids=lambda c: c[0])
+def test_ringing_source_clamps_in_every_channel(pf, ctx, case):
+    low, high = reproject_cases.clamp_counts(case)   # a condition on the inputs, on the model alone
+    assert min(low + high) >= reproject_cases.RINGING_MIN_CLAMPED, (low, high)
+    img = reproject_cases.source_cached(case[1])
+    want = reproject_cases.model_image(case)
+    p = _params(pf, case)
+    got = ctx.reproject(img, case[3], case[4], p)
+    assert np.array_equal(got, want), "host form: " + _differing(got, want)
+    got = _reproject_dev(ctx, img, case[3], case[4], p)
+    assert np.array_equal(got, want), "device form: " + _differing(got, want)
+
+
 def test_row_strides_and_profile_family(pf, ctx):
     img = reproject_cases.source_cached("90x40")
     p = pf.reproject_params(projection=M.EQUIRECT, filter=M.BICUBIC, rot=M.rotation(37.0, -21.0, 11.0))
