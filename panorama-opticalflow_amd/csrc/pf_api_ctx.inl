@@ -79,13 +79,14 @@ struct pf_ctx {
   unsigned* d_rig_diff = nullptr;       // pixels whose region code differs from the rig's (k_rig_maps adds, the host reads after a sync)
   size_t rig_diff_cap = 0;
   bool rig_overlap_uploads = true;   // pf_rig_stitch_batch: later waves' second upload beside the compute (pf_rig_set_upload_overlap)
+  // which host-made table an arena slot holds (resident_table): where the slot was and how large, and what the table was made for
+  struct Resident { const void* p = nullptr; size_t cap = 0; int key[3] = {0, 0, 0}; };
   // pf_resize*: the host's tables of the last few (in, out, filter) axes, and which of them sits in the arena's "rz_tab_h" / "rz_tab_v"
   std::vector<resize_table::Table> rz_tables;
-  struct RzResident { const void* p = nullptr; size_t cap = 0; int in = 0, out = 0, filter = 0; } rz_dev[2];
-  // pf_reproject*: which tables sit in the arena's "rp_cubic" (the Catmull-Rom phases) and "rp_eq" (an equirect output's sines and cosines)
-  struct RpResident { const void* p = nullptr; size_t cap = 0; int out_cols = 0, out_rows = 0; } rp_cubic, rp_eq;
-  // pf_lens_*: the same for the remap's own "ln_cubic" and "ln_eq" (the canvas's sines and cosines)
-  RpResident ln_cubic, ln_eq;
+  Resident rz_dev[2];
+  // pf_reproject*: the tables in the arena's "rp_cubic" (the Catmull-Rom phases) and "rp_eq" (an equirect output's sines and cosines);
+  // pf_lens_*: the same in the remap's own "ln_cubic" and "ln_eq" (the canvas's sines and cosines)
+  struct SphereTables { const char *cubic_slot, *eq_slot; Resident cubic, eq; } rp_tab = {"rp_cubic", "rp_eq", {}, {}}, ln_tab = {"ln_cubic", "ln_eq", {}, {}};
   bool tiff_inflate = false;         // pf_tiff_decode*: deflate strips decode on the device (pf_tiff_set_inflate); off: they are refused
   std::vector<std::string> prof_names;
   std::vector<ProfEntry> prof_tot;

@@ -79,10 +79,8 @@ static int jpeg_encode_group(pf_ctx* c, int n, const uint8_t* const* d_bgra, int
 }
 
 static int jpeg_encode_many(pf_ctx* c, int n, const uint8_t* const* d_bgra, int cols, int rows, const pf_jpeg_params& p, uint8_t* const* jpg_out, size_t cap, size_t* sizes_out) {
-  for (int k = 0; k < n; ++k) {
-    if (!d_bgra[k] || !jpg_out[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
-    if (reinterpret_cast<uintptr_t>(d_bgra[k]) & 3) return fail(c, PF_ERR_ARG, "jpeg: device image %d is not 4-byte aligned", k);
-  }
+  for (int k = 0; k < n; ++k) if (!jpg_out[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
+  if (int e = check_dev_images(c, "jpeg", n, d_bgra, size_t(cols) * rows * 4)) return e;
   for (int first = 0; first < n; first += kMaxBatch) {
     const int count = std::min(kMaxBatch, n - first);
     if (int e = jpeg_encode_group(c, count, d_bgra + first, cols, rows, p, jpg_out + first, cap, sizes_out + first)) return e;
@@ -121,11 +119,9 @@ int pf_jpeg_encode(pf_ctx* c, const uint8_t* bgra, size_t step_bytes, int cols, 
   pf_jpeg_params p;
   if (int e = jpeg_check(c, cols, rows, params, &p)) return e;
   if (step_bytes < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  uint8_t* d = (uint8_t*)ensure(c, "jpg_src", size_t(cols) * rows * 4);
-  if (!d) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d, size_t(cols) * 4, bgra, step_bytes, size_t(cols) * 4, rows)) return e;
-  const uint8_t* dc = d;
-  return jpeg_encode_many(c, 1, &dc, cols, rows, p, &jpg_out, cap, size_out);
+  const uint8_t* d;
+  if (int e = upload_bgra(c, "jpg_src", bgra, step_bytes, cols, rows, &d)) return e;
+  return jpeg_encode_many(c, 1, &d, cols, rows, p, &jpg_out, cap, size_out);
 }
 
 int pf_jpeg_encode_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_bgra, int cols, int rows, const pf_jpeg_params* params, uint8_t* const* jpg_out, size_t cap_each,
@@ -140,29 +136,26 @@ int pf_jpeg_encode_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_bgra, int
   return jpeg_encode_many(c, n, d_bgra, cols, rows, p, jpg_out, cap_each, sizes_out);
 }
 
-// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final", what r == NULL chains on), read in place
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM (what r == NULL chains on), read in place
 int pf_stitch_result_jpeg(pf_ctx* c, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap, size_t* size_out) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!jpg_out || !size_out) return fail(c, PF_ERR_ARG, "null pointer");
-  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_jpeg: no stitch step result in HBM");
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_result_jpeg", nullptr, &r)) return e;
   pf_jpeg_params p;
-  if (int e = jpeg_check(c, c->chain_cols, c->chain_rows, params, &p)) return e;
-  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
-  return jpeg_encode_many(c, 1, &d, c->chain_cols, c->chain_rows, p, &jpg_out, cap, size_out);
+  if (int e = jpeg_check(c, r.cols, r.rows, params, &p)) return e;
+  return jpeg_encode_many(c, 1, &r.p, r.cols, r.rows, p, &jpg_out, cap, size_out);
 }
 
-// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call
 int pf_stitch_batch_result_jpeg(pf_ctx* c, int frame, const pf_jpeg_params* params, uint8_t* jpg_out, size_t cap, size_t* size_out) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!jpg_out || !size_out) return fail(c, PF_ERR_ARG, "null pointer");
-  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_jpeg: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
-  char name[32];
-  snprintf(name, sizeof name, "sb_fin%d", frame);
-  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
-  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_jpeg: no batch result in frame slot %d", frame);
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_batch_result_jpeg", &frame, &r)) return e;
   pf_jpeg_params p;
-  if (int e = jpeg_check(c, c->sb_cols, c->sb_rows, params, &p)) return e;
-  return jpeg_encode_many(c, 1, &d, c->sb_cols, c->sb_rows, p, &jpg_out, cap, size_out);
+  if (int e = jpeg_check(c, r.cols, r.rows, params, &p)) return e;
+  return jpeg_encode_many(c, 1, &r.p, r.cols, r.rows, p, &jpg_out, cap, size_out);
 }

@@ -44,55 +44,17 @@ int lens_check(pf_ctx* c, int photo_cols, int photo_rows, int cols, int rows, in
   return 0;
 }
 
-// the tables in the arena: uploaded when the slot holds another size's or has moved
-int lens_tables(pf_ctx* c, const lens::Geometry& g, bool cubic, const double** d_eq, const int** d_cubic) {
-  *d_eq = nullptr; *d_cubic = nullptr;
-  if (cubic) {
-    int* d = (int*)ensure(c, "ln_cubic", 1024 * sizeof(int));
-    if (!d) return PF_ERR_NOMEM;
-    if (c->ln_cubic.p != d) {
-      int tab[1024];
-      reproject::make_cubic_table(tab);
-      HIPCHK(c, hipMemcpyAsync(d, tab, sizeof tab, hipMemcpyHostToDevice, c->s_main));
-      HIPCHK(c, hipStreamSynchronize(c->s_main));   // the table is on this frame
-      c->ln_cubic.p = d;
-    }
-    *d_cubic = d;
-  }
-  const size_t count = 2 * (size_t(g.cols) + g.rows);
-  double* d = (double*)ensure(c, "ln_eq", count * sizeof(double));
-  if (!d) return PF_ERR_NOMEM;
-  pf_ctx::RpResident& r = c->ln_eq;
-  const size_t cap = c->bufs["ln_eq"].cap;   // (a slot that grew is a fresh allocation, wherever it landed)
-  if (r.p != d || r.cap != cap || r.out_cols != g.cols || r.out_rows != g.rows) {
-    r.p = nullptr;
-    std::vector<double> eq(count);
-    reproject::make_equirect_tables(g.cols, g.rows, eq.data());
-    HIPCHK(c, hipMemcpyAsync(d, eq.data(), count * sizeof(double), hipMemcpyHostToDevice, c->s_main));
-    HIPCHK(c, hipStreamSynchronize(c->s_main));
-    r.p = d; r.cap = cap; r.out_cols = g.cols; r.out_rows = g.rows;
-  }
-  *d_eq = d;
-  return 0;
-}
-
 // n device photos -> n device canvases, image k under lenses[k] and filters[k], enqueued on s_main in launches of up to kMaxBatch images
 // of one filter; the caller drains
 int lens_many(pf_ctx* c, int n, const uint8_t* const* d_src, uint8_t* const* d_dst, const lens::Geometry& g, const lens::Lens* lenses, const pf_lens* params) {
   const size_t in_bytes = size_t(g.photo_cols) * g.photo_rows * 4, out_bytes = size_t(g.cols) * g.rows * 4;
-  for (int k = 0; k < n; ++k) {
-    if (!d_src[k] || !d_dst[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
-    if ((reinterpret_cast<uintptr_t>(d_src[k]) | reinterpret_cast<uintptr_t>(d_dst[k])) & 3) return fail(c, PF_ERR_ARG, "lens: device image %d is not 4-byte aligned", k);
-  }
-  for (int k = 0; k < n; ++k)
-    for (int q = 0; q < n; ++q)
-      if (ranges_overlap(d_dst[k], out_bytes, d_src[q], in_bytes)) return fail(c, PF_ERR_ARG, "lens: canvas %d overlaps photo %d", k, q);
+  if (int e = check_dev_images(c, "lens", n, d_src, in_bytes, d_dst, out_bytes, "canvas", "photo")) return e;
   bool cubic = false;
   for (int k = 0; k < n; ++k) cubic = cubic || params[k].filter == PF_REPROJECT_BICUBIC;
   LensArgs a;
   memset(&a, 0, sizeof a);
   a.g = g;
-  if (int e = lens_tables(c, g, cubic, &a.eq, &a.cubic)) return e;
+  if (int e = sphere_tables(c, c->ln_tab, cubic, true, g.cols, g.rows, &a.eq, &a.cubic)) return e;
   for (int filter : {PF_REPROJECT_BILINEAR, PF_REPROJECT_BICUBIC}) {
     a.g.filter = filter;
     int count = 0;
@@ -147,15 +109,13 @@ int pf_lens_remap(pf_ctx* c, const uint8_t* photo_bgra, size_t photo_step, int p
   std::vector<lens::Lens> l;
   if (int e = lens_check(c, photo_cols, photo_rows, cols, rows, 1, params, &g, &l)) return e;
   if (photo_step < size_t(photo_cols) * 4 || canvas_step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  if (ranges_overlap(canvas_bgra, size_t(rows - 1) * canvas_step + size_t(cols) * 4, photo_bgra, size_t(photo_rows - 1) * photo_step + size_t(photo_cols) * 4))
-    return fail(c, PF_ERR_ARG, "lens: the canvas overlaps the photo");
-  uint8_t* d_src = (uint8_t*)ensure(c, "ln_src", size_t(photo_cols) * photo_rows * 4);
+  if (ranges_overlap(canvas_bgra, bgra_span(cols, rows, canvas_step), photo_bgra, bgra_span(photo_cols, photo_rows, photo_step))) return fail(c, PF_ERR_ARG, "lens: the canvas overlaps the photo");
+  const uint8_t* d_src;
+  if (int e = upload_bgra(c, "ln_src", photo_bgra, photo_step, photo_cols, photo_rows, &d_src)) return e;
   uint8_t* d_dst = (uint8_t*)ensure(c, "ln_dst", size_t(cols) * rows * 4);
-  if (!d_src || !d_dst) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d_src, size_t(photo_cols) * 4, photo_bgra, photo_step, size_t(photo_cols) * 4, photo_rows)) return e;
-  const uint8_t* dc = d_src;
-  if (int e = lens_many(c, 1, &dc, &d_dst, g, l.data(), params)) return e;
-  if (int e = down2d(c, canvas_bgra, canvas_step, d_dst, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (!d_dst) return PF_ERR_NOMEM;
+  if (int e = lens_many(c, 1, &d_src, &d_dst, g, l.data(), params)) return e;
+  if (int e = download_bgra(c, canvas_bgra, canvas_step, d_dst, cols, rows)) return e;
   return finish(c);
 }
 
@@ -185,7 +145,7 @@ int pf_stage_lens_coords(pf_ctx* c, int photo_cols, int photo_rows, int cols, in
   const size_t bytes = size_t(cols) * rows * 4;
   a.fx_out = (int*)ensure(c, "ln_fx", bytes); a.fy_out = (int*)ensure(c, "ln_fy", bytes);
   if (!a.fx_out || !a.fy_out) return PF_ERR_NOMEM;
-  if (int e = lens_tables(c, a.g, false, &a.eq, &a.cubic)) return e;   // (no destination: no tap, no phase table)
+  if (int e = sphere_tables(c, c->ln_tab, false, true, cols, rows, &a.eq, &a.cubic)) return e;   // (no destination: no tap, no phase table)
   { PROF(c, c->s_main, "lens"); launch_lens_remap(c->s_main, 1, a); }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(fx_out, a.fx_out, bytes, hipMemcpyDeviceToHost, c->s_main));

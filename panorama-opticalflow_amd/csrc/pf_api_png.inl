@@ -62,10 +62,8 @@ static int png_encode_group(pf_ctx* c, int n, const uint8_t* const* d_bgra, int 
 }
 
 static int png_encode_many(pf_ctx* c, int n, const uint8_t* const* d_bgra, int cols, int rows, uint8_t* const* png_out, size_t cap, size_t* sizes_out) {
-  for (int k = 0; k < n; ++k) {
-    if (!d_bgra[k] || !png_out[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
-    if (reinterpret_cast<uintptr_t>(d_bgra[k]) & 3) return fail(c, PF_ERR_ARG, "png: device image %d is not 4-byte aligned", k);
-  }
+  for (int k = 0; k < n; ++k) if (!png_out[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
+  if (int e = check_dev_images(c, "png", n, d_bgra, size_t(cols) * rows * 4)) return e;
   for (int first = 0; first < n; first += kMaxBatch) {
     const int count = std::min(kMaxBatch, n - first);
     if (int e = png_encode_group(c, count, d_bgra + first, cols, rows, png_out + first, cap, sizes_out + first)) return e;
@@ -90,11 +88,9 @@ int pf_png_encode(pf_ctx* c, const uint8_t* bgra, size_t step_bytes, int cols, i
   if (!bgra || !png_out || !size_out) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (step_bytes < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  uint8_t* d = (uint8_t*)ensure(c, "png_src", size_t(cols) * rows * 4);
-  if (!d) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d, size_t(cols) * 4, bgra, step_bytes, size_t(cols) * 4, rows)) return e;
-  const uint8_t* dc = d;
-  return png_encode_many(c, 1, &dc, cols, rows, &png_out, cap, size_out);
+  const uint8_t* d;
+  if (int e = upload_bgra(c, "png_src", bgra, step_bytes, cols, rows, &d)) return e;
+  return png_encode_many(c, 1, &d, cols, rows, &png_out, cap, size_out);
 }
 
 int pf_png_encode_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_bgra, int cols, int rows, uint8_t* const* png_out, size_t cap_each, size_t* sizes_out) {
@@ -106,25 +102,22 @@ int pf_png_encode_batch_dev(pf_ctx* c, int n, const uint8_t* const* d_bgra, int 
   return png_encode_many(c, n, d_bgra, cols, rows, png_out, cap_each, sizes_out);
 }
 
-// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final", what r == NULL chains on), read in place
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM (what r == NULL chains on), read in place
 int pf_stitch_result_png(pf_ctx* c, uint8_t* png_out, size_t cap, size_t* size_out) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!png_out || !size_out) return fail(c, PF_ERR_ARG, "null pointer");
-  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_png: no stitch step result in HBM");
-  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
-  return png_encode_many(c, 1, &d, c->chain_cols, c->chain_rows, &png_out, cap, size_out);
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_result_png", nullptr, &r)) return e;
+  return png_encode_many(c, 1, &r.p, r.cols, r.rows, &png_out, cap, size_out);
 }
 
-// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call
 int pf_stitch_batch_result_png(pf_ctx* c, int frame, uint8_t* png_out, size_t cap, size_t* size_out) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!png_out || !size_out) return fail(c, PF_ERR_ARG, "null pointer");
-  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_png: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
-  char name[32];
-  snprintf(name, sizeof name, "sb_fin%d", frame);
-  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
-  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_png: no batch result in frame slot %d", frame);
-  return png_encode_many(c, 1, &d, c->sb_cols, c->sb_rows, &png_out, cap, size_out);
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_batch_result_png", &frame, &r)) return e;
+  return png_encode_many(c, 1, &r.p, r.cols, r.rows, &png_out, cap, size_out);
 }

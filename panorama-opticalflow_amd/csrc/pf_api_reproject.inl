@@ -36,37 +36,16 @@ int reproject_check(pf_ctx* c, int cols, int rows, int out_cols, int out_rows, c
   return 0;
 }
 
-// the tables in the arena: uploaded when the slot holds another size's or has moved
-int reproject_tables(pf_ctx* c, const reproject::Geometry& g, const double** d_eq, const int** d_cubic) {
-  *d_eq = nullptr; *d_cubic = nullptr;
-  if (g.filter == PF_REPROJECT_BICUBIC) {
-    int* d = (int*)ensure(c, "rp_cubic", 1024 * sizeof(int));
-    if (!d) return PF_ERR_NOMEM;
-    if (c->rp_cubic.p != d) {
-      int tab[1024];
-      reproject::make_cubic_table(tab);
-      HIPCHK(c, hipMemcpyAsync(d, tab, sizeof tab, hipMemcpyHostToDevice, c->s_main));
-      HIPCHK(c, hipStreamSynchronize(c->s_main));   // the table is on this frame
-      c->rp_cubic.p = d;
-    }
-    *d_cubic = d;
-  }
-  if (g.projection == PF_PROJ_EQUIRECT) {
-    const size_t count = 2 * (size_t(g.out_cols) + g.out_rows);
-    double* d = (double*)ensure(c, "rp_eq", count * sizeof(double));
-    if (!d) return PF_ERR_NOMEM;
-    pf_ctx::RpResident& r = c->rp_eq;
-    const size_t cap = c->bufs["rp_eq"].cap;   // (a slot that grew is a fresh allocation, wherever it landed)
-    if (r.p != d || r.cap != cap || r.out_cols != g.out_cols || r.out_rows != g.out_rows) {
-      r.p = nullptr;
-      std::vector<double> eq(count);
-      reproject::make_equirect_tables(g.out_cols, g.out_rows, eq.data());
-      HIPCHK(c, hipMemcpyAsync(d, eq.data(), count * sizeof(double), hipMemcpyHostToDevice, c->s_main));
-      HIPCHK(c, hipStreamSynchronize(c->s_main));
-      r.p = d; r.cap = cap; r.out_cols = g.out_cols; r.out_rows = g.out_rows;
-    }
-    *d_eq = d;
-  }
+// The two tables a launch of either sphere sampler reads (reproject_math.hpp), resident in the family's own slots: the Catmull-Rom
+// phases (want_cubic) and the sines and cosines of an equirect grid of cols x rows (want_eq).  A table not wanted comes back null.
+int sphere_tables(pf_ctx* c, pf_ctx::SphereTables& t, bool want_cubic, bool want_eq, int cols, int rows, const double** d_eq, const int** d_cubic) {
+  const uint8_t *eq = nullptr, *cubic = nullptr;
+  if (want_cubic)
+    if (int e = resident_table(c, t.cubic_slot, t.cubic, 0, 0, 0, 1024 * sizeof(int), [](uint8_t* h) { reproject::make_cubic_table((int*)h); }, &cubic)) return e;
+  if (want_eq)
+    if (int e = resident_table(c, t.eq_slot, t.eq, cols, rows, 0, 2 * (size_t(cols) + rows) * sizeof(double),
+                               [&](uint8_t* h) { reproject::make_equirect_tables(cols, rows, (double*)h); }, &eq)) return e;
+  *d_eq = (const double*)eq; *d_cubic = (const int*)cubic;
   return 0;
 }
 
@@ -74,17 +53,11 @@ int reproject_tables(pf_ctx* c, const reproject::Geometry& g, const double** d_e
 // faces: null (every image takes `face`), or the face of each image.
 int reproject_many(pf_ctx* c, int n, const uint8_t* const* d_src, uint8_t* const* d_dst, const reproject::Geometry& g, int face, const int* faces) {
   const size_t in_bytes = size_t(g.cols) * g.rows * 4, out_bytes = size_t(g.out_cols) * g.out_rows * 4;
-  for (int k = 0; k < n; ++k) {
-    if (!d_src[k] || !d_dst[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
-    if ((reinterpret_cast<uintptr_t>(d_src[k]) | reinterpret_cast<uintptr_t>(d_dst[k])) & 3) return fail(c, PF_ERR_ARG, "reproject: device image %d is not 4-byte aligned", k);
-  }
-  for (int k = 0; k < n; ++k)
-    for (int q = 0; q < n; ++q)
-      if (ranges_overlap(d_dst[k], out_bytes, d_src[q], in_bytes)) return fail(c, PF_ERR_ARG, "reproject: destination %d overlaps source %d", k, q);
+  if (int e = check_dev_images(c, "reproject", n, d_src, in_bytes, d_dst, out_bytes)) return e;
   ReprojectArgs a;
   memset(&a, 0, sizeof a);
   a.g = g;
-  if (int e = reproject_tables(c, g, &a.eq, &a.cubic)) return e;
+  if (int e = sphere_tables(c, c->rp_tab, g.filter == PF_REPROJECT_BICUBIC, g.projection == PF_PROJ_EQUIRECT, g.out_cols, g.out_rows, &a.eq, &a.cubic)) return e;
   for (int first = 0; first < n; first += kMaxBatch) {
     const int count = std::min(kMaxBatch, n - first);
     for (int k = 0; k < count; ++k) {
@@ -130,15 +103,13 @@ int pf_reproject(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, 
   reproject::Geometry g;
   if (int e = reproject_check(c, cols, rows, out_cols, out_rows, params, &g)) return e;
   if (src_step < size_t(cols) * 4 || dst_step < size_t(out_cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  if (ranges_overlap(dst_bgra, size_t(out_rows - 1) * dst_step + size_t(out_cols) * 4, src_bgra, size_t(rows - 1) * src_step + size_t(cols) * 4))
-    return fail(c, PF_ERR_ARG, "reproject: the destination overlaps the source");
-  uint8_t* d_src = (uint8_t*)ensure(c, "rp_src", size_t(cols) * rows * 4);
+  if (ranges_overlap(dst_bgra, bgra_span(out_cols, out_rows, dst_step), src_bgra, bgra_span(cols, rows, src_step))) return fail(c, PF_ERR_ARG, "reproject: the destination overlaps the source");
+  const uint8_t* d_src;
+  if (int e = upload_bgra(c, "rp_src", src_bgra, src_step, cols, rows, &d_src)) return e;
   uint8_t* d_dst = (uint8_t*)ensure(c, "rp_dst", size_t(out_cols) * out_rows * 4);
-  if (!d_src || !d_dst) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, src_step, size_t(cols) * 4, rows)) return e;
-  const uint8_t* dc = d_src;
-  if (int e = reproject_many(c, 1, &dc, &d_dst, g, params->face, nullptr)) return e;
-  if (int e = down2d(c, dst_bgra, dst_step, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  if (!d_dst) return PF_ERR_NOMEM;
+  if (int e = reproject_many(c, 1, &d_src, &d_dst, g, params->face, nullptr)) return e;
+  if (int e = download_bgra(c, dst_bgra, dst_step, d_dst, out_cols, out_rows)) return e;
   return finish(c);
 }
 
@@ -170,32 +141,29 @@ int pf_reproject_cube_dev(pf_ctx* c, const uint8_t* d_src_bgra, int cols, int ro
   return finish(c);
 }
 
-// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final"), read in place
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM, read in place
 int pf_stitch_result_reprojected_dev(pf_ctx* c, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
-  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_reprojected_dev: no stitch step result in HBM");
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_result_reprojected_dev", nullptr, &r)) return e;
   reproject::Geometry g;
-  if (int e = reproject_check(c, c->chain_cols, c->chain_rows, out_cols, out_rows, params, &g)) return e;
-  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
-  if (int e = reproject_many(c, 1, &d, &d_dst_bgra, g, params->face, nullptr)) return e;
+  if (int e = reproject_check(c, r.cols, r.rows, out_cols, out_rows, params, &g)) return e;
+  if (int e = reproject_many(c, 1, &r.p, &d_dst_bgra, g, params->face, nullptr)) return e;
   return finish(c);
 }
 
-// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call
 int pf_stitch_batch_result_reprojected_dev(pf_ctx* c, int frame, int out_cols, int out_rows, const pf_reproject_params* params, uint8_t* d_dst_bgra) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
-  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_reprojected_dev: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
-  char name[32];
-  snprintf(name, sizeof name, "sb_fin%d", frame);
-  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
-  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_reprojected_dev: no batch result in frame slot %d", frame);
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_batch_result_reprojected_dev", &frame, &r)) return e;
   reproject::Geometry g;
-  if (int e = reproject_check(c, c->sb_cols, c->sb_rows, out_cols, out_rows, params, &g)) return e;
-  if (int e = reproject_many(c, 1, &d, &d_dst_bgra, g, params->face, nullptr)) return e;
+  if (int e = reproject_check(c, r.cols, r.rows, out_cols, out_rows, params, &g)) return e;
+  if (int e = reproject_many(c, 1, &r.p, &d_dst_bgra, g, params->face, nullptr)) return e;
   return finish(c);
 }
 
@@ -210,7 +178,7 @@ int pf_stage_reproject_coords(pf_ctx* c, int cols, int rows, int out_cols, int o
   const size_t bytes = size_t(out_cols) * out_rows * 4;
   a.fx_out = (int*)ensure(c, "rp_fx", bytes); a.fy_out = (int*)ensure(c, "rp_fy", bytes);
   if (!a.fx_out || !a.fy_out) return PF_ERR_NOMEM;
-  if (int e = reproject_tables(c, a.g, &a.eq, &a.cubic)) return e;
+  if (int e = sphere_tables(c, c->rp_tab, a.g.filter == PF_REPROJECT_BICUBIC, a.g.projection == PF_PROJ_EQUIRECT, out_cols, out_rows, &a.eq, &a.cubic)) return e;
   a.face[0] = params->face;
   { PROF(c, c->s_main, "reproject"); launch_reproject(c->s_main, 1, a); }
   HIPCHK(c, hipGetLastError());

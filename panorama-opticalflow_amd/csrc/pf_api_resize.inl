@@ -15,28 +15,15 @@ const resize_table::Table* resize_table_of(pf_ctx* c, int in, int out, int filte
   return &c->rz_tables.back();
 }
 
-// the table of one axis in the arena: bounds, then the coefficients.  Uploaded when the slot holds another table or has moved.
+// the table of one axis resident in the arena: bounds, then the coefficients at the next 256-byte boundary
 int resize_table_dev(pf_ctx* c, int axis, int in, int out, int filter, const int** d_bounds, const int** d_k) {
   const resize_table::Table* t = resize_table_of(c, in, out, filter);
   const size_t nb = t->bounds.size() * 4, nk = t->k.size() * 4, at_k = (nb + 255) & ~size_t(255);
-  uint8_t* d = (uint8_t*)ensure(c, axis ? "rz_tab_v" : "rz_tab_h", at_k + nk);
-  if (!d) return PF_ERR_NOMEM;
-  pf_ctx::RzResident& r = c->rz_dev[axis];
-  const size_t cap = c->bufs[axis ? "rz_tab_v" : "rz_tab_h"].cap;   // (a slot that grew is a fresh allocation, wherever it landed)
-  if (r.p != d || r.cap != cap || r.in != in || r.out != out || r.filter != filter) {
-    r.p = nullptr;
-    HIPCHK(c, hipMemcpyAsync(d, t->bounds.data(), nb, hipMemcpyHostToDevice, c->s_main));
-    HIPCHK(c, hipMemcpyAsync(d + at_k, t->k.data(), nk, hipMemcpyHostToDevice, c->s_main));
-    HIPCHK(c, hipStreamSynchronize(c->s_main));   // the host table may leave the context's list before the next call
-    r.p = d; r.cap = cap; r.in = in; r.out = out; r.filter = filter;
-  }
+  const uint8_t* d;
+  auto fill = [&](uint8_t* h) { memcpy(h, t->bounds.data(), nb); memcpy(h + at_k, t->k.data(), nk); };
+  if (int e = resident_table(c, axis ? "rz_tab_v" : "rz_tab_h", c->rz_dev[axis], in, out, filter, at_k + nk, fill, &d)) return e;
   *d_bounds = (const int*)d; *d_k = (const int*)(d + at_k);
   return 0;
-}
-
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
 }
 
 // sizes, the filter and the tables' bound: everything known without a pointer
@@ -53,13 +40,7 @@ int resize_check(pf_ctx* c, int cols, int rows, int out_cols, int out_rows, int 
 // n device images of cols x rows -> n of out_cols x out_rows, enqueued on s_main in groups of kMaxBatch; the caller drains
 int resize_many(pf_ctx* c, int n, const uint8_t* const* d_src, int cols, int rows, uint8_t* const* d_dst, int out_cols, int out_rows, int filter) {
   const size_t in_bytes = size_t(cols) * rows * 4, out_bytes = size_t(out_cols) * out_rows * 4;
-  for (int k = 0; k < n; ++k) {
-    if (!d_src[k] || !d_dst[k]) return fail(c, PF_ERR_ARG, "null pointer (image %d)", k);
-    if ((reinterpret_cast<uintptr_t>(d_src[k]) | reinterpret_cast<uintptr_t>(d_dst[k])) & 3) return fail(c, PF_ERR_ARG, "resize: device image %d is not 4-byte aligned", k);
-  }
-  for (int k = 0; k < n; ++k)
-    for (int q = 0; q < n; ++q)
-      if (ranges_overlap(d_dst[k], out_bytes, d_src[q], in_bytes)) return fail(c, PF_ERR_ARG, "resize: destination %d overlaps source %d", k, q);
+  if (int e = check_dev_images(c, "resize", n, d_src, in_bytes, d_dst, out_bytes)) return e;
   hipStream_t sm = c->s_main;
   const bool do_h = out_cols != cols, do_v = out_rows != rows;
   if (!do_h && !do_v) {
@@ -106,15 +87,13 @@ int pf_resize(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, int
   if (!src_bgra || !dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
   if (src_step < size_t(cols) * 4 || dst_step < size_t(out_cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  if (ranges_overlap(dst_bgra, size_t(out_rows - 1) * dst_step + size_t(out_cols) * 4, src_bgra, size_t(rows - 1) * src_step + size_t(cols) * 4))
-    return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
-  uint8_t* d_src = (uint8_t*)ensure(c, "rz_src", size_t(cols) * rows * 4);
+  if (ranges_overlap(dst_bgra, bgra_span(out_cols, out_rows, dst_step), src_bgra, bgra_span(cols, rows, src_step))) return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
+  const uint8_t* d_src;
+  if (int e = upload_bgra(c, "rz_src", src_bgra, src_step, cols, rows, &d_src)) return e;
   uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", size_t(out_cols) * out_rows * 4);
-  if (!d_src || !d_dst) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, src_step, size_t(cols) * 4, rows)) return e;
-  const uint8_t* dc = d_src;
-  if (int e = resize_many(c, 1, &dc, cols, rows, &d_dst, out_cols, out_rows, filter)) return e;
-  if (int e = down2d(c, dst_bgra, dst_step, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  if (!d_dst) return PF_ERR_NOMEM;
+  if (int e = resize_many(c, 1, &d_src, cols, rows, &d_dst, out_cols, out_rows, filter)) return e;
+  if (int e = download_bgra(c, dst_bgra, dst_step, d_dst, out_cols, out_rows)) return e;
   return finish(c);
 }
 
@@ -129,21 +108,21 @@ int pf_stage_resize_pass(pf_ctx* c, const uint8_t* src_bgra, int cols, int rows,
   if (int e = resize_check(c, cols, rows, out_cols, out_rows, filter)) return e;
   const int in = axis ? rows : cols;
   if (!resize_table::fits(in, n_out, filter)) return fail(c, PF_ERR_ARG, "resize: the table of %d -> %d %s exceeds %.0f coefficients", in, n_out, axis ? "rows" : "columns", resize_table::kMaxCoefs);
-  const size_t in_bytes = size_t(cols) * rows * 4, out_bytes = size_t(out_cols) * out_rows * 4;
-  if (ranges_overlap(dst_bgra, out_bytes, src_bgra, in_bytes)) return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
-  uint8_t* d_src = (uint8_t*)ensure(c, "rz_src", in_bytes);
-  uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", out_bytes);
-  if (!d_src || !d_dst) return PF_ERR_NOMEM;
+  const size_t in_step = size_t(cols) * 4, out_step = size_t(out_cols) * 4;   // both host images are packed
+  if (ranges_overlap(dst_bgra, bgra_span(out_cols, out_rows, out_step), src_bgra, bgra_span(cols, rows, in_step))) return fail(c, PF_ERR_ARG, "resize: the destination overlaps the source");
+  const uint8_t* d_src;
+  if (int e = upload_bgra(c, "rz_src", src_bgra, in_step, cols, rows, &d_src)) return e;
+  uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", out_step * out_rows);
+  if (!d_dst) return PF_ERR_NOMEM;
   const int *bounds = nullptr, *k = nullptr;
   if (int e = resize_table_dev(c, axis, in, n_out, filter, &bounds, &k)) return e;
-  if (int e = up2d(c, d_src, size_t(cols) * 4, src_bgra, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
   ResizePtrs io;
   memset(&io, 0, sizeof io);
   io.src[0] = (const uint32_t*)d_src; io.dst[0] = (uint32_t*)d_dst;
   if (axis) { PROF(c, c->s_main, "resize_v"); launch_resize_v(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
   else { PROF(c, c->s_main, "resize_h"); launch_resize_h(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
   HIPCHK(c, hipGetLastError());
-  if (int e = down2d(c, dst_bgra, size_t(out_cols) * 4, d_dst, size_t(out_cols) * 4, size_t(out_cols) * 4, out_rows)) return e;
+  if (int e = download_bgra(c, dst_bgra, out_step, d_dst, out_cols, out_rows)) return e;
   return finish(c);
 }
 
@@ -157,29 +136,26 @@ int pf_resize_batch_dev(pf_ctx* c, int n,const uint8_t* const* d_src_bgra, int c
   return finish(c);
 }
 
-// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM ("ch_final"), read in place
+// The composite the last pf_stitch_step / pf_stitch_step_planned left in HBM, read in place
 int pf_stitch_result_resized_dev(pf_ctx* c, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
-  if (c->chain_cols <= 0 || c->chain_rows <= 0 || !c->bufs["ch_final"].p) return fail(c, PF_ERR_ARG, "pf_stitch_result_resized_dev: no stitch step result in HBM");
-  if (int e = resize_check(c, c->chain_cols, c->chain_rows, out_cols, out_rows, filter)) return e;
-  const uint8_t* d = (const uint8_t*)c->bufs["ch_final"].p;
-  if (int e = resize_many(c, 1, &d, c->chain_cols, c->chain_rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_result_resized_dev", nullptr, &r)) return e;
+  if (int e = resize_check(c, r.cols, r.rows, out_cols, out_rows, filter)) return e;
+  if (int e = resize_many(c, 1, &r.p, r.cols, r.rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
   return finish(c);
 }
 
-// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call ("sb_fin<frame>")
+// ... and frame slot `frame` of the last host-form pf_stitch_step_batch* call
 int pf_stitch_batch_result_resized_dev(pf_ctx* c, int frame, int out_cols, int out_rows, int filter, uint8_t* d_dst_bgra) {
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!d_dst_bgra) return fail(c, PF_ERR_ARG, "null pointer");
-  if (frame < 0 || frame >= c->sb_frames) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_resized_dev: no batch result in frame slot %d (%d slots hold one)", frame, c->sb_frames);
-  char name[32];
-  snprintf(name, sizeof name, "sb_fin%d", frame);
-  const uint8_t* d = (const uint8_t*)c->bufs[name].p;
-  if (!d) return fail(c, PF_ERR_ARG, "pf_stitch_batch_result_resized_dev: no batch result in frame slot %d", frame);
-  if (int e = resize_check(c, c->sb_cols, c->sb_rows, out_cols, out_rows, filter)) return e;
-  if (int e = resize_many(c, 1, &d, c->sb_cols, c->sb_rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
+  DevImage r;
+  if (int e = resident_result(c, "pf_stitch_batch_result_resized_dev", &frame, &r)) return e;
+  if (int e = resize_check(c, r.cols, r.rows, out_cols, out_rows, filter)) return e;
+  if (int e = resize_many(c, 1, &r.p, r.cols, r.rows, &d_dst_bgra, out_cols, out_rows, filter)) return e;
   return finish(c);
 }

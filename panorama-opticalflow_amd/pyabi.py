@@ -213,6 +213,30 @@ def _u8(a):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
+def _bgra(image):
+    """(array, cols, rows, row step): the uint8 BGRA image as it is where its pixels are packed (rows any distance apart), else a contiguous copy"""
+    a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
+    if a.strides[2] != 1 or a.strides[1] != 4:
+        a = np.ascontiguousarray(a)
+    return a, cols, rows, C.c_size_t(a.strides[0])
+
+
+def _dst(out, cols, rows):
+    """(array, row step): the caller's destination array, or a fresh (rows, cols, 4) one"""
+    if out is None:
+        out = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8)
+    return out, C.c_size_t(out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(cols, 0) * 4)
+
+
+def _dptrs(v, n=None):
+    """sequence of device pointers (ints; 0 or None: NULL) -> c_void_p array of n entries (default len(v)); a shorter v leaves NULLs"""
+    return (C.c_void_p * max(len(v) if n is None else n, 1))(*[C.c_void_p(int(x)) if x else None for x in v])
+
+
+def _ref(params):
+    return C.byref(params) if params is not None else None
+
+
 def max_percentage_by_name(name):
     """makeOpticalFlowByName (CPU/PixFlow.hpp:459-500): raises on an unknown algorithm name."""
     v = lib().pf_max_percentage_by_name(name.encode())
@@ -562,9 +586,8 @@ class Context:
         return RigPlan(self, h.value)
 
     def rig_plan_dev(self, d_top, d_ls, cols, rows):
-        arr = (C.c_void_p * max(len(d_ls), 1))(*[C.c_void_p(int(x)) if x else None for x in d_ls])
         h = C.c_void_p(None)
-        self._chk(self.l.pf_rig_plan_create_dev(self.h, len(d_ls), C.c_void_p(d_top), arr, cols, rows, C.byref(h)))
+        self._chk(self.l.pf_rig_plan_create_dev(self.h, len(d_ls), C.c_void_p(d_top), _dptrs(d_ls), cols, rows, C.byref(h)))
         return RigPlan(self, h.value)
 
     def rig_stitch_batch(self, rig, tops, Ls, max_pct, in_flight=8, want=None, out=None):
@@ -592,10 +615,8 @@ class Context:
 
     def rig_stitch_batch_dev(self, rig, d_tops, d_ls, max_pct, d_outs, in_flight=8):
         """the device form: d_tops[k], d_ls[k][i], d_outs[k][i] device pointers (packed BGRA); only d_outs[k][-1] must be given"""
-        n = len(d_tops)
-        ptrs = lambda v: (C.c_void_p * max(len(v), 1))(*[C.c_void_p(int(x)) if x else None for x in v])
-        self._chk(self.l.pf_rig_stitch_batch_dev(self.h, rig.h, n, ptrs(d_tops), ptrs([x for r in d_ls for x in r]), rig.cols, rig.rows, max_pct,
-                                                 ptrs([x for r in d_outs for x in r]), in_flight))
+        self._chk(self.l.pf_rig_stitch_batch_dev(self.h, rig.h, len(d_tops), _dptrs(d_tops), _dptrs([x for r in d_ls for x in r]), rig.cols, rig.rows, max_pct,
+                                                 _dptrs([x for r in d_outs for x in r]), in_flight))
 
     def stitch_step(self, L, R, max_pct, want_out=True, out=None, plan=None):
         """One iteration of main.cpp's loop on the device; R=None chains on the previous result kept in HBM.
@@ -644,11 +665,10 @@ class Context:
     def stitch_step_batch_dev(self, d_l, d_r, cols, rows, max_pct, d_out, in_flight=8, plan=None):
         """the device form: lists of device pointers (packed BGRA), every d_r entry non-NULL"""
         n = len(d_l)
-        arr = lambda v: (C.c_void_p * max(n, 1))(*[C.c_void_p(int(x)) if x else None for x in v])
         if plan is not None:
-            self._chk(self.l.pf_stitch_step_batch_planned_dev(self.h, plan.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
+            self._chk(self.l.pf_stitch_step_batch_planned_dev(self.h, plan.h, n, _dptrs(d_l), _dptrs(d_r, n), cols, rows, max_pct, _dptrs(d_out, n), in_flight))
         else:
-            self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, arr(d_l), arr(d_r), cols, rows, max_pct, arr(d_out), in_flight))
+            self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, _dptrs(d_l), _dptrs(d_r, n), cols, rows, max_pct, _dptrs(d_out, n), in_flight))
 
     # ---- flow visualisation (CPU/OpticalFlow.cpp:147-204, the panel of CPU/main.cpp:20-45) ----
     def vis_grey_disparity(self, flow):
@@ -692,90 +712,72 @@ class Context:
         return a, b
 
     # ---- PNG files made on the device (pf_png_*): every method returns the file as bytes ----
-    def _png_call(self, cols, rows, call, cap=None):
-        """call(buffer, cap, size_ref) -> rc.  cap=None: pf_png_bound.  A short buffer raises PngCapacityError carrying the needed size."""
-        cap = int(self.l.pf_png_bound(cols, rows)) if cap is None else int(cap)
+    def _file_call(self, bound, cols, rows, call, cap, *pr):
+        """call(*pr, buffer, cap, size_ref) -> rc, where pr is the params reference of a format that takes one.  cap=None: bound(cols, rows, *pr).
+        A short buffer raises PngCapacityError carrying the needed size."""
+        cap = int(bound(cols, rows, *pr)) if cap is None else int(cap)
         buf = np.empty(max(cap, 1), np.uint8); size = C.c_size_t(0)
-        rc = call(_p(buf), C.c_size_t(cap), C.byref(size))
+        rc = call(*pr, _p(buf), C.c_size_t(cap), C.byref(size))
         if rc != 0 and 0 < cap < size.value:
             raise PngCapacityError("panoflow error %d: %s" % (rc, self.l.pf_last_error(self.h).decode()), size.value)
         self._chk(rc)
         return buf[:size.value].tobytes()
 
+    def _file_batch_call(self, bound, encode, d_bgra, cols, rows, *pr):
+        """encode(handle, n, sources, cols, rows, *pr, buffers, cap_each, sizes) -> rc: n files into buffers of bound(cols, rows, *pr) bytes"""
+        n = len(d_bgra)
+        cap = int(bound(cols, rows, *pr))
+        bufs = [np.empty(max(cap, 1), np.uint8) for _ in range(n)]
+        outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)()
+        self._chk(encode(self.h, n, _dptrs(d_bgra), cols, rows, *pr, outs, C.c_size_t(cap), sizes))
+        return [bufs[k][:sizes[k]].tobytes() for k in range(n)]
+
     def png_encode(self, image, cap=None):
         """host BGRA (rows, cols, 4) array, any row stride -> PNG file bytes"""
-        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_png_encode(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, b, c, s), cap)
+        a, cols, rows, step = _bgra(image)
+        return self._file_call(self.l.pf_png_bound, cols, rows, lambda b, c, s: self.l.pf_png_encode(self.h, _p(a), step, cols, rows, b, c, s), cap)
 
     def png_encode_dev(self, d_bgra, cols, rows, cap=None):
-        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_png_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, b, c, s), cap)
+        return self._file_call(self.l.pf_png_bound, cols, rows, lambda b, c, s: self.l.pf_png_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, b, c, s), cap)
 
     def png_encode_batch_dev(self, d_bgra, cols, rows):
         """n same-size device images -> list of n files"""
-        n = len(d_bgra)
-        cap = int(self.l.pf_png_bound(cols, rows))
-        bufs = [np.empty(cap, np.uint8) for _ in range(n)]
-        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_bgra]); outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        sizes = (C.c_size_t * n)()
-        self._chk(self.l.pf_png_encode_batch_dev(self.h, n, srcs, cols, rows, outs, C.c_size_t(cap), sizes))
-        return [bufs[k][:sizes[k]].tobytes() for k in range(n)]
+        return self._file_batch_call(self.l.pf_png_bound, self.l.pf_png_encode_batch_dev, d_bgra, cols, rows)
 
     def stitch_result_png(self, shape=None, cap=None):
         """the PNG of the composite the last stitch_step left in HBM; shape = (rows, cols) of that step (default: the last stitch_step made
         through this object), used only to size the buffer"""
         rows, cols = shape if shape is not None else getattr(self, "_step_shape", (1, 1))
-        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_result_png(self.h, b, c, s), cap)
+        return self._file_call(self.l.pf_png_bound, cols, rows, lambda b, c, s: self.l.pf_stitch_result_png(self.h, b, c, s), cap)
 
     def stitch_batch_result_png(self, frame, shape, cap=None):
         """the PNG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
         rows, cols = shape
-        return self._png_call(cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
+        return self._file_call(self.l.pf_png_bound, cols, rows, lambda b, c, s: self.l.pf_stitch_batch_result_png(self.h, frame, b, c, s), cap)
 
     # ---- JPEG files made on the device (pf_jpeg_*): every method returns the file as bytes; params = a JpegParams or None (defaults) ----
-    def _jpeg_call(self, cols, rows, params, call, cap=None):
-        """call(params_ref, buffer, cap, size_ref) -> rc.  cap=None: pf_jpeg_bound.  A short buffer raises PngCapacityError carrying the needed size."""
-        pr = C.byref(params) if params is not None else None
-        cap = int(self.l.pf_jpeg_bound(cols, rows, pr)) if cap is None else int(cap)
-        buf = np.empty(max(cap, 1), np.uint8); size = C.c_size_t(0)
-        rc = call(pr, _p(buf), C.c_size_t(cap), C.byref(size))
-        if rc != 0 and 0 < cap < size.value:
-            raise PngCapacityError("panoflow error %d: %s" % (rc, self.l.pf_last_error(self.h).decode()), size.value)
-        self._chk(rc)
-        return buf[:size.value].tobytes()
-
     def jpeg_encode(self, image, params=None, cap=None):
         """host BGRA (rows, cols, 4) array, any row stride -> JPEG file bytes"""
-        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_jpeg_encode(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, pr, b, c, s), cap)
+        a, cols, rows, step = _bgra(image)
+        return self._file_call(self.l.pf_jpeg_bound, cols, rows, lambda pr, b, c, s: self.l.pf_jpeg_encode(self.h, _p(a), step, cols, rows, pr, b, c, s), cap, _ref(params))
 
     def jpeg_encode_dev(self, d_bgra, cols, rows, params=None, cap=None):
-        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_jpeg_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, pr, b, c, s), cap)
+        return self._file_call(self.l.pf_jpeg_bound, cols, rows, lambda pr, b, c, s: self.l.pf_jpeg_encode_dev(self.h, C.c_void_p(d_bgra), cols, rows, pr, b, c, s), cap, _ref(params))
 
     def jpeg_encode_batch_dev(self, d_bgra, cols, rows, params=None):
         """n same-size device images -> list of n files"""
-        n = len(d_bgra)
-        pr = C.byref(params) if params is not None else None
-        cap = int(self.l.pf_jpeg_bound(cols, rows, pr))
-        bufs = [np.empty(max(cap, 1), np.uint8) for _ in range(n)]
-        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_bgra]); outs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-        sizes = (C.c_size_t * n)()
-        self._chk(self.l.pf_jpeg_encode_batch_dev(self.h, n, srcs, cols, rows, pr, outs, C.c_size_t(cap), sizes))
-        return [bufs[k][:sizes[k]].tobytes() for k in range(n)]
+        return self._file_batch_call(self.l.pf_jpeg_bound, self.l.pf_jpeg_encode_batch_dev, d_bgra, cols, rows, _ref(params))
 
     def stitch_result_jpeg(self, params=None, shape=None, cap=None):
         """the JPEG of the composite the last stitch_step left in HBM; shape = (rows, cols) of that step (default: the last stitch_step made
         through this object), used only to size the buffer"""
         rows, cols = shape if shape is not None else getattr(self, "_step_shape", (1, 1))
-        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_stitch_result_jpeg(self.h, pr, b, c, s), cap)
+        return self._file_call(self.l.pf_jpeg_bound, cols, rows, lambda pr, b, c, s: self.l.pf_stitch_result_jpeg(self.h, pr, b, c, s), cap, _ref(params))
 
     def stitch_batch_result_jpeg(self, frame, shape, params=None, cap=None):
         """the JPEG of frame slot `frame` of the last stitch_step_batch; shape = (rows, cols) of that call"""
         rows, cols = shape
-        return self._jpeg_call(cols, rows, params, lambda pr, b, c, s: self.l.pf_stitch_batch_result_jpeg(self.h, frame, pr, b, c, s), cap)
+        return self._file_call(self.l.pf_jpeg_bound, cols, rows, lambda pr, b, c, s: self.l.pf_stitch_batch_result_jpeg(self.h, frame, pr, b, c, s), cap, _ref(params))
 
     # ---- TIFF files decoded on the device (pf_tiff_*): `data` = the file's bytes ----
     def tiff_set_inflate(self, on):
@@ -804,19 +806,14 @@ class Context:
         n = len(datas)
         bufs = [np.frombuffer(bytes(d), np.uint8) for d in datas]
         files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)(*[b.size for b in bufs])
-        outs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_outs])
-        self._chk(self.l.pf_tiff_decode_batch_dev(self.h, n, files, sizes, cols, rows, outs))
+        self._chk(self.l.pf_tiff_decode_batch_dev(self.h, n, files, sizes, cols, rows, _dptrs(d_outs, n)))
 
     # ---- resize on the device (pf_resize*): Pillow's Image.resize of an RGBA image, byte for byte; filter = one of RESIZE_* ----
     def resize(self, image, out_cols, out_rows, filter=RESIZE_LANCZOS, out=None):
         """host BGRA (rows, cols, 4) array, any row stride -> host (out_rows, out_cols, 4); out: a destination array (its row stride is kept)"""
-        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        if out is None:
-            out = np.empty((max(out_rows, 0), max(out_cols, 0), 4), np.uint8)
-        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(out_cols, 0) * 4
-        self._chk(self.l.pf_resize(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, _p(out), C.c_size_t(step), out_cols, out_rows, int(filter)))
+        a, cols, rows, step = _bgra(image)
+        out, ostep = _dst(out, out_cols, out_rows)
+        self._chk(self.l.pf_resize(self.h, _p(a), step, cols, rows, _p(out), ostep, out_cols, out_rows, int(filter)))
         return out
 
     def resize_dev(self, d_src, cols, rows, d_dst, out_cols, out_rows, filter=RESIZE_LANCZOS):
@@ -825,8 +822,7 @@ class Context:
     def resize_batch_dev(self, d_srcs, cols, rows, d_dsts, out_cols, out_rows, filter=RESIZE_LANCZOS):
         """n same-size device images -> n device images of out_cols x out_rows, one drain"""
         n = len(d_srcs)
-        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_srcs]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_dsts])
-        self._chk(self.l.pf_resize_batch_dev(self.h, n, srcs, cols, rows, dsts, out_cols, out_rows, int(filter)))
+        self._chk(self.l.pf_resize_batch_dev(self.h, n, _dptrs(d_srcs), cols, rows, _dptrs(d_dsts, n), out_cols, out_rows, int(filter)))
 
     def stitch_result_resized_dev(self, out_cols, out_rows, d_dst, filter=RESIZE_LANCZOS):
         """the composite the last stitch_step left in HBM, resized into d_dst (out_cols * out_rows * 4 bytes of device memory)"""
@@ -846,13 +842,9 @@ class Context:
     # ---- reprojection on the device (pf_reproject*): params = a ReprojectParams (reproject_params()) ----
     def reproject(self, image, out_cols, out_rows, params, out=None):
         """host BGRA (rows, cols, 4) equirectangular sphere, any row stride -> host (out_rows, out_cols, 4); out: a destination array (its row stride is kept)"""
-        a = np.asarray(image, dtype=np.uint8); rows, cols, _ = a.shape
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        if out is None:
-            out = np.empty((max(out_rows, 0), max(out_cols, 0), 4), np.uint8)
-        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(out_cols, 0) * 4
-        self._chk(self.l.pf_reproject(self.h, _p(a), C.c_size_t(a.strides[0]), cols, rows, _p(out), C.c_size_t(step), out_cols, out_rows, C.byref(params)))
+        a, cols, rows, step = _bgra(image)
+        out, ostep = _dst(out, out_cols, out_rows)
+        self._chk(self.l.pf_reproject(self.h, _p(a), step, cols, rows, _p(out), ostep, out_cols, out_rows, C.byref(params)))
         return out
 
     def reproject_dev(self, d_src, cols, rows, d_dst, out_cols, out_rows, params):
@@ -861,8 +853,7 @@ class Context:
     def reproject_batch_dev(self, d_srcs, cols, rows, d_dsts, out_cols, out_rows, params):
         """n same-size device images -> n device images of out_cols x out_rows, one drain"""
         n = len(d_srcs)
-        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_srcs]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_dsts])
-        self._chk(self.l.pf_reproject_batch_dev(self.h, n, srcs, cols, rows, dsts, out_cols, out_rows, C.byref(params)))
+        self._chk(self.l.pf_reproject_batch_dev(self.h, n, _dptrs(d_srcs), cols, rows, _dptrs(d_dsts, n), out_cols, out_rows, C.byref(params)))
 
     def reproject_cube_dev(self, d_src, cols, rows, d_faces, face_size, params):
         """one device sphere -> six device faces of face_size x face_size (FACE_* order), one launch"""
@@ -886,13 +877,9 @@ class Context:
     # ---- lens remap on the device (pf_lens_*): lens = a Lens (lens()) ----
     def lens_remap(self, photo, cols, rows, lens, out=None):
         """host BGRA photo (photo_rows, photo_cols, 4), any row stride -> host canvas (rows, cols, 4); out: a destination array (its row stride is kept)"""
-        a = np.asarray(photo, dtype=np.uint8); photo_rows, photo_cols, _ = a.shape
-        if a.strides[2] != 1 or a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
-        if out is None:
-            out = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8)
-        step = out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(cols, 0) * 4
-        self._chk(self.l.pf_lens_remap(self.h, _p(a), C.c_size_t(a.strides[0]), photo_cols, photo_rows, _p(out), C.c_size_t(step), cols, rows, C.byref(lens)))
+        a, photo_cols, photo_rows, step = _bgra(photo)
+        out, ostep = _dst(out, cols, rows)
+        self._chk(self.l.pf_lens_remap(self.h, _p(a), step, photo_cols, photo_rows, _p(out), ostep, cols, rows, C.byref(lens)))
         return out
 
     def lens_remap_dev(self, d_photo, photo_cols, photo_rows, d_canvas, cols, rows, lens):
@@ -901,9 +888,7 @@ class Context:
     def lens_remap_batch_dev(self, d_photos, photo_cols, photo_rows, d_canvases, cols, rows, lenses):
         """n same-size device photos -> n device canvases of cols x rows, image k under lenses[k], one drain"""
         n = len(d_photos)
-        srcs = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_photos]); dsts = (C.c_void_p * n)(*[C.c_void_p(int(x)) for x in d_canvases])
-        arr = (Lens * n)(*lenses)
-        self._chk(self.l.pf_lens_remap_batch_dev(self.h, n, srcs, photo_cols, photo_rows, dsts, cols, rows, arr))
+        self._chk(self.l.pf_lens_remap_batch_dev(self.h, n, _dptrs(d_photos), photo_cols, photo_rows, _dptrs(d_canvases, n), cols, rows, (Lens * n)(*lenses)))
 
     def stage_lens_coords(self, photo_cols, photo_rows, cols, rows, lens):
         """(fx, fy): the device's quantised photo coordinates of every canvas pixel, int32 (rows, cols)"""
