@@ -15,6 +15,18 @@
  *     blend : float in [0,1] = weight of the RIGHT image                   (CV_32FC1)
  *     map   : uint8 region codes 0/50/100/150                              (CV_8UC1)
  *   - every call is synchronous on return; a context is owned by one host thread and one GPU.
+ *   - row steps (host-buffer entry points): a step is the distance in bytes between the starts of two rows of the caller's plane, at
+ *     least the row's width (cols x 4 for BGRA and float planes, x 8 for flows, x 1 for the map, x 3 / x 12 for the colour wheel / a
+ *     panel) and a multiple of the element's size; bytes of a row beyond its width are never read and never written.  A step below
+ *     the row width is PF_ERR_ARG "row step too small", checked before any work; the step of an optional plane that is NULL is
+ *     not looked at (0 will do).  Planes that share ONE step argument share the step: L and R (and the merged image of pf_stitch_gather,
+ *     the images of a batch, a rig's top and left images), the two flows, the outputs of a batch, the two panels of pf_stitch_visualize;
+ *     pf_stitch_prepare / pf_stitch_match write overlapped_l / overlapped_r at the INPUT step (step_bytes), and merged_dis is packed.
+ *   - device pointers (the _dev entry points): packed planes at their element's natural alignment -- 4 bytes for BGRA, blend and
+ *     other float planes, 8 bytes for flows ((dx, dy) pairs are read and written whole) -- anywhere inside an allocation; nothing
+ *     wider is ever required (DESIGN.md 8.9 lists the kernels).  No output of a call may overlap an input or another output of the
+ *     same call (inputs may repeat or overlap each other): outputs are written while inputs are still gathered from.  Both are
+ *     PF_ERR_ARG before any work ("... is not 4-byte aligned", "... overlaps ...").
  *   - there is NO CPU fallback: without a usable gfx950 device pf_create() fails.
  * ============================================================================================= */
 #ifndef PANOFLOW_H_
@@ -153,7 +165,7 @@ int pf_novel_view(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int
  * bits and a per-block scratch area in the context's arena (pre-sized by pf_create).  The one exception: a window that reaches across
  * the whole canvas (k/2 >= min(cols, rows): canvases more than ~260 times taller than wide) returns PF_ERR_ARG. */
 /* Stitchtools::prepare, CPU/StitchTool.cpp:7-36 (MatchImages :38-50, GenerateBlend :98-146,
- * countblend :148-191).  merged_dis may be NULL.  All planes cols x rows, packed rows of `step`. */
+ * countblend :148-191).  Every output may be NULL.  All planes cols x rows; overlapped_l / overlapped_r have the inputs' step_bytes. */
 int pf_stitch_prepare(pf_ctx* ctx, const uint8_t* l_bgra, const uint8_t* r_bgra, int cols, int rows, size_t step_bytes,
                       uint8_t* map_out, size_t map_step_bytes, uint8_t* overlapped_l, uint8_t* overlapped_r,
                       float* blend_out, size_t blend_step_bytes, float* merged_dis /* packed, nullable */);
@@ -302,7 +314,8 @@ int pf_rig_stitch_dev(pf_ctx* ctx, const pf_rig_plan* rig, const uint8_t* d_top,
                       int max_percentage, uint8_t* const* d_out);
 
 /* ---- device-resident entry points (packed buffers already in this context's HBM) -----------
- * Same semantics as above; used by bench.py (inputs resident when the clock starts) and by the
+ * Same semantics as above, alignment and aliasing as under "Conventions" (d_out inside d_l, say, is refused: the blend gathers from
+ * the images it would be overwriting); used by bench.py (inputs resident when the clock starts) and by the
  * multi-GPU driver.  Pointers are device pointers on the context's device.  The calls are synchronous on
  * return, but they run on the context's own non-blocking streams and do NOT wait for work the caller has
  * in flight on other streams: inputs produced there (e.g. by a framework's kernels) must be complete --

@@ -236,4 +236,34 @@ int check_dims(pf_ctx* c, int cols, int rows, int pad) {
   return 0;
 }
 
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + nb && pb < pa + na;
+}
+
+// The caller-owned planes of a core device form (pf_flow_bidir_dev, pf_blend_dev, pf_novel_view*_dev, pf_vis_panel_dev): each at its
+// element's natural alignment (BGRA and float planes 4, flows 8: the kernels read them as uchar4 / float / float2), and no output
+// inside an input or another output -- the kernels gather from the inputs while the outputs are written.  A null p is an optional
+// plane the caller left out.  index < 0: the argument is no array.  Refusals in the words of check_dev_images (pf_api_image.inl).
+struct DevPlane { const void* p; size_t bytes; unsigned align; bool out; const char* noun; int index; };
+int check_dev_planes(pf_ctx* c, const char* fn, const DevPlane* pl, size_t n) {
+  auto name = [](const DevPlane& d, char (&buf)[48]) { if (d.index < 0) snprintf(buf, sizeof buf, "%s", d.noun); else snprintf(buf, sizeof buf, "%s %d", d.noun, d.index); return buf; };
+  char a[48], b[48];
+  for (size_t k = 0; k < n; ++k)
+    if (pl[k].p && (reinterpret_cast<uintptr_t>(pl[k].p) & (pl[k].align - 1))) return fail(c, PF_ERR_ARG, "%s: device plane %s is not %u-byte aligned", fn, name(pl[k], a), pl[k].align);
+  for (size_t k = 0; k < n; ++k) {
+    if (!pl[k].out || !pl[k].p) continue;
+    for (size_t q = 0; q < n; ++q)
+      if (q != k && pl[q].p && (!pl[q].out || q > k) && ranges_overlap(pl[k].p, pl[k].bytes, pl[q].p, pl[q].bytes))
+        return fail(c, PF_ERR_ARG, "%s: %s overlaps %s", fn, name(pl[k], a), name(pl[q], b));
+  }
+  return 0;
+}
+// ... and the alignment alone of an array of n planes (NULL entries skipped), for the forms that check their own aliasing rules
+int check_dev_align(pf_ctx* c, const char* fn, const char* noun, const uint8_t* const* p, size_t n, unsigned align = 4) {
+  for (size_t k = 0; k < n; ++k)
+    if (p[k] && (reinterpret_cast<uintptr_t>(p[k]) & (align - 1))) return fail(c, PF_ERR_ARG, "%s: device plane %s %d is not %u-byte aligned", fn, noun, (int)k, align);
+  return 0;
+}
+
 // Levels up to this many pixels trade launches for longer kernels (upsample inside the next Gaussian, second median inside the

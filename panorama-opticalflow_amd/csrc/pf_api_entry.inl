@@ -4,6 +4,12 @@ int pf_flow_bidir_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int col
   if (int e = use(c)) return e;
   CallGuard guard_(c);
   if (!d_l || !d_r || !d_l2r || !d_r2l) return fail(c, PF_ERR_ARG, "null device pointer");
+  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  {
+    const size_t n = size_t(cols) * rows;
+    const DevPlane pl[] = {{d_l, n * 4, 4, false, "d_l", -1}, {d_r, n * 4, 4, false, "d_r", -1}, {d_l2r, n * 8, 8, true, "d_flow_l2r", -1}, {d_r2l, n * 8, 8, true, "d_flow_r2l", -1}};
+    if (int e = check_dev_planes(c, "pf_flow_bidir_dev", pl, 4)) return e;
+  }
   const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT};  // OpticalFlow.cpp:134,139
   float* outs[2] = {d_l2r, d_r2l};
   const int pad = cols / 20;                            // OpticalFlow.cpp:113
@@ -18,6 +24,12 @@ int pf_blend_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r, const float*
   CallGuard guard_(c);
   if (!d_l || !d_r || !d_l2r || !d_r2l || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
+  {
+    const size_t n = size_t(cols) * rows;
+    const DevPlane pl[] = {{d_l, n * 4, 4, false, "d_l", -1}, {d_r, n * 4, 4, false, "d_r", -1}, {d_l2r, n * 8, 8, false, "d_flow_l2r", -1}, {d_r2l, n * 8, 8, false, "d_flow_r2l", -1},
+                           {d_blend, n * 4, 4, false, "d_blend", -1}, {d_out, n * 4, 4, true, "d_out", -1}};
+    if (int e = check_dev_planes(c, "pf_blend_dev", pl, 6)) return e;
+  }
   { PROF(c, c->s_main, "blend"); launch_blend(c->s_main, d_l, d_r, d_l2r, d_r2l, d_blend, cols, rows, d_out); }
   HIPCHK(c, hipGetLastError());
   return finish(c);
@@ -29,6 +41,12 @@ int pf_novel_view_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int col
   CallGuard guard_(c);
   if (!d_l || !d_r || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "null device pointer");
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+  {
+    const size_t n = size_t(cols) * rows;
+    const DevPlane pl[] = {{d_l, n * 4, 4, false, "d_l", -1}, {d_r, n * 4, 4, false, "d_r", -1}, {d_blend, n * 4, 4, false, "d_blend", -1}, {d_out, n * 4, 4, true, "d_out", -1},
+                           {d_l2r, n * 8, 8, true, "d_flow_l2r", -1}, {d_r2l, n * 8, 8, true, "d_flow_r2l", -1}};
+    if (int e = check_dev_planes(c, "pf_novel_view_dev", pl, 6)) return e;
+  }
   float* f0 = d_l2r ? d_l2r : (float*)ensure(c, "nv_flow_l2r", size_t(cols) * rows * 8);
   float* f1 = d_r2l ? d_r2l : (float*)ensure(c, "nv_flow_r2l", size_t(cols) * rows * 8);
   if (!f0 || !f1) return PF_ERR_NOMEM;
@@ -138,6 +156,19 @@ int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, c
   if (int e = use(c)) return e;
   c->vis_step_valid = false;   // lane 0 solves in this context's arena
   if (n_pairs < 0 || !d_l || !d_r || !d_blend || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
+  if (n_pairs > 0) {
+    // the pairs of a batch share launches and the lanes run side by side: every plane of the call is checked against every other, before any work
+    if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+    const size_t n = size_t(cols) * rows;
+    std::vector<DevPlane> pl;
+    for (int p = 0; p < n_pairs; ++p) {
+      if (!d_l[p] || !d_r[p] || !d_blend[p] || !d_out[p]) return fail(c, PF_ERR_ARG, "null device pointer (pair %d)", p);
+      pl.push_back({d_l[p], n * 4, 4, false, "d_l", p}); pl.push_back({d_r[p], n * 4, 4, false, "d_r", p}); pl.push_back({d_blend[p], n * 4, 4, false, "d_blend", p});
+      pl.push_back({d_out[p], n * 4, 4, true, "d_out", p});
+      pl.push_back({d_l2r ? d_l2r[p] : nullptr, n * 8, 8, true, "d_flow_l2r", p}); pl.push_back({d_r2l ? d_r2l[p] : nullptr, n * 8, 8, true, "d_flow_r2l", p});
+    }
+    if (int e = check_dev_planes(c, "pf_novel_view_batch_dev", pl.data(), pl.size())) return e;
+  }
   // three streams per lane + this context's blend-ramp and copy streams
   return run_lanes(c, n_pairs, in_flight, cols, rows, 3, "pf_novel_view_batch_dev", [&](pf_ctx* lane, int first, int count) {
     return novel_view_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_blend, d_out, d_l2r, d_r2l);
@@ -171,8 +202,10 @@ int pf_novel_view(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int r
   CallGuard guard_(c);
   if (!l || !r) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  if (step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
   if (out && !blend) return fail(c, PF_ERR_ARG, "blend is required when out_bgra is given");
+  // a step is checked where its plane is given: pf_flow_bidir passes no blend and no output, each with step 0
+  if (step < size_t(cols) * 4 || (out && (ostep < size_t(cols) * 4 || bstep < size_t(cols) * 4)) || ((f_l2r || f_r2l) && fstep < size_t(cols) * 8))
+    return fail(c, PF_ERR_ARG, "row step too small");
   const size_t ib = size_t(cols) * rows * 4, fb = size_t(cols) * rows * 8;
   uint8_t* dl = (uint8_t*)ensure(c, "h_img0", ib); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", ib);
   float* d0 = (float*)ensure(c, "h_flow0", fb); float* d1 = (float*)ensure(c, "h_flow1", fb);

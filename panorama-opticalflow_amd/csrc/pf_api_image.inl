@@ -22,11 +22,7 @@ int resident_result(pf_ctx* c, const char* fn, const int* frame, DevImage* out) 
   return 0;
 }
 
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
-
+// (ranges_overlap: pf_api_ctx.inl, beside the checks of the core device forms)
 // n device images of src_bytes each and, where d_dst is given, their n destinations of dst_bytes each: none null, all 4-byte aligned,
 // no destination inside any source.  The refusals speak the family's words ("resize: destination 1 overlaps source 0").
 int check_dev_images(pf_ctx* c, const char* family, int n, const uint8_t* const* d_src, size_t src_bytes, uint8_t* const* d_dst = nullptr, size_t dst_bytes = 0,

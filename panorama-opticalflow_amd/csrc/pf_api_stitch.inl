@@ -359,7 +359,8 @@ int pf_stitch_step_planned(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t*
 // simply uploads as usual and the prefetched copy is dropped.  NULL cancels.
 int pf_stitch_prefetch(pf_ctx* c, const uint8_t* next_l, int cols, int rows, size_t step) {
   if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
-  if (next_l && (cols <= 0 || rows <= 0 || step < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "bad argument");
+  if (next_l && (cols <= 0 || rows <= 0)) return fail(c, PF_ERR_ARG, "bad argument");
+  if (next_l && step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
   c->hint.src = next_l; c->hint.cols = cols; c->hint.rows = rows; c->hint.step = step;
   return 0;
 }
@@ -411,10 +412,7 @@ int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, 
   if (plan) collect_plan_diff(lane, first, count, diff);
   return check_sweeps(lane);
 }
-bool overlaps(const void* a, const void* b, size_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
-}
+bool overlaps(const void* a, const void* b, size_t bytes) { return ranges_overlap(a, bytes, b, bytes); }
 }  // namespace
 
 static int stitch_batch_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
@@ -428,6 +426,12 @@ static int stitch_batch_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames,
   const size_t bytes = size_t(cols) * rows * 4;
   for (int k = 0; k < n_frames; ++k)
     if (!d_l[k] || !d_r[k] || !d_out[k]) return fail(c, PF_ERR_ARG, "null device pointer (frame %d)", k);
+  {
+    const char* const fn = plan ? "pf_stitch_step_batch_planned_dev" : "pf_stitch_step_batch_dev";
+    if (int e = check_dev_align(c, fn, "d_l", d_l, n_frames)) return e;
+    if (int e = check_dev_align(c, fn, "d_r", d_r, n_frames)) return e;
+    if (int e = check_dev_align(c, fn, "d_out", d_out, n_frames)) return e;
+  }
   // a composite is written while the frame's inputs (and those of the frames in its launches) are still read: no aliasing
   for (int k = 0; k < n_frames; ++k)
     for (int j = 0; j < n_frames; ++j)
@@ -594,6 +598,8 @@ int pf_stitch_plan_create_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r,
   if (int e = check_dims(c, cols, rows, cols / 20)) return e;
   const RampGeom g = ramp_geom(cols, rows);
   if (int e = check_blend_ramp(c, cols, rows, g)) return e;
+  const uint8_t* const imgs[2] = {d_l, d_r};
+  if (int e = check_dev_align(c, "pf_stitch_plan_create_dev", "image", imgs, 2)) return e;
   return stitch_plan_make(c, d_l, d_r, cols, rows, g, plan_out);
 }
 int pf_stitch_plan_destroy(pf_ctx* c, pf_stitch_plan* plan) {
@@ -760,6 +766,7 @@ int pf_rig_plan_create_dev(pf_ctx* c, int n_steps, const uint8_t* d_top, const u
   const uint8_t* d_img[kMaxBatch + 1];
   d_img[0] = d_top;
   for (int i = 0; i < n_steps; ++i) { if (!d_l[i]) return fail(c, PF_ERR_ARG, "null device pointer (step %d)", i + 1); d_img[i + 1] = d_l[i]; }
+  if (int e = check_dev_align(c, "pf_rig_plan_create_dev", "image", d_img, size_t(n_steps) + 1)) return e;
   return rig_plan_make(c, n_steps, d_img, cols, rows, g, out);
 }
 int pf_rig_plan_destroy(pf_ctx* c, pf_rig_plan* rig) {
@@ -945,6 +952,8 @@ int pf_rig_stitch_batch_dev(pf_ctx* c, const pf_rig_plan* rig, int n_frames, con
     }
     if (!d_out[size_t(k) * ns + ns - 1]) return fail(c, PF_ERR_ARG, "frame %d: the last step's d_out must not be NULL", k);
   }
+  if (int e = check_dev_align(c, what, "image", img.data(), img.size())) return e;
+  if (int e = check_dev_align(c, what, "d_out", outs.data(), outs.size())) return e;
   // a composite is written while inputs of the call are still read: no aliasing (the rules of pf_stitch_step_batch_dev)
   for (size_t a = 0; a < outs.size(); ++a) {
     for (size_t j = 0; j < img.size(); ++j)

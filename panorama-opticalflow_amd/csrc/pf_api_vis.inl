@@ -114,6 +114,11 @@ int pf_vis_panel_dev(pf_ctx* c, const float* d_flow, const uint8_t* d_img, int c
   CallGuard guard_(c);
   if (!d_flow || !d_img || !d_out) return fail(c, PF_ERR_ARG, "null device pointer");
   if (int e = check_image(c, cols, rows)) return e;
+  {
+    const size_t n = size_t(cols) * rows;
+    const DevPlane pl[] = {{d_flow, n * 8, 8, false, "d_flow", -1}, {d_img, n * 4, 4, false, "d_image", -1}, {d_out, n * 12, 4, true, "d_out", -1}};
+    if (int e = check_dev_planes(c, "pf_vis_panel_dev", pl, 3)) return e;
+  }
   return vis_panel_dev(c, d_flow, d_img, cols, rows, d_out);
 }
 

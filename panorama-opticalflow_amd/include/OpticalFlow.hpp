@@ -32,9 +32,12 @@ struct NovelViewUtil {
   static Mat combineNovelViews(const Mat& imageL, const Mat& imageR, const Mat& flowLtoR, const Mat& flowRtoL, const Mat& blend) {
     if (imageL.type() != CV_8UC4 || imageR.type() != CV_8UC4 || flowLtoR.type() != CV_32FC2 || flowRtoL.type() != CV_32FC2 || blend.type() != CV_32FC1)
       throw VrCamException("combineNovelViews: unexpected Mat types");
-    if (imageL.step != imageR.step || flowLtoR.step != flowRtoL.step) throw VrCamException("combineNovelViews: mismatched row steps");
+    for (const Mat* m : {&imageR, &flowLtoR, &flowRtoL, &blend})
+      if (m->rows != imageL.rows || m->cols != imageL.cols) throw VrCamException("combineNovelViews: images, flows and blend differ in size");
+    std::vector<Mat> im = {imageL, imageR}, fl = {flowLtoR, flowRtoL};
+    pano::shareStep(im); pano::shareStep(fl);
     Mat blendImage(imageL.rows, imageL.cols, CV_8UC4);
-    pano::check(pf_blend(pano::context(), imageL.data, imageR.data, imageL.step, flowLtoR.ptr<float>(), flowRtoL.ptr<float>(), flowLtoR.step,
+    pano::check(pf_blend(pano::context(), im[0].data, im[1].data, im[0].step, fl[0].ptr<float>(), fl[1].ptr<float>(), fl[0].step,
                          blend.ptr<float>(), blend.step, imageL.cols, imageL.rows, blendImage.data, blendImage.step));
     return blendImage;
   }

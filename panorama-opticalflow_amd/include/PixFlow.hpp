@@ -37,9 +37,10 @@ struct PixFlow : public OpticalFlowInterface {
   ~PixFlow() {}
 
   void computeOpticalFlow(const Mat& rgba0byte, const Mat& rgba1byte, Mat& flow, DirectionHint hint) override {
-    if (rgba0byte.type() != CV_8UC4 || rgba1byte.type() != CV_8UC4 || rgba0byte.rows != rgba1byte.rows || rgba0byte.cols != rgba1byte.cols ||
-        rgba0byte.step != rgba1byte.step)
+    if (rgba0byte.type() != CV_8UC4 || rgba1byte.type() != CV_8UC4 || rgba0byte.rows != rgba1byte.rows || rgba0byte.cols != rgba1byte.cols)
       throw VrCamException("computeOpticalFlow: inputs must be two CV_8UC4 images of equal size");
+    std::vector<Mat> im = {rgba0byte, rgba1byte};
+    pano::shareStep(im);
     Mat out(rgba0byte.rows, rgba0byte.cols, CV_32FC2);
     // this object's parameters for this solve; the shared per-thread context then returns to the factory's presets, which the other classes
     // (NovelViewGeneratorAsymmetricFlow, Stitchtools: they only know algorithm NAMES, CPU/OpticalFlow.cpp:128) rely on
@@ -47,7 +48,7 @@ struct PixFlow : public OpticalFlowInterface {
     const pf_solver_params sp = {pyrScaleFactor, smoothnessCoef, verticalRegularizationCoef, horizontalRegularizationCoef, gradientStepSize, downscaleFactor,
                                  directionalRegularizationCoef};
     pano::check(pf_set_solver_params(ctx, &sp));
-    const int rc = pf_flow(ctx, rgba0byte.data, rgba1byte.data, rgba0byte.cols, rgba0byte.rows, rgba0byte.step, MaxPercentage, int(hint), out.ptr<float>(), out.step);
+    const int rc = pf_flow(ctx, im[0].data, im[1].data, im[0].cols, im[0].rows, im[0].step, MaxPercentage, int(hint), out.ptr<float>(), out.step);
     const std::string msg = rc ? pf_last_error(ctx) : "";
     pf_set_solver_params(ctx, nullptr);
     if (rc) throw VrCamException("panoflow: " + msg);

@@ -95,11 +95,14 @@ static inline Mat stitchStep(const Mat& colorImageL, const Mat* colorImageR, con
   const int maxPct = pf_max_percentage_by_name(flowAlgName.c_str());
   if (maxPct < 0) throw util::VrCamException("unrecognized flow algorithm name: " + flowAlgName);
   if (colorImageL.type() != CV_8UC4 || (colorImageR && (colorImageR->type() != CV_8UC4 || colorImageR->rows != colorImageL.rows ||
-                                                         colorImageR->cols != colorImageL.cols || colorImageR->step != colorImageL.step)))
+                                                         colorImageR->cols != colorImageL.cols)))
     throw util::VrCamException("stitchStep: inputs must be CV_8UC4 images of equal size");
+  std::vector<Mat> im = {colorImageL};
+  if (colorImageR) im.push_back(*colorImageR);
+  pano::shareStep(im);
   Mat out(colorImageL.rows, colorImageL.cols, CV_8UC4);
-  pano::check(pf_stitch_step(pano::context(), colorImageL.data, colorImageR ? colorImageR->data : nullptr, colorImageL.cols, colorImageL.rows,
-                             colorImageL.step, maxPct, out.data, out.step));
+  pano::check(pf_stitch_step(pano::context(), im[0].data, colorImageR ? im[1].data : nullptr, colorImageL.cols, colorImageL.rows,
+                             im[0].step, maxPct, out.data, out.step));
   return out;
 }
 
@@ -111,10 +114,12 @@ class StitchPlan {
   StitchPlan() {}
   StitchPlan(const Mat& colorImageL, const Mat* colorImageR) {
     if (colorImageL.type() != CV_8UC4 || (colorImageR && (colorImageR->type() != CV_8UC4 || colorImageR->rows != colorImageL.rows ||
-                                                           colorImageR->cols != colorImageL.cols || colorImageR->step != colorImageL.step)))
+                                                           colorImageR->cols != colorImageL.cols)))
       throw util::VrCamException("StitchPlan: inputs must be CV_8UC4 images of equal size");
-    pano::check(pf_stitch_plan_create(pano::context(), colorImageL.data, colorImageR ? colorImageR->data : nullptr, colorImageL.cols, colorImageL.rows,
-                                      colorImageL.step, &plan_));
+    std::vector<Mat> im = {colorImageL};
+    if (colorImageR) im.push_back(*colorImageR);
+    pano::shareStep(im);
+    pano::check(pf_stitch_plan_create(pano::context(), im[0].data, colorImageR ? im[1].data : nullptr, colorImageL.cols, colorImageL.rows, im[0].step, &plan_));
   }
   ~StitchPlan() { reset(); }
   StitchPlan(const StitchPlan&) = delete;
@@ -155,13 +160,16 @@ class RigPlan {
  public:
   RigPlan() {}
   RigPlan(const Mat& colorImageT, const std::vector<Mat>& colorImagesL) {
-    std::vector<const uint8_t*> l;
+    std::vector<Mat> im = {colorImageT};
     for (const Mat& m : colorImagesL) {
-      if (colorImageT.type() != CV_8UC4 || m.type() != CV_8UC4 || m.rows != colorImageT.rows || m.cols != colorImageT.cols || m.step != colorImageT.step)
+      if (colorImageT.type() != CV_8UC4 || m.type() != CV_8UC4 || m.rows != colorImageT.rows || m.cols != colorImageT.cols)
         throw util::VrCamException("RigPlan: inputs must be CV_8UC4 images of equal size");
-      l.push_back(m.data);
+      im.push_back(m);
     }
-    pano::check(pf_rig_plan_create(pano::context(), (int)l.size(), colorImageT.data, l.data(), colorImageT.cols, colorImageT.rows, colorImageT.step, &rig_));
+    pano::shareStep(im);
+    std::vector<const uint8_t*> l;
+    for (size_t i = 1; i < im.size(); ++i) l.push_back(im[i].data);
+    pano::check(pf_rig_plan_create(pano::context(), (int)l.size(), im[0].data, l.data(), colorImageT.cols, colorImageT.rows, im[0].step, &rig_));
   }
   ~RigPlan() { reset(); }
   RigPlan(const RigPlan&) = delete;
@@ -196,11 +204,14 @@ static inline Mat stitchStep(const StitchPlan& plan, const Mat& colorImageL, con
   const int maxPct = pf_max_percentage_by_name(flowAlgName.c_str());
   if (maxPct < 0) throw util::VrCamException("unrecognized flow algorithm name: " + flowAlgName);
   if (colorImageL.type() != CV_8UC4 || (colorImageR && (colorImageR->type() != CV_8UC4 || colorImageR->rows != colorImageL.rows ||
-                                                         colorImageR->cols != colorImageL.cols || colorImageR->step != colorImageL.step)))
+                                                         colorImageR->cols != colorImageL.cols)))
     throw util::VrCamException("stitchStep: inputs must be CV_8UC4 images of equal size");
+  std::vector<Mat> im = {colorImageL};
+  if (colorImageR) im.push_back(*colorImageR);
+  pano::shareStep(im);
   Mat out(colorImageL.rows, colorImageL.cols, CV_8UC4);
-  pano::check(pf_stitch_step_planned(pano::context(), plan.get(), colorImageL.data, colorImageR ? colorImageR->data : nullptr, colorImageL.cols,
-                                     colorImageL.rows, colorImageL.step, maxPct, out.data, out.step));
+  pano::check(pf_stitch_step_planned(pano::context(), plan.get(), im[0].data, colorImageR ? im[1].data : nullptr, colorImageL.cols,
+                                     colorImageL.rows, im[0].step, maxPct, out.data, out.step));
   return out;
 }
 

@@ -157,6 +157,16 @@ static inline void check(int rc) {
   if (rc != 0) throw util::VrCamException(std::string("panoflow: ") + pf_last_error(context()));
 }
 
+// Images that go behind ONE step argument of the C ABI (L and R, the two flows, a rig's inputs): as they are where their rows are the same
+// distance apart, else every one that is not packed is replaced by a packed copy.  cv::Mat arguments carry a step each, so a caller
+// may pass a wrapped padded buffer beside a Mat of its own.
+static inline void shareStep(std::vector<panocv::Mat>& m) {
+  bool same = true;
+  for (const panocv::Mat& x : m) same = same && x.step == m[0].step;
+  if (same) return;
+  for (panocv::Mat& x : m) if (x.step != size_t(x.cols) * x.elemSize()) x = x.clone();
+}
+
 }  // namespace pano
 
 #endif  // PANO_UTIL_HPP_

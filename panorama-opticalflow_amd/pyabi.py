@@ -228,6 +228,55 @@ def _dst(out, cols, rows):
     return out, C.c_size_t(out.strides[0] if out.ndim == 3 and out.shape[0] > 1 else max(cols, 0) * 4)
 
 
+def _rows(a, dtype):
+    """(array, row step in bytes): the (rows, cols[, channels]) array as it is where the elements of a row are packed (rows any distance
+    apart, as in padded[:, :cols]), else a contiguous copy -- _bgra() for planes of any type"""
+    a = np.asarray(a, dtype=dtype)
+    inner = a.itemsize
+    for ax in range(a.ndim - 1, 0, -1):
+        if a.strides[ax] != inner:
+            a = np.ascontiguousarray(a)
+            break
+        inner *= a.shape[ax]
+    if a.shape[0] > 1 and a.strides[0] < inner:
+        a = np.ascontiguousarray(a)
+    return a, (a.strides[0] if a.shape[0] > 1 else inner)
+
+
+def _shared(planes, dtype):
+    """(arrays, c_size_t step) of planes that go behind ONE step argument (L and R, the two flows, a rig's images): as they are where
+    their rows are the same distance apart, else contiguous copies"""
+    rs = [_rows(a, dtype) for a in planes]
+    if len(set(st for _, st in rs)) > 1:
+        rs = [_rows(np.ascontiguousarray(a), dtype) for a, _ in rs]
+    return [a for a, _ in rs], C.c_size_t(rs[0][1] if rs else 0)
+
+
+def _like(shape, dtype, step):
+    """a fresh plane of `shape` whose rows are `step` bytes apart (what an output that shares an input's step argument needs)"""
+    row = int(np.prod(shape[1:])) * np.dtype(dtype).itemsize
+    buf = np.empty((shape[0], max(int(step), row)), np.uint8)
+    strides, inner = [buf.strides[0]], row
+    for n in shape[1:]:
+        inner //= n
+        strides.append(inner)
+    return np.ndarray(tuple(shape), dtype, buffer=buf, strides=tuple(strides))
+
+
+def _outs(outs, shape, dtype):
+    """(arrays, c_size_t step): the caller's destination arrays (None: fresh ones) of one shape behind one step argument; a given array
+    keeps its row stride, its rows' elements must be packed and all given arrays must share the stride"""
+    outs = [np.empty(shape, dtype) if o is None else o for o in outs]
+    steps = set()
+    for o in outs:
+        assert o.dtype == np.dtype(dtype) and o.shape == tuple(shape), "destination of shape %r / %s expected" % (tuple(shape), np.dtype(dtype))
+        a, st = _rows(o, dtype)
+        assert a is o or np.shares_memory(a, o), "the elements of a destination's rows must be packed"
+        steps.add(st)
+    assert len(steps) <= 1, "destinations behind one step argument must share their row stride"
+    return outs, C.c_size_t(steps.pop() if steps else 0)
+
+
 def _dptrs(v, n=None):
     """sequence of device pointers (ints; 0 or None: NULL) -> c_void_p array of n entries (default len(v)); a shorter v leaves NULLs"""
     return (C.c_void_p * max(len(v) if n is None else n, 1))(*[C.c_void_p(int(x)) if x else None for x in v])
@@ -488,86 +537,96 @@ class Context:
             raise PanoflowError("panoflow error %d: %s" % (rc, self.l.pf_last_error(self.h).decode()))
 
     # ---- host-buffer entry points ----
-    def flow(self, i0, i1, max_pct, hint):
-        a = _u8(i0); b = _u8(i1); rows, cols, _ = a.shape
-        out = np.empty((rows, cols, 2), np.float32)
-        self._chk(self.l.pf_flow(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), max_pct, hint, _p(out), C.c_size_t(cols * 8)))
+    # Images, flows, blend planes and maps may be views whose rows are any distance apart (padded[:, :cols]): they are passed in place with
+    # their row step.  Planes that share one step argument of the C call are passed in place where their strides agree, else as copies.
+    # out= (where a method has it) takes destination arrays, whose row stride is kept; the default is a fresh packed array, as before.
+    def flow(self, i0, i1, max_pct, hint, out=None):
+        (a, b), step = _shared([i0, i1], np.uint8); rows, cols, _ = a.shape
+        (out,), fstep = _outs([out], (rows, cols, 2), np.float32)
+        self._chk(self.l.pf_flow(self.h, _p(a), _p(b), cols, rows, step, max_pct, hint, _p(out), fstep))
         return out
 
-    def flow_bidir(self, L, R, max_pct):
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
-        f0 = np.empty((rows, cols, 2), np.float32); f1 = np.empty((rows, cols, 2), np.float32)
-        self._chk(self.l.pf_flow_bidir(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), max_pct, _p(f0), _p(f1), C.c_size_t(cols * 8)))
+    def flow_bidir(self, L, R, max_pct, out=None):
+        """out: (flow_l2r, flow_r2l) destination arrays of one row stride"""
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
+        (f0, f1), fstep = _outs(out if out is not None else [None, None], (rows, cols, 2), np.float32)
+        self._chk(self.l.pf_flow_bidir(self.h, _p(a), _p(b), cols, rows, step, max_pct, _p(f0), _p(f1), fstep))
         return f0, f1
 
-    def blend(self, L, R, f_l2r, f_r2l, blend):
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
-        out = np.empty((rows, cols, 4), np.uint8)
-        self._chk(self.l.pf_blend(self.h, _p(a), _p(b), C.c_size_t(cols * 4), _p(_f32(f_l2r)), _p(_f32(f_r2l)), C.c_size_t(cols * 8), _p(_f32(blend)),
-                                  C.c_size_t(cols * 4), cols, rows, _p(out), C.c_size_t(cols * 4)))
+    def blend(self, L, R, f_l2r, f_r2l, blend, out=None):
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
+        (f0, f1), fstep = _shared([f_l2r, f_r2l], np.float32)
+        bl, bstep = _rows(blend, np.float32)
+        (out,), ostep = _outs([out], (rows, cols, 4), np.uint8)
+        self._chk(self.l.pf_blend(self.h, _p(a), _p(b), step, _p(f0), _p(f1), fstep, _p(bl), C.c_size_t(bstep), cols, rows, _p(out), ostep))
         return out
 
-    def novel_view(self, L, R, max_pct, blend, want_flows=True):
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
-        out = np.empty((rows, cols, 4), np.uint8)
-        f0 = np.empty((rows, cols, 2), np.float32) if want_flows else None
-        f1 = np.empty((rows, cols, 2), np.float32) if want_flows else None
-        self._chk(self.l.pf_novel_view(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), max_pct, _p(_f32(blend)), C.c_size_t(cols * 4), _p(out),
-                                       C.c_size_t(cols * 4), _p(f0) if want_flows else None, _p(f1) if want_flows else None, C.c_size_t(cols * 8)))
+    def novel_view(self, L, R, max_pct, blend, want_flows=True, out=None, flows_out=None):
+        """flows_out: (flow_l2r, flow_r2l) destination arrays of one row stride (implies want_flows)"""
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
+        bl, bstep = _rows(blend, np.float32)
+        (out,), ostep = _outs([out], (rows, cols, 4), np.uint8)
+        f0 = f1 = None; fstep = C.c_size_t(cols * 8)
+        if want_flows or flows_out is not None:
+            (f0, f1), fstep = _outs(flows_out if flows_out is not None else [None, None], (rows, cols, 2), np.float32)
+        self._chk(self.l.pf_novel_view(self.h, _p(a), _p(b), cols, rows, step, max_pct, _p(bl), C.c_size_t(bstep), _p(out), ostep,
+                                       _p(f0) if f0 is not None else None, _p(f1) if f1 is not None else None, fstep))
         return out, f0, f1
 
     def stitch_prepare(self, L, R):
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
-        mp = np.empty((rows, cols), np.uint8); ovl = np.empty_like(a); ovr = np.empty_like(a)
+        """(map, overlapped L, overlapped R, blend ramp, MergedDis); the overlapped images come at the inputs' row stride (the C call's rule)"""
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
+        mp = np.empty((rows, cols), np.uint8); ovl = _like(a.shape, np.uint8, step.value); ovr = _like(a.shape, np.uint8, step.value)
         bl = np.empty((rows, cols), np.float32); md = np.empty((rows, cols), np.float32)
-        self._chk(self.l.pf_stitch_prepare(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), _p(mp), C.c_size_t(cols), _p(ovl), _p(ovr), _p(bl),
+        self._chk(self.l.pf_stitch_prepare(self.h, _p(a), _p(b), cols, rows, step, _p(mp), C.c_size_t(cols), _p(ovl), _p(ovr), _p(bl),
                                            C.c_size_t(cols * 4), _p(md)))
         return mp, ovl, ovr, bl, md
 
     def stitch_match(self, L, R):
         """MatchImages + overlap masking only"""
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
-        mp = np.empty((rows, cols), np.uint8); ovl = np.empty_like(a); ovr = np.empty_like(a)
-        self._chk(self.l.pf_stitch_match(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), _p(mp), C.c_size_t(cols), _p(ovl), _p(ovr)))
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
+        mp = np.empty((rows, cols), np.uint8); ovl = _like(a.shape, np.uint8, step.value); ovr = _like(a.shape, np.uint8, step.value)
+        self._chk(self.l.pf_stitch_match(self.h, _p(a), _p(b), cols, rows, step, _p(mp), C.c_size_t(cols), _p(ovl), _p(ovr)))
         return mp, ovl, ovr
 
     def stitch_generate_blend(self, mp):
         """GenerateBlend from a given map (the reference reads its public Map member)"""
-        m = _u8(mp); rows, cols = m.shape
+        m, mstep = _rows(mp, np.uint8); rows, cols = m.shape
         bl = np.empty((rows, cols), np.float32); md = np.empty((rows, cols), np.float32)
-        self._chk(self.l.pf_stitch_generate_blend(self.h, _p(m), C.c_size_t(cols), cols, rows, _p(bl), C.c_size_t(cols * 4), _p(md)))
+        self._chk(self.l.pf_stitch_generate_blend(self.h, _p(m), C.c_size_t(mstep), cols, rows, _p(bl), C.c_size_t(cols * 4), _p(md)))
         return bl, md
 
     def stitch_raw_blend(self, L, R):
         """GenerateBlend before its smoothing (what countblend returns in the overlap) + MergedDis."""
-        a = _u8(L); b = _u8(R); rows, cols, _ = a.shape
+        (a, b), step = _shared([L, R], np.uint8); rows, cols, _ = a.shape
         bl = np.empty((rows, cols), np.float32); md = np.empty((rows, cols), np.float32)
-        self._chk(self.l.pf_stitch_raw_blend(self.h, _p(a), _p(b), cols, rows, C.c_size_t(cols * 4), _p(bl), C.c_size_t(cols * 4), _p(md)))
+        self._chk(self.l.pf_stitch_raw_blend(self.h, _p(a), _p(b), cols, rows, step, _p(bl), C.c_size_t(cols * 4), _p(md)))
         return bl, md
 
-    def stitch_gather(self, L, R, merged, mp):
-        a = _u8(L); b = _u8(R); g = _u8(merged); m = _u8(mp); rows, cols, _ = a.shape
-        out = np.empty((rows, cols, 4), np.uint8)
-        self._chk(self.l.pf_stitch_gather(self.h, _p(a), _p(b), _p(g), C.c_size_t(cols * 4), _p(m), C.c_size_t(cols), cols, rows,
-                                          _p(out), C.c_size_t(cols * 4)))
+    def stitch_gather(self, L, R, merged, mp, out=None):
+        (a, b, g), step = _shared([L, R, merged], np.uint8); rows, cols, _ = a.shape
+        m, mstep = _rows(mp, np.uint8)
+        (out,), ostep = _outs([out], (rows, cols, 4), np.uint8)
+        self._chk(self.l.pf_stitch_gather(self.h, _p(a), _p(b), _p(g), step, _p(m), C.c_size_t(mstep), cols, rows, _p(out), ostep))
         return out
 
     def stitch_prefetch(self, next_L):
-        """announce the NEXT stitch_step's left image (must be a contiguous uint8 array kept alive and unchanged until then)"""
+        """announce the NEXT stitch_step's left image (a uint8 array with packed pixels, rows any distance apart, kept alive and unchanged
+        until then)"""
         if next_L is None:
             self._chk(self.l.pf_stitch_prefetch(self.h, None, 0, 0, C.c_size_t(0)))
             return
-        assert next_L.dtype == np.uint8 and next_L.flags["C_CONTIGUOUS"]
+        a, step = _rows(next_L, np.uint8)
+        assert a is next_L, "the announced image is read in place: a uint8 array whose pixels are packed"
         rows, cols, _ = next_L.shape
-        self._chk(self.l.pf_stitch_prefetch(self.h, _p(next_L), cols, rows, C.c_size_t(cols * 4)))
+        self._chk(self.l.pf_stitch_prefetch(self.h, _p(next_L), cols, rows, C.c_size_t(step)))
 
     def stitch_plan(self, L, R):
         """The plan of a step whose alpha masks are L's and R's (only alpha matters); R=None takes the R mask from the composite the
         last stitch_step left in HBM."""
-        a = _u8(L); rows, cols, _ = a.shape
-        r = None if R is None else _u8(R)
+        ims, step = _shared([L] if R is None else [L, R], np.uint8); rows, cols, _ = ims[0].shape
         h = C.c_void_p(None)
-        self._chk(self.l.pf_stitch_plan_create(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), C.byref(h)))
+        self._chk(self.l.pf_stitch_plan_create(self.h, _p(ims[0]), None if R is None else _p(ims[1]), cols, rows, step, C.byref(h)))
         return StitchPlan(self, h.value)
 
     def stitch_plan_dev(self, d_l, d_r, cols, rows):
@@ -577,12 +636,11 @@ class Context:
 
     def rig_plan(self, top, Ls):
         """The plans of the whole chain top, Ls[0], Ls[1], ... (only alphas matter): RigPlan"""
-        t = _u8(top); rows, cols, _ = t.shape
-        ls = [_u8(a) for a in Ls]
-        assert all(a.shape == (rows, cols, 4) for a in ls)
-        arr = (C.c_void_p * max(len(ls), 1))(*[a.ctypes.data for a in ls])
+        ims, step = _shared([top] + list(Ls), np.uint8); rows, cols, _ = ims[0].shape
+        assert all(a.shape == (rows, cols, 4) for a in ims)
+        arr = (C.c_void_p * max(len(ims) - 1, 1))(*[a.ctypes.data for a in ims[1:]])
         h = C.c_void_p(None)
-        self._chk(self.l.pf_rig_plan_create(self.h, len(ls), _p(t), arr, cols, rows, C.c_size_t(cols * 4), C.byref(h)))
+        self._chk(self.l.pf_rig_plan_create(self.h, len(ims) - 1, _p(ims[0]), arr, cols, rows, step, C.byref(h)))
         return RigPlan(self, h.value)
 
     def rig_plan_dev(self, d_top, d_ls, cols, rows):
@@ -593,20 +651,23 @@ class Context:
     def rig_stitch_batch(self, rig, tops, Ls, max_pct, in_flight=8, want=None, out=None):
         """The whole chain of len(tops) frames of the rig: Ls[k] = frame k's left images in chain order.  Returns outs[k][i], the
         composite after step i + 1 of frame k; want(k, i) -> bool selects what is downloaded (default all; None where not), out[k][i]
-        are optional preallocated (rows, cols, 4) uint8 arrays (None entries skip).  Raises as a whole if any frame is off the rig."""
+        are optional preallocated (rows, cols, 4) uint8 arrays of one row stride (None entries skip).  Raises as a whole if any frame is off the rig."""
         n, ns = len(tops), rig.n_steps
-        ts = [_u8(a) for a in tops]
-        ls = [[_u8(a) for a in row] for row in Ls]
         rows, cols = rig.rows, rig.cols
-        assert all(a.shape == (rows, cols, 4) for a in ts) and len(ls) == n and all(len(r) == ns and all(a.shape == (rows, cols, 4) for a in r) for r in ls)
+        assert len(Ls) == n and all(len(r) == ns for r in Ls)
+        ims, step = _shared(list(tops) + [a for row in Ls for a in row], np.uint8)
+        assert all(a.shape == (rows, cols, 4) for a in ims)
+        ts, ls = ims[:n], ims[n:]
         if out is not None:
             outs = [list(r) for r in out]
-            assert all(o is None or (o.dtype == np.uint8 and o.shape == (rows, cols, 4) and o.flags["C_CONTIGUOUS"]) for r in outs for o in r)
+            given, ostep = _outs([o for r in outs for o in r if o is not None], (rows, cols, 4), np.uint8)
+            if not given:
+                ostep = C.c_size_t(cols * 4)
         else:
             outs = [[np.empty((rows, cols, 4), np.uint8) if want is None or want(k, i) else None for i in range(ns)] for k in range(n)]
+            ostep = C.c_size_t(cols * 4)
         ptrs = lambda v: (C.c_void_p * max(len(v), 1))(*[a.ctypes.data if a is not None else None for a in v])
-        self._chk(self.l.pf_rig_stitch_batch(self.h, rig.h, n, ptrs(ts), ptrs([a for r in ls for a in r]), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                             ptrs([o for r in outs for o in r]), C.c_size_t(cols * 4), in_flight))
+        self._chk(self.l.pf_rig_stitch_batch(self.h, rig.h, n, ptrs(ts), ptrs(ls), cols, rows, step, max_pct, ptrs([o for r in outs for o in r]), ostep, in_flight))
         return outs
 
     def rig_set_upload_overlap(self, on):
@@ -620,46 +681,46 @@ class Context:
 
     def stitch_step(self, L, R, max_pct, want_out=True, out=None, plan=None):
         """One iteration of main.cpp's loop on the device; R=None chains on the previous result kept in HBM.
-        out: optional preallocated (rows, cols, 4) uint8 array for the composite (a caller that reuses its buffer, like
-        the reference's Mat, does not pay a fresh 144 MB allocation + first-touch page faults per call).
+        out: optional preallocated (rows, cols, 4) uint8 array for the composite, rows any distance apart (a caller that reuses its buffer,
+        like the reference's Mat, does not pay a fresh 144 MB allocation + first-touch page faults per call).
         plan: a StitchPlan of these masks -- the same bytes without recomputing the map and the ramp; raises if the masks differ."""
-        a = _u8(L); rows, cols, _ = a.shape
-        r = None if R is None else _u8(R)     # named, so that a converted copy outlives the call
-        if out is not None:
-            assert out.dtype == np.uint8 and out.shape == (rows, cols, 4) and out.flags["C_CONTIGUOUS"]
-        elif want_out:
-            out = np.empty((rows, cols, 4), np.uint8)
-        if plan is not None:
-            self._chk(self.l.pf_stitch_step_planned(self.h, plan.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                                    None if out is None else _p(out), C.c_size_t(cols * 4)))
-        else:
-            self._chk(self.l.pf_stitch_step(self.h, _p(a), None if r is None else _p(r), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                            None if out is None else _p(out), C.c_size_t(cols * 4)))
+        ims, step = _shared([L] if R is None else [L, R], np.uint8); rows, cols, _ = ims[0].shape   # named, so that a converted copy outlives the call
+        ostep = C.c_size_t(cols * 4)
+        if out is not None or want_out:
+            (out,), ostep = _outs([out], (rows, cols, 4), np.uint8)
+        fn = self.l.pf_stitch_step if plan is None else self.l.pf_stitch_step_planned
+        self._chk(fn(*([self.h] + ([] if plan is None else [plan.h]) + [_p(ims[0]), None if R is None else _p(ims[1]), cols, rows, step, max_pct,
+                                                                       None if out is None else _p(out), ostep])))
         self._step_shape = (rows, cols)
         return out
 
     def stitch_step_batch(self, Ls, Rs, max_pct, in_flight=8, want_out=True, out=None, plan=None):
         """n independent stitch steps of one size (frame k = one stitch_step of its own chain).  Rs=None, or a None entry, chains
         frame k on its composite from the previous stitch_step_batch call.  Returns a list of (rows, cols, 4) arrays, or of None.
-        out: optional list of preallocated (rows, cols, 4) uint8 arrays for the composites (as stitch_step's `out`)."""
+        out: optional list of preallocated (rows, cols, 4) uint8 arrays of one row stride for the composites (as stitch_step's `out`)."""
         n = len(Ls)
-        ls = [_u8(a) for a in Ls]
+        given = [] if Rs is None else [r for r in Rs if r is not None]
+        assert Rs is None or len(Rs) == n
+        ims, step = _shared(list(Ls) + given, np.uint8)
+        ls = ims[:n]
         rows, cols = ls[0].shape[:2] if n else (0, 0)
-        assert all(a.shape == (rows, cols, 4) for a in ls)
-        rs = None if Rs is None else [None if r is None else _u8(r) for r in Rs]
-        assert rs is None or (len(rs) == n and all(r is None or r.shape == (rows, cols, 4) for r in rs))
+        assert all(a.shape == (rows, cols, 4) for a in ims)
+        it = iter(ims[n:])
+        rs = None if Rs is None else [None if r is None else next(it) for r in Rs]
+        ostep = C.c_size_t(cols * 4)
         if out is not None:
-            assert len(out) == n and all(o.dtype == np.uint8 and o.shape == (rows, cols, 4) and o.flags["C_CONTIGUOUS"] for o in out)
-            outs, want_out = list(out), True
+            assert len(out) == n
+            outs, ostep = _outs(list(out), (rows, cols, 4), np.uint8)
+            want_out = True
         else:
             outs = [np.empty((rows, cols, 4), np.uint8) for _ in range(n)] if want_out else [None] * n
         arr = lambda v: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a is not None else None for a in v])
         if plan is not None:   # one plan for all frames; the call raises as a whole if any frame's masks differ from it
-            self._chk(self.l.pf_stitch_step_batch_planned(self.h, plan.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4),
-                                                          max_pct, arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
+            self._chk(self.l.pf_stitch_step_batch_planned(self.h, plan.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, step,
+                                                          max_pct, arr(outs) if want_out else None, ostep, in_flight))
         else:
-            self._chk(self.l.pf_stitch_step_batch(self.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, C.c_size_t(cols * 4), max_pct,
-                                                  arr(outs) if want_out else None, C.c_size_t(cols * 4), in_flight))
+            self._chk(self.l.pf_stitch_step_batch(self.h, n, arr(ls), None if rs is None else arr(rs), cols, rows, step, max_pct,
+                                                  arr(outs) if want_out else None, ostep, in_flight))
         return outs
 
     def stitch_step_batch_dev(self, d_l, d_r, cols, rows, max_pct, d_out, in_flight=8, plan=None):
@@ -671,44 +732,43 @@ class Context:
             self._chk(self.l.pf_stitch_step_batch_dev(self.h, n, _dptrs(d_l), _dptrs(d_r, n), cols, rows, max_pct, _dptrs(d_out, n), in_flight))
 
     # ---- flow visualisation (CPU/OpticalFlow.cpp:147-204, the panel of CPU/main.cpp:20-45) ----
-    def vis_grey_disparity(self, flow):
+    def vis_grey_disparity(self, flow, out=None):
         """visualizeFlowAsGreyDisparity: (rows, cols) uint8"""
-        f = _f32(flow); rows, cols, _ = f.shape
-        out = np.empty((rows, cols), np.uint8)
-        self._chk(self.l.pf_vis_grey_disparity(self.h, _p(f), C.c_size_t(cols * 8), cols, rows, _p(out), C.c_size_t(cols)))
+        f, fstep = _rows(flow, np.float32); rows, cols, _ = f.shape
+        (out,), ostep = _outs([out], (rows, cols), np.uint8)
+        self._chk(self.l.pf_vis_grey_disparity(self.h, _p(f), C.c_size_t(fstep), cols, rows, _p(out), ostep))
         return out
 
-    def vis_color_wheel(self, flow):
+    def vis_color_wheel(self, flow, out=None):
         """visualizeFlowColorWheel: (rows, cols, 3) uint8 BGR"""
-        f = _f32(flow); rows, cols, _ = f.shape
-        out = np.empty((rows, cols, 3), np.uint8)
-        self._chk(self.l.pf_vis_color_wheel(self.h, _p(f), C.c_size_t(cols * 8), cols, rows, _p(out), C.c_size_t(cols * 3)))
+        f, fstep = _rows(flow, np.float32); rows, cols, _ = f.shape
+        (out,), ostep = _outs([out], (rows, cols, 3), np.uint8)
+        self._chk(self.l.pf_vis_color_wheel(self.h, _p(f), C.c_size_t(fstep), cols, rows, _p(out), ostep))
         return out
 
-    def vis_vector_field(self, flow, image):
+    def vis_vector_field(self, flow, image, out=None):
         """visualizeFlowAsVectorField: (rows, cols, 4) uint8 BGRA, the image with the flow's arrows"""
-        f = _f32(flow); im = _u8(image); rows, cols, _ = f.shape
-        out = np.empty((rows, cols, 4), np.uint8)
-        self._chk(self.l.pf_vis_vector_field(self.h, _p(f), C.c_size_t(cols * 8), _p(im), C.c_size_t(cols * 4), cols, rows, _p(out),
-                                             C.c_size_t(cols * 4)))
+        f, fstep = _rows(flow, np.float32); im, istep = _rows(image, np.uint8); rows, cols, _ = f.shape
+        (out,), ostep = _outs([out], (rows, cols, 4), np.uint8)
+        self._chk(self.l.pf_vis_vector_field(self.h, _p(f), C.c_size_t(fstep), _p(im), C.c_size_t(istep), cols, rows, _p(out), ostep))
         return out
 
-    def vis_panel(self, flow, image):
+    def vis_panel(self, flow, image, out=None):
         """buildvisualizations' strip of one direction: (rows, 3 * cols, 4) uint8 BGRA"""
-        f = _f32(flow); im = _u8(image); rows, cols, _ = f.shape
-        out = np.empty((rows, 3 * cols, 4), np.uint8)
-        self._chk(self.l.pf_vis_panel(self.h, _p(f), C.c_size_t(cols * 8), _p(im), C.c_size_t(cols * 4), cols, rows, _p(out), C.c_size_t(cols * 12)))
+        f, fstep = _rows(flow, np.float32); im, istep = _rows(image, np.uint8); rows, cols, _ = f.shape
+        (out,), ostep = _outs([out], (rows, 3 * cols, 4), np.uint8)
+        self._chk(self.l.pf_vis_panel(self.h, _p(f), C.c_size_t(fstep), _p(im), C.c_size_t(istep), cols, rows, _p(out), ostep))
         return out
 
     def vis_panel_dev(self, d_flow, d_image, cols, rows, d_out):
         self._chk(self.l.pf_vis_panel_dev(self.h, C.c_void_p(d_flow), C.c_void_p(d_image), cols, rows, C.c_void_p(d_out)))
 
-    def stitch_visualize(self, shape=None):
+    def stitch_visualize(self, shape=None, out=None):
         """the (L->R, R->L) panels of the last stitch_step from what it left in HBM; shape = (rows, cols) of that step (default: the last
-        stitch_step made through this object)"""
+        stitch_step made through this object); out: the two destination arrays, of one row stride"""
         rows, cols = shape if shape is not None else self._step_shape
-        a = np.empty((rows, 3 * cols, 4), np.uint8); b = np.empty_like(a)
-        self._chk(self.l.pf_stitch_visualize(self.h, _p(a), _p(b), C.c_size_t(cols * 12)))
+        (a, b), step = _outs(out if out is not None else [None, None], (rows, 3 * cols, 4), np.uint8)
+        self._chk(self.l.pf_stitch_visualize(self.h, _p(a), _p(b), step))
         return a, b
 
     # ---- PNG files made on the device (pf_png_*): every method returns the file as bytes ----
