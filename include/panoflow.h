@@ -117,9 +117,15 @@ int pf_max_percentage_by_name(const char* flow_alg_name);
 /* The constructor arguments of the reference's PixFlow<P> (CPU/PixFlow.hpp:46-68).  Its factory only ever passes the values
  * pf_solver_params_init() fills in (:459-497, both presets), but the class accepts any: so does this library (round 6).  The
  * parameters belong to the context and apply to every later solve on it (pf_flow*, pf_novel_view*, pf_stitch_step, the lanes of
- * pf_novel_view_batch_dev).  Results are bit-identical to the reference's arithmetic for every accepted set.
+ * pf_novel_view_batch_dev).  Results are bit-identical to the reference's arithmetic for every accepted set.  Coefficients large
+ * enough to overflow an energy are accepted (the reference computes with them, too); from there on "bit-identical" means: every
+ * element of a flow is of the reference's class -- finite, +inf, -inf or NaN -- and a finite element has the reference's bits.  A
+ * NaN's sign and payload are not part of the promise (IEEE 754 leaves open which operand's an operation hands on).
  *   pyr_scale_factor  in [0.25, 0.98]: level sizes int(w * s + 0.5f) while both > 24 (:137-151), inter-level flow scale 1.0f / s (:124);
- *                     at most 96 levels (PF_ERR_ARG from the solve otherwise);
+ *                     at most 96 levels (PF_ERR_ARG from the solve otherwise, naming the count, before the solve sizes or launches anything).  0.98f itself is
+ *                     accepted here and refused by every solve whose half-resolution sides exceed 25: int(25 * 0.98f + 0.5f) is 25, so
+ *                     the reference's pyramid never ends and runs to its limit of 1000 levels (and solves each).  The largest usable
+ *                     value is the float below, nextafterf(0.98f, 0);
  *   smoothness_coef, vertical_/horizontal_regularization_coef: finite and >= 0 (errorFunction :450-453; a negative coefficient could
  *                     make an energy negative, which the sweep's "keep" sentinel excludes);
  *   gradient_step_size: finite and >= 0 (:321,334).  A power of two in [2^-16, 2^16] (the presets' 0.5 is one) runs at full speed; any

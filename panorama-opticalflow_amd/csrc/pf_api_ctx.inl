@@ -193,12 +193,14 @@ struct Geometry {
   size_t P;                 // total level pixels (padded to 64 per level)
   size_t Pexact;
 };
-// the levels below level 0 (g.w0 x g.h0), their offsets inside a pyramid plane and the totals
+// the levels below level 0 (g.w0 x g.h0), their offsets inside a pyramid plane and the totals.  The reference's loop as it stands: a scale
+// that stops shrinking a side above 24 (0.98f: int(25 * 0.98f + 0.5f) is 25) repeats that level up to kPyrMaxLevels, and the reference
+// solves every one of them -- the list says so, and the solve refuses it (more than kLevelTableMax levels), rather than ending the
+// pyramid where the reference does not.
 void fill_levels(Geometry& g, float pyrScale) {
   g.ws = {g.w0}; g.hs = {g.h0};
   while ((int)g.ws.size() < kPyrMaxLevels) {
     const int nw = int(g.ws.back() * pyrScale + 0.5f), nh = int(g.hs.back() * pyrScale + 0.5f);
-    if (nw >= g.ws.back() && nh >= g.hs.back()) break;   // (a scale that does not shrink the image any more: pf_set_solver_params keeps it below 1, this keeps the loop finite regardless)
     if (nh <= kPyrMinImageSize || nw <= kPyrMinImageSize) break;
     g.ws.push_back(nw); g.hs.push_back(nh);
   }
@@ -233,6 +235,15 @@ int check_dims(pf_ctx* c, int cols, int rows, int pad) {
   const int w0 = int((cols + 2 * pad) * kDownscaleFactor), h0 = int(rows * kDownscaleFactor);
   if (w0 < 2 || h0 < 2) return fail(c, PF_ERR_ARG, "image %dx%d too small for the half-res solver", cols, rows);
   if ((double)cols * rows > 2.0e9) return fail(c, PF_ERR_ARG, "image too large");
+  return 0;
+}
+
+// A run-time pyramid scale may ask for more levels than one launch's level table holds (the 0.9 pyramid only does so beyond ~1.4 Gpix, where
+// the solve goes level by level): refused before anything is sized from the level count.  0.98f ends here for every image whose
+// half-resolution sides exceed 25: a side of 25 does not shrink any more and the reference's list runs to its 1000-level limit.
+int check_levels(pf_ctx* c, const Geometry& g) {
+  if (g.n > kLevelTableMax && c->sp.pyr_scale_factor != kPyrScaleFactor)
+    return fail(c, PF_ERR_ARG, "pyrScaleFactor %.9g gives %d pyramid levels (at most %d)", (double)c->sp.pyr_scale_factor, g.n, kLevelTableMax);
   return 0;
 }
 

@@ -159,6 +159,7 @@ int pf_novel_view_batch_dev(pf_ctx* c, int n_pairs, const uint8_t* const* d_l, c
   if (n_pairs > 0) {
     // the pairs of a batch share launches and the lanes run side by side: every plane of the call is checked against every other, before any work
     if (int e = check_dims(c, cols, rows, cols / 20)) return e;
+    if (int e = check_levels(c, make_geometry(cols, rows, cols / 20, c->sp.pyr_scale_factor))) return e;   // ... and before any lane is created
     const size_t n = size_t(cols) * rows;
     std::vector<DevPlane> pl;
     for (int p = 0; p < n_pairs; ++p) {

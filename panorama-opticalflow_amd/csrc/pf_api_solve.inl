@@ -225,7 +225,7 @@ int solve_n(pf_ctx* c, int nb, const uint8_t* const* d_img0, const uint8_t* cons
   const Geometry g = make_geometry(cols, rows, pad, c->sp.pyr_scale_factor);
   SolveBufs sb;
   Batch bt;
-  if (g.n > kLevelTableMax && c->sp.pyr_scale_factor != kPyrScaleFactor) return fail(c, PF_ERR_ARG, "pyrScaleFactor %g gives %d pyramid levels (at most %d)", (double)c->sp.pyr_scale_factor, g.n, kLevelTableMax);
+  if (int e = check_levels(c, g)) return e;   // before alloc_solve: the hand-off offsets and control words are sized from g.n
   if (nb == 1) { if (int e = alloc_solve(c, g, ndirs, sb)) return e; }
   else {
     if (g.n > kLevelTableMax || g.P >= (size_t(1) << 31)) return fail(c, PF_ERR_ARG, "image too large for a batched solve");
