@@ -25,12 +25,13 @@
 using namespace pf;
 
 
-// One translation unit in fourteen parts (the anonymous namespace and the extern "C" block span several of them):
+// One translation unit in fifteen parts (the anonymous namespace and the extern "C" block span several of them):
 #include "pf_api_ctx.inl"      // pf_ctx, errors / warnings, arena, profiling events, geometry, checks
 #include "pf_api_solve.inl"    // run_level, solve buffers, solve / solve_n (stream orchestration)
 #include "pf_api_life.inl"     // finish / CallGuard, pf_create* / pf_destroy, memory helpers            (opens extern "C")
 #include "pf_api_entry.inl"    // pf_flow* / pf_blend* / pf_novel_view* incl. the throughput mode
-#include "pf_api_stitch.inl"   // pf_stitch_*
+#include "pf_api_stitch.inl"   // pf_stitch_* but the plans: lone calls, the chain step and its prefetch, the batched step
+#include "pf_api_plan.inl"     // pf_stitch_plan_*, pf_rig_plan_*, pf_rig_stitch* (stitch plans, rig plans, the rig chain)
 #include "pf_api_image.inl"    // shared by the file-and-image parts below: resident results, device-image checks, host-image staging, resident tables
 #include "pf_api_stage.inl"    // pf_stage_*, pf_profile_*, pf_level_pixels / pf_algorithmic_bytes
 #include "pf_api_vis.inl"      // pf_vis_*, pf_stitch_visualize (flow visualisers)

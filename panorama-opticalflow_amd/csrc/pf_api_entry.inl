@@ -80,6 +80,8 @@ void batch_split(const pf_ctx* c, int in_flight, int& lanes, int& per_batch) {
   if (per_batch > in_flight) per_batch = in_flight;
   lanes = (in_flight + per_batch - 1) / per_batch;
 }
+// items in flight: 1 .. 2 * kMaxBatch and no more than there are (an empty call: 1)
+int clamp_in_flight(int in_flight, int n_items) { return std::max(1, std::min({in_flight, 2 * kMaxBatch, n_items})); }
 // one batch: pairs [first, first + count) of the arrays through one set of launches on `lane`
 int novel_view_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
                      const float* const* d_blend, uint8_t* const* d_out, float* const* d_l2r, float* const* d_r2l) {
@@ -107,9 +109,7 @@ int novel_view_group(pf_ctx* lane, int first, int count, const uint8_t* const* d
 // pf_stitch_step_batch*.  queues_per_lane: the HIP streams a lane drives (check_hw_queues: that many per lane + 2).
 extern "C++" template <class Group>
 int run_lanes(pf_ctx* c, int n_items, int in_flight, int cols, int rows, int queues_per_lane, const char* what, Group group) {
-  if (in_flight < 1) in_flight = 1;
-  if (in_flight > 2 * kMaxBatch) in_flight = 2 * kMaxBatch;
-  if (in_flight > n_items) in_flight = n_items > 0 ? n_items : 1;
+  in_flight = clamp_in_flight(in_flight, n_items);
   int nlanes = 1, per_batch = 1;
   batch_split(c, in_flight, nlanes, per_batch);
   check_hw_queues(c, queues_per_lane * nlanes + 2, what);
@@ -188,11 +188,11 @@ int pf_flow(pf_ctx* c, const uint8_t* i0, const uint8_t* i1, int cols, int rows,
   uint8_t* d0 = (uint8_t*)ensure(c, "h_img0", ib); uint8_t* d1 = (uint8_t*)ensure(c, "h_img1", ib);
   float* df = (float*)ensure(c, "h_flow0", size_t(cols) * rows * 8);
   if (!d0 || !d1 || !df) return PF_ERR_NOMEM;
-  if (int e = up2d(c, d0, size_t(cols) * 4, i0, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, d1, size_t(cols) * 4, i1, step, size_t(cols) * 4, rows)) return e;
+  if (int e = up_plane(c, d0, i0, step, cols, rows, 4)) return e;
+  if (int e = up_plane(c, d1, i1, step, cols, rows, 4)) return e;
   const int hints[2] = {hint, hint}; float* outs[2] = {df, nullptr};
   if (int e = solve(c, d0, d1, cols, rows, 0, max_pct, 1, hints, outs)) return e;
-  if (int e = down2d(c, flow, fstep, df, size_t(cols) * 8, size_t(cols) * 8, rows)) return e;
+  if (int e = down_plane(c, flow, fstep, df, cols, rows, 8)) return e;
   if (int e = finish(c)) return e;
   return check_sweeps(c);
 }
@@ -211,20 +211,20 @@ int pf_novel_view(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int r
   uint8_t* dl = (uint8_t*)ensure(c, "h_img0", ib); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", ib);
   float* d0 = (float*)ensure(c, "h_flow0", fb); float* d1 = (float*)ensure(c, "h_flow1", fb);
   if (!dl || !dr || !d0 || !d1) return PF_ERR_NOMEM;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
+  if (int e = up_plane(c, dl, l, step, cols, rows, 4)) return e;
+  if (int e = up_plane(c, dr, r, step, cols, rows, 4)) return e;
   const int hints[2] = {PF_HINT_LEFT, PF_HINT_RIGHT}; float* outs[2] = {d0, d1};
   const int pad = cols / 20;
   if (int e = solve(c, dl, dr, cols, rows, pad, max_pct, 2, hints, outs)) return e;
   if (out) {
     float* db = (float*)ensure(c, "h_blend", size_t(cols) * rows * 4); uint8_t* dout = (uint8_t*)ensure(c, "h_out", ib);
     if (!db || !dout) return PF_ERR_NOMEM;
-    if (int e = up2d(c, db, size_t(cols) * 4, blend, bstep, size_t(cols) * 4, rows)) return e;
+    if (int e = up_plane(c, db, blend, bstep, cols, rows, 4)) return e;
     { PROF(c, c->s_main, "blend"); launch_blend(c->s_main, dl, dr, d0, d1, db, cols, rows, dout); }
-    if (int e = down2d(c, out, ostep, dout, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+    if (int e = down_plane(c, out, ostep, dout, cols, rows, 4)) return e;
   }
-  if (f_l2r) if (int e = down2d(c, f_l2r, fstep, d0, size_t(cols) * 8, size_t(cols) * 8, rows)) return e;
-  if (f_r2l) if (int e = down2d(c, f_r2l, fstep, d1, size_t(cols) * 8, size_t(cols) * 8, rows)) return e;
+  if (f_l2r) if (int e = down_plane(c, f_l2r, fstep, d0, cols, rows, 8)) return e;
+  if (f_r2l) if (int e = down_plane(c, f_r2l, fstep, d1, cols, rows, 8)) return e;
   if (int e = finish(c)) return e;
   return check_sweeps(c);
 }
@@ -245,13 +245,13 @@ int pf_blend(pf_ctx* c, const uint8_t* l, const uint8_t* r, size_t step, const f
   uint8_t* dl = (uint8_t*)ensure(c, "h_img0", ib); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", ib); uint8_t* dout = (uint8_t*)ensure(c, "h_out", ib);
   float* d0 = (float*)ensure(c, "h_flow0", fb); float* d1 = (float*)ensure(c, "h_flow1", fb); float* db = (float*)ensure(c, "h_blend", ib);
   if (!dl || !dr || !dout || !d0 || !d1 || !db) return PF_ERR_NOMEM;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, d0, size_t(cols) * 8, f_l2r, fstep, size_t(cols) * 8, rows)) return e;
-  if (int e = up2d(c, d1, size_t(cols) * 8, f_r2l, fstep, size_t(cols) * 8, rows)) return e;
-  if (int e = up2d(c, db, size_t(cols) * 4, blend, bstep, size_t(cols) * 4, rows)) return e;
+  if (int e = up_plane(c, dl, l, step, cols, rows, 4)) return e;
+  if (int e = up_plane(c, dr, r, step, cols, rows, 4)) return e;
+  if (int e = up_plane(c, d0, f_l2r, fstep, cols, rows, 8)) return e;
+  if (int e = up_plane(c, d1, f_r2l, fstep, cols, rows, 8)) return e;
+  if (int e = up_plane(c, db, blend, bstep, cols, rows, 4)) return e;
   { PROF(c, c->s_main, "blend"); launch_blend(c->s_main, dl, dr, d0, d1, db, cols, rows, dout); }
-  if (int e = down2d(c, out, ostep, dout, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (int e = down_plane(c, out, ostep, dout, cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }

@@ -45,12 +45,9 @@ int upload_bgra(pf_ctx* c, const char* slot, const uint8_t* host, size_t step, i
   void* d = ensure(c, slot, size_t(cols) * rows * 4);
   if (!d) return PF_ERR_NOMEM;
   *d_out = (const uint8_t*)d;
-  return up2d(c, d, size_t(cols) * 4, host, step, size_t(cols) * 4, rows);
+  return up_plane(c, d, host, step, cols, rows, 4);
 }
-// ... and a packed device image back into one (enqueued on s_main; the caller drains)
-int download_bgra(pf_ctx* c, uint8_t* host, size_t step, const uint8_t* dev, int cols, int rows) {
-  return down2d(c, host, step, dev, size_t(cols) * 4, size_t(cols) * 4, rows);
-}
+// (... and a packed device image back into one: down_plane, pf_api_life.inl; the caller drains)
 
 // A table the host makes, resident in the arena slot `slot`: fill(host) writes its `bytes` bytes, and only when the slot does not hold
 // them already.  It does not when the slot moved, when it grew (a slot that grew is a fresh allocation, wherever it landed) or when it

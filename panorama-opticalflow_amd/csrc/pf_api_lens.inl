@@ -115,7 +115,7 @@ int pf_lens_remap(pf_ctx* c, const uint8_t* photo_bgra, size_t photo_step, int p
   uint8_t* d_dst = (uint8_t*)ensure(c, "ln_dst", size_t(cols) * rows * 4);
   if (!d_dst) return PF_ERR_NOMEM;
   if (int e = lens_many(c, 1, &d_src, &d_dst, g, l.data(), params)) return e;
-  if (int e = download_bgra(c, canvas_bgra, canvas_step, d_dst, cols, rows)) return e;
+  if (int e = down_plane(c, canvas_bgra, canvas_step, d_dst, cols, rows, 4)) return e;
   return finish(c);
 }
 

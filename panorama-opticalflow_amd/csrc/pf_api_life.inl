@@ -40,17 +40,43 @@ int use(pf_ctx* c) {
   return 0;
 }
 
-// packed rows on both sides (the usual case): one linear copy -- the DMA engines at the link rate when the host side is pinned
-int up2d(pf_ctx* c, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, int rows) {
-  if (dpitch == width_bytes && spitch == width_bytes) HIPCHK(c, hipMemcpyAsync(dst, src, width_bytes * size_t(rows), hipMemcpyHostToDevice, c->s_main));
-  else HIPCHK(c, hipMemcpy2DAsync(dst, dpitch, src, spitch, width_bytes, rows, hipMemcpyHostToDevice, c->s_main));
+// A caller's plane of cols x rows elements of `elem` bytes: rows `step` apart on the host, packed on the device.  Packed rows on the host
+// too (the usual case): one linear copy -- the DMA engines at the link rate when the host side is pinned.  up_plane_on: on any stream
+// (the prefetches copy on s_copy); up_plane / down_plane: on s_main.
+hipError_t up_plane_on(hipStream_t st, void* dst, const void* host, size_t step, int cols, int rows, size_t elem) {
+  const size_t rb = size_t(cols) * elem;
+  return step == rb ? hipMemcpyAsync(dst, host, rb * size_t(rows), hipMemcpyHostToDevice, st) : hipMemcpy2DAsync(dst, rb, host, step, rb, rows, hipMemcpyHostToDevice, st);
+}
+int up_plane(pf_ctx* c, void* dst, const void* host, size_t step, int cols, int rows, size_t elem) {
+  HIPCHK(c, up_plane_on(c->s_main, dst, host, step, cols, rows, elem));
   return 0;
 }
-int down2d(pf_ctx* c, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width_bytes, int rows) {
-  if (dpitch == width_bytes && spitch == width_bytes) HIPCHK(c, hipMemcpyAsync(dst, src, width_bytes * size_t(rows), hipMemcpyDeviceToHost, c->s_main));
-  else HIPCHK(c, hipMemcpy2DAsync(dst, dpitch, src, spitch, width_bytes, rows, hipMemcpyDeviceToHost, c->s_main));
+int down_plane(pf_ctx* c, void* host, size_t step, const void* dev, int cols, int rows, size_t elem) {
+  const size_t rb = size_t(cols) * elem;
+  HIPCHK(c, step == rb ? hipMemcpyAsync(host, dev, rb * size_t(rows), hipMemcpyDeviceToHost, c->s_main)
+                       : hipMemcpy2DAsync(host, step, dev, rb, rb, rows, hipMemcpyDeviceToHost, c->s_main));
   return 0;
 }
+
+// A stitch plan's memory has one owner.  plan_new: a plan with both device planes (5 B/px), or null with nothing left allocated -- the
+// caller fails with its own words; plan_free: the only place that frees one (every call is synchronous on return: nothing in flight reads
+// its planes).  A handle is valid if the context lists it, and is never dereferenced before that: a destroyed plan, or another context's,
+// is refused by address.
+void plan_free(pf_stitch_plan* pl) { if (pl) { hipFree(pl->map); hipFree(pl->ramp); delete pl; } }
+pf_stitch_plan* plan_new(int cols, int rows, bool rig_owned) {
+  pf_stitch_plan* pl = new pf_stitch_plan();
+  pl->cols = cols; pl->rows = rows; pl->rig_owned = rig_owned;
+  const size_t n = size_t(cols) * rows;
+  if (hipMalloc((void**)&pl->map, (n + 255) & ~size_t(255)) == hipSuccess && hipMalloc((void**)&pl->ramp, (n * 4 + 255) & ~size_t(255)) == hipSuccess) return pl;
+  plan_free(pl);
+  return nullptr;
+}
+bool plan_is_live(const pf_ctx* c, const pf_stitch_plan* plan) { return std::find(c->plans.begin(), c->plans.end(), plan) != c->plans.end(); }
+// frees what a creation that fails leaves behind: a lone plan, or a rig with the steps it has so far (a creation that succeeds nulls both)
+struct PlanDrop {
+  pf_stitch_plan* pl = nullptr; pf_rig_plan* rig = nullptr;
+  ~PlanDrop() { plan_free(pl); if (rig) for (pf_stitch_plan* s : rig->steps) plan_free(s); delete rig; }
+};
 
 }  // namespace
 
@@ -212,7 +238,7 @@ void pf_destroy(pf_ctx* c) {
   hipSetDevice(c->device);
   hipDeviceSynchronize();
   for (auto& kv : c->bufs) if (kv.second.p) hipFree(kv.second.p);
-  for (pf_stitch_plan* pl : c->plans) { hipFree(pl->map); hipFree(pl->ramp); delete pl; }
+  for (pf_stitch_plan* pl : c->plans) plan_free(pl);
   for (pf_rig_plan* rg : c->rigs) delete rg;   // (its step plans went with the list above)
   for (auto e : c->ev_pool) hipEventDestroy(e);
   for (auto& p : c->prof_pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }

@@ -109,7 +109,7 @@ int pf_reproject(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, 
   uint8_t* d_dst = (uint8_t*)ensure(c, "rp_dst", size_t(out_cols) * out_rows * 4);
   if (!d_dst) return PF_ERR_NOMEM;
   if (int e = reproject_many(c, 1, &d_src, &d_dst, g, params->face, nullptr)) return e;
-  if (int e = download_bgra(c, dst_bgra, dst_step, d_dst, out_cols, out_rows)) return e;
+  if (int e = down_plane(c, dst_bgra, dst_step, d_dst, out_cols, out_rows, 4)) return e;
   return finish(c);
 }
 

@@ -93,7 +93,7 @@ int pf_resize(pf_ctx* c, const uint8_t* src_bgra, size_t src_step, int cols, int
   uint8_t* d_dst = (uint8_t*)ensure(c, "rz_dst", size_t(out_cols) * out_rows * 4);
   if (!d_dst) return PF_ERR_NOMEM;
   if (int e = resize_many(c, 1, &d_src, cols, rows, &d_dst, out_cols, out_rows, filter)) return e;
-  if (int e = download_bgra(c, dst_bgra, dst_step, d_dst, out_cols, out_rows)) return e;
+  if (int e = down_plane(c, dst_bgra, dst_step, d_dst, out_cols, out_rows, 4)) return e;
   return finish(c);
 }
 
@@ -122,7 +122,7 @@ int pf_stage_resize_pass(pf_ctx* c, const uint8_t* src_bgra, int cols, int rows,
   if (axis) { PROF(c, c->s_main, "resize_v"); launch_resize_v(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
   else { PROF(c, c->s_main, "resize_h"); launch_resize_h(c->s_main, 1, io, cols, rows, n_out, bounds, k, premul != 0, unpremul != 0); }
   HIPCHK(c, hipGetLastError());
-  if (int e = download_bgra(c, dst_bgra, out_step, d_dst, out_cols, out_rows)) return e;
+  if (int e = down_plane(c, dst_bgra, out_step, d_dst, out_cols, out_rows, 4)) return e;
   return finish(c);
 }
 

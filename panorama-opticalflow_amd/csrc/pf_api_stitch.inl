@@ -1,4 +1,4 @@
-// Part of pf_api.hip (one translation unit, split along its seams in round 5): Stitchtools: prepare / match / blend ramp / gather, the device-resident chain step and its prefetch.
+// Part of pf_api.hip (one translation unit, split along its seams in round 5): Stitchtools: prepare / match / blend ramp / gather, the device-resident chain step and its prefetch, the batched step.  (Plans and the rig chain: pf_api_plan.inl.)
 
 // The ramp's geometry is ramp_geom()'s (kernels_misc.hip), computed once per call.
 static bool tile_reach_ok(int cols, int rows, int k) { return tile_blur_reach(k) < (cols < rows ? cols : rows); }
@@ -97,6 +97,31 @@ static int stitch_step_dev(pf_ctx* c, const StitchPtrs& p, int count, float* con
   return 0;
 }
 
+// The lone calls' planes: the subset `want` of the arena slots below, under the names pf_create pre-sizes, into frame 0 of p (what is not
+// asked for stays null).  SP_CHAIN: the inputs and the composite are the chain's, which stay resident between steps, not the staging slots.
+enum { SP_IN = 1, SP_MAP = 2, SP_OV = 4, SP_RAMP = 8, SP_MERGED = 16, SP_OUT = 32, SP_CHAIN = 64 };
+static int stitch_planes(pf_ctx* c, int want, int cols, int rows, StitchPtrs& p) {
+  const size_t n = size_t(cols) * rows;
+  const bool chain = want & SP_CHAIN;
+  bool ok = true;
+  auto slot = [&](int bit, const char* name, size_t bytes) -> void* {
+    if (!(want & bit)) return nullptr;
+    void* d = ensure(c, name, bytes);
+    ok = ok && d;
+    return d;
+  };
+  p.L[0] = (uint8_t*)slot(SP_IN, chain ? "ch_l" : "h_img0", n * 4); p.R[0] = (uint8_t*)slot(SP_IN, chain ? "ch_r" : "h_img1", n * 4);
+  p.map[0] = (uint8_t*)slot(SP_MAP, "st_map", n); p.ovL[0] = (uint8_t*)slot(SP_OV, "st_ovl", n * 4); p.ovR[0] = (uint8_t*)slot(SP_OV, "st_ovr", n * 4);
+  p.blend[0] = (float*)slot(SP_RAMP, "st_blend", n * 4); p.md[0] = (float*)slot(SP_RAMP, "st_md", n * 4);
+  p.merged[0] = (uint8_t*)slot(SP_MERGED, "st_merged", n * 4); p.out[0] = (uint8_t*)slot(SP_OUT, chain ? "ch_final" : "h_out", n * 4);
+  return ok ? 0 : PF_ERR_NOMEM;
+}
+// a lone call's two input images into p.L / p.R (enqueued on s_main)
+static int up_inputs(pf_ctx* c, const StitchPtrs& p, const uint8_t* l, const uint8_t* r, size_t step, int cols, int rows) {
+  if (int e = up_plane(c, (void*)p.L[0], l, step, cols, rows, 4)) return e;
+  return up_plane(c, (void*)p.R[0], r, step, cols, rows, 4);
+}
+
 int pf_stitch_prepare(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, uint8_t* map_out, size_t mstep, uint8_t* ovl,
                       uint8_t* ovr, float* blend_out, size_t bstep, float* merged_dis) {
   if (int e = use(c)) return e;
@@ -104,26 +129,21 @@ int pf_stitch_prepare(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, i
   if (!l || !r) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (step < size_t(cols) * 4 || (map_out && mstep < size_t(cols)) || (blend_out && bstep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", n * 4);
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
-  if (!dl || !dr || !dm || !dol || !dor || !db || !dmd) return PF_ERR_NOMEM;
+  StitchPtrs p{};
+  if (int e = stitch_planes(c, SP_IN | SP_MAP | SP_OV | SP_RAMP, cols, rows, p)) return e;
   const RampGeom g = ramp_geom(cols, rows);
-  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd;
   RampWork w;
   if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   hipStream_t sm = c->s_main;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
+  if (int e = up_inputs(c, p, l, r, step, cols, rows)) return e;
   { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
   const float* ramp = nullptr;
   if (int e = blend_ramp_dev(c, sm, p, 1, cols, rows, g, w, true, &ramp)) return e;
-  if (map_out) if (int e = down2d(c, map_out, mstep, dm, cols, cols, rows)) return e;
-  if (ovl) if (int e = down2d(c, ovl, step, dol, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (ovr) if (int e = down2d(c, ovr, step, dor, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (blend_out) if (int e = down2d(c, blend_out, bstep, ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (map_out) if (int e = down_plane(c, map_out, mstep, p.map[0], cols, rows, 1)) return e;
+  if (ovl) if (int e = down_plane(c, ovl, step, p.ovL[0], cols, rows, 4)) return e;
+  if (ovr) if (int e = down_plane(c, ovr, step, p.ovR[0], cols, rows, 4)) return e;
+  if (blend_out) if (int e = down_plane(c, blend_out, bstep, ramp, cols, rows, 4)) return e;
+  if (merged_dis) if (int e = down_plane(c, merged_dis, size_t(cols) * 4, p.md[0], cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
   return check_sweeps(c);
@@ -136,17 +156,13 @@ int pf_stitch_match(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int
   if (!l || !r) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (step < size_t(cols) * 4 || (map_out && mstep < size_t(cols))) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", n * 4);
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  if (!dl || !dr || !dm || !dol || !dor) return PF_ERR_NOMEM;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor;
+  StitchPtrs p{};
+  if (int e = stitch_planes(c, SP_IN | SP_MAP | SP_OV, cols, rows, p)) return e;
+  if (int e = up_inputs(c, p, l, r, step, cols, rows)) return e;
   { PROF(c, c->s_main, "match_images"); launch_match_images(c->s_main, p, 1, cols, rows); }
-  if (map_out) if (int e = down2d(c, map_out, mstep, dm, cols, cols, rows)) return e;
-  if (ovl) if (int e = down2d(c, ovl, step, dol, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (ovr) if (int e = down2d(c, ovr, step, dor, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (map_out) if (int e = down_plane(c, map_out, mstep, p.map[0], cols, rows, 1)) return e;
+  if (ovl) if (int e = down_plane(c, ovl, step, p.ovL[0], cols, rows, 4)) return e;
+  if (ovr) if (int e = down_plane(c, ovr, step, p.ovR[0], cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }
@@ -159,18 +175,16 @@ int pf_stitch_generate_blend(pf_ctx* c, const uint8_t* map, size_t mstep, int co
   if (!map || !blend_out) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (mstep < size_t(cols) || bstep < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
-  if (!dm || !db || !dmd) return PF_ERR_NOMEM;
+  StitchPtrs p{};
+  if (int e = stitch_planes(c, SP_MAP | SP_RAMP, cols, rows, p)) return e;
   const RampGeom g = ramp_geom(cols, rows);
-  StitchPtrs p{}; p.map[0] = dm; p.blend[0] = db; p.md[0] = dmd;
   RampWork w;
   if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
-  if (int e = up2d(c, dm, cols, map, mstep, cols, rows)) return e;
+  if (int e = up_plane(c, p.map[0], map, mstep, cols, rows, 1)) return e;
   const float* ramp = nullptr;
   if (int e = blend_ramp_dev(c, c->s_main, p, 1, cols, rows, g, w, true, &ramp)) return e;
-  if (int e = down2d(c, blend_out, bstep, ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (int e = down_plane(c, blend_out, bstep, ramp, cols, rows, 4)) return e;
+  if (merged_dis) if (int e = down_plane(c, merged_dis, size_t(cols) * 4, p.md[0], cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
   return check_sweeps(c);
@@ -184,19 +198,14 @@ int pf_stitch_raw_blend(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols,
   if (!l || !r || !raw_blend) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (step < size_t(cols) * 4 || bstep < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", n * 4);
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
-  if (!dl || !dr || !dm || !dol || !dor || !db || !dmd) return PF_ERR_NOMEM;
+  StitchPtrs p{};
+  if (int e = stitch_planes(c, SP_IN | SP_MAP | SP_OV | SP_RAMP, cols, rows, p)) return e;
   hipStream_t sm = c->s_main;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd;
+  if (int e = up_inputs(c, p, l, r, step, cols, rows)) return e;
   { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
   { PROF(c, sm, "countblend"); launch_countblend(sm, p, 1, cols, rows); }
-  if (int e = down2d(c, raw_blend, bstep, db, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  if (merged_dis) if (int e = down2d(c, merged_dis, size_t(cols) * 4, dmd, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (int e = down_plane(c, raw_blend, bstep, p.blend[0], cols, rows, 4)) return e;
+  if (merged_dis) if (int e = down_plane(c, merged_dis, size_t(cols) * 4, p.md[0], cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }
@@ -208,21 +217,16 @@ int pf_stitch_gather(pf_ctx* c, const uint8_t* l, const uint8_t* r, const uint8_
   if (!l || !r || !merged || !map || !out) return fail(c, PF_ERR_ARG, "null pointer");
   if (int e = check_image(c, cols, rows)) return e;
   if (step < size_t(cols) * 4 || ostep < size_t(cols) * 4 || mstep < size_t(cols)) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "h_img1", n * 4); uint8_t* dg = (uint8_t*)ensure(c, "st_merged", n * 4);
-  uint8_t* dm = (uint8_t*)ensure(c, "st_map", n); uint8_t* dout = (uint8_t*)ensure(c, "h_out", n * 4);
-  if (!dl || !dr || !dg || !dm || !dout) return PF_ERR_NOMEM;
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dg, size_t(cols) * 4, merged, step, size_t(cols) * 4, rows)) return e;
-  if (int e = up2d(c, dm, cols, map, mstep, cols, rows)) return e;
-  StitchPtrs p{}; p.L[0] = dl; p.R[0] = dr; p.merged[0] = dg; p.map[0] = dm; p.out[0] = dout;
+  StitchPtrs p{};
+  if (int e = stitch_planes(c, SP_IN | SP_MERGED | SP_MAP | SP_OUT, cols, rows, p)) return e;
+  if (int e = up_inputs(c, p, l, r, step, cols, rows)) return e;
+  if (int e = up_plane(c, p.merged[0], merged, step, cols, rows, 4)) return e;
+  if (int e = up_plane(c, p.map[0], map, mstep, cols, rows, 1)) return e;
   { PROF(c, c->s_main, "gather"); launch_gather(c->s_main, p, 1, cols, rows); }
-  if (int e = down2d(c, out, ostep, dout, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (int e = down_plane(c, out, ostep, p.out[0], cols, rows, 4)) return e;
   HIPCHK(c, hipGetLastError());
   return finish(c);
 }
-
 
 // One whole iteration of the reference's stitch loop without leaving the device (stitch_step_dev with one frame on the arena's
 // own planes).  r_bgra == NULL chains on the previous call's result, which stays resident in HBM (main.cpp:64-65).
@@ -240,9 +244,9 @@ static uint64_t host_image_sig(const uint8_t* p, int cols, int rows, size_t step
   return h;
 }
 
-// a handle is valid if the context lists it (no dereference before that: a destroyed plan, or another context's, is refused by address)
+// (plan_is_live, pf_api_life.inl: no dereference before the context is found to list the handle)
 static int check_plan(pf_ctx* c, const pf_stitch_plan* plan, int cols, int rows, const char* what) {
-  if (std::find(c->plans.begin(), c->plans.end(), plan) == c->plans.end()) return fail(c, PF_ERR_ARG, "%s: not a live stitch plan of this context", what);
+  if (!plan_is_live(c, plan)) return fail(c, PF_ERR_ARG, "%s: not a live stitch plan of this context", what);
   if (plan->cols != cols || plan->rows != rows) return fail(c, PF_ERR_ARG, "%s: the plan is %dx%d, the canvas %dx%d", what, plan->cols, plan->rows, cols, rows);
   return 0;
 }
@@ -269,18 +273,15 @@ static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t
   check_hw_queues(c, plan ? 4 : 5, what);   // front end, two flow directions, blend ramp (unplanned), prefetch copy
   c->vis_step_valid = false;
   const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "ch_l", n * 4); uint8_t* dr = (uint8_t*)ensure(c, "ch_r", n * 4); uint8_t* dfin = (uint8_t*)ensure(c, "ch_final", n * 4);
-  // a planned step needs neither a map nor ramp planes of its own
-  uint8_t* dm = plan ? plan->map : (uint8_t*)ensure(c, "st_map", n); uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  float* db = plan ? nullptr : (float*)ensure(c, "st_blend", n * 4); float* dmd = plan ? nullptr : (float*)ensure(c, "st_md", n * 4);
-  uint8_t* dmerged = (uint8_t*)ensure(c, "st_merged", n * 4);
-  float* f0 = (float*)ensure(c, "nv_flow_l2r", n * 8); float* f1 = (float*)ensure(c, "nv_flow_r2l", n * 8);
-  if (!dl || !dr || !dfin || !dm || !dol || !dor || (!plan && (!db || !dmd)) || !dmerged || !f0 || !f1) return PF_ERR_NOMEM;
-  hipStream_t sm = c->s_main;
-  uint8_t* dnext = (uint8_t*)ensure(c, "ch_l_next", n * 4);
-  if (!dnext) return PF_ERR_NOMEM;
-  const RampGeom g = ramp_geom(cols, rows);
   StitchPtrs p{};
+  // a planned step needs neither a map nor ramp planes of its own
+  if (int e = stitch_planes(c, SP_CHAIN | SP_IN | SP_OUT | SP_OV | SP_MERGED | (plan ? 0 : SP_MAP | SP_RAMP), cols, rows, p)) return e;
+  if (plan) p.map[0] = plan->map;
+  float* f0 = (float*)ensure(c, "nv_flow_l2r", n * 8); float* f1 = (float*)ensure(c, "nv_flow_r2l", n * 8);
+  uint8_t* dnext = (uint8_t*)ensure(c, "ch_l_next", n * 4);
+  if (!f0 || !f1 || !dnext) return PF_ERR_NOMEM;
+  hipStream_t sm = c->s_main;
+  const RampGeom g = ramp_geom(cols, rows);
   RampWork w;
   if (!plan) if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w)) return e;
   // both prefetch records are one-shot: latched and cleared here, whatever this step does with them
@@ -290,17 +291,17 @@ static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t
     // this step's left image was uploaded while the previous step computed: the two buffers trade places (no copy; the old
     // "ch_l" is free -- the previous call drained every stream -- and receives the next prefetch)
     std::swap(c->bufs["ch_l"], c->bufs["ch_l_next"]);
-    std::swap(dl, dnext);
+    uint8_t* const freed = (uint8_t*)p.L[0];
+    p.L[0] = dnext; dnext = freed;
   } else {
-    if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
+    if (int e = up_plane(c, (void*)p.L[0], l, step, cols, rows, 4)) return e;
   }
-  if (r) { if (int e = up2d(c, dr, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e; }
+  if (r) { if (int e = up_plane(c, (void*)p.R[0], r, step, cols, rows, 4)) return e; }
   else {
     if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "%s: no previous result of this size to chain on", what);
-    HIPCHK(c, hipMemcpyAsync(dr, dfin, n * 4, hipMemcpyDeviceToDevice, sm));
+    HIPCHK(c, hipMemcpyAsync((void*)p.R[0], p.out[0], n * 4, hipMemcpyDeviceToDevice, sm));
   }
   if (!c->s_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
-  p.L[0] = dl; p.R[0] = dr; p.map[0] = dm; p.ovL[0] = dol; p.ovR[0] = dor; p.blend[0] = db; p.md[0] = dmd; p.merged[0] = dmerged; p.out[0] = dfin;
   float* const flows[2] = {f0, f1};
   // "ch_final" is rewritten from here on; a frame that fails the plan leaves nothing to chain on.  (So does a planned step that fails for
   // any other reason, e.g. an allocation inside the solve, where the unplanned step keeps the old chain size: the composite it
@@ -311,8 +312,7 @@ static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t
   // host-side staging of a pageable source runs while the GPU computes
   auto prefetch_next = [&]() -> int {
     if (hint.src && hint.src != l && hint.cols == cols && hint.rows == rows) {
-      if (hint.step == size_t(cols) * 4) HIPCHK(c, hipMemcpyAsync(dnext, hint.src, n * 4, hipMemcpyHostToDevice, c->s_copy));
-      else HIPCHK(c, hipMemcpy2DAsync(dnext, size_t(cols) * 4, hint.src, hint.step, size_t(cols) * 4, rows, hipMemcpyHostToDevice, c->s_copy));
+      HIPCHK(c, up_plane_on(c->s_copy, dnext, hint.src, hint.step, cols, rows, 4));
       HIPCHK(c, hipStreamSynchronize(c->s_copy));
       c->ready = hint;
       c->ready.sig = host_image_sig(hint.src, cols, rows, hint.step);
@@ -320,7 +320,7 @@ static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t
     return 0;
   };
   if (!plan) {
-    if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+    if (out) if (int e = down_plane(c, out, ostep, p.out[0], cols, rows, 4)) return e;
     if (int e = prefetch_next()) return e;
   } else {
     // the composite goes to the caller only once the frame is known to match the plan: the step is drained (the prefetch upload ran
@@ -333,7 +333,7 @@ static int stitch_step_lone(pf_ctx* c, const pf_stitch_plan* plan, const uint8_t
     if (int e = check_sweeps(c)) return e;
     if (int e = report_plan_diff(c, what, &diff, 1)) return e;
     c->drained = false;   // the download below is this call's work again
-    if (out) if (int e = down2d(c, out, ostep, dfin, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+    if (out) if (int e = down_plane(c, out, ostep, p.out[0], cols, rows, 4)) return e;
   }
   HIPCHK(c, hipGetLastError());
   if (int e = finish(c)) return e;
@@ -415,6 +415,16 @@ int stitch_group(pf_ctx* lane, int first, int count, const uint8_t* const* d_l, 
 bool overlaps(const void* a, const void* b, size_t bytes) { return ranges_overlap(a, bytes, b, bytes); }
 }  // namespace
 
+// A device form fails as a whole: no composite is delivered.  The caller's `count` buffers of `bytes` each are cleared and the call fails
+// with `code` and the message it had on entry (the first error's).
+static int clear_outputs(pf_ctx* c, int code, uint8_t* const* d_out, size_t count, size_t bytes) {
+  const std::string msg = c->err;
+  CallGuard guard_(c);
+  for (size_t k = 0; k < count; ++k) HIPCHK(c, hipMemsetAsync(d_out[k], 0, bytes, c->s_main));
+  if (int e = finish(c)) return e;
+  return fail(c, code, "%s", msg.c_str());
+}
+
 static int stitch_batch_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
                             uint8_t* const* d_out, int in_flight) {
   if (int e = use(c)) return e;
@@ -437,22 +447,13 @@ static int stitch_batch_dev(pf_ctx* c, const pf_stitch_plan* plan, int n_frames,
     for (int j = 0; j < n_frames; ++j)
       if (overlaps(d_out[k], d_l[j], bytes) || overlaps(d_out[k], d_r[j], bytes) || (j != k && overlaps(d_out[k], d_out[j], bytes)))
         return fail(c, PF_ERR_ARG, "d_out[%d] overlaps an input or another output of the call (frame %d)", k, j);
-  if (!plan)
-    return run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
-      return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out);
-    });
-  std::vector<unsigned> diff(n_frames, 0u);
-  if (int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, "pf_stitch_step_batch_planned", [&](pf_ctx* lane, int first, int count) {
+  std::vector<unsigned> diff(plan ? n_frames : 0, 0u);
+  if (int e = run_lanes(c, n_frames, in_flight, cols, rows, 3, plan ? "pf_stitch_step_batch_planned" : "pf_stitch_step_batch", [&](pf_ctx* lane, int first, int count) {
         return stitch_group(lane, first, count, d_l, d_r, cols, rows, max_pct, d_out, plan, diff.data());
       })) return e;
-  if (std::all_of(diff.begin(), diff.end(), [](unsigned d) { return d == 0; })) return 0;
-  // the call fails as a whole: no composite is delivered (the gathers have run, so the caller's buffers are cleared)
-  {
-    CallGuard guard_(c);
-    for (int k = 0; k < n_frames; ++k) HIPCHK(c, hipMemsetAsync(d_out[k], 0, bytes, c->s_main));
-    if (int e = finish(c)) return e;
-  }
-  return report_plan_diff(c, "pf_stitch_step_batch_planned_dev", diff.data(), n_frames);
+  // a frame off the plan: the gathers have run, so the caller's buffers are cleared
+  if (plan) if (int e = report_plan_diff(c, "pf_stitch_step_batch_planned_dev", diff.data(), n_frames)) return clear_outputs(c, e, d_out, n_frames, bytes);
+  return 0;
 }
 int pf_stitch_step_batch_dev(pf_ctx* c, int n_frames, const uint8_t* const* d_l, const uint8_t* const* d_r, int cols, int rows, int max_pct,
                              uint8_t* const* d_out, int in_flight) {
@@ -493,8 +494,8 @@ static int stitch_batch_host(pf_ctx* c, const pf_stitch_plan* plan, int n_frames
   {
     CallGuard guard_(c);
     for (int k = 0; k < n_frames; ++k) {
-      if (int e = up2d(c, dl[k], size_t(cols) * 4, l[k], step, size_t(cols) * 4, rows)) return e;
-      if (r && r[k]) { if (int e = up2d(c, dr[k], size_t(cols) * 4, r[k], step, size_t(cols) * 4, rows)) return e; }
+      if (int e = up_plane(c, dl[k], l[k], step, cols, rows, 4)) return e;
+      if (r && r[k]) { if (int e = up_plane(c, dr[k], r[k], step, cols, rows, 4)) return e; }
       else HIPCHK(c, hipMemcpyAsync(dr[k], dfin[k], n * 4, hipMemcpyDeviceToDevice, c->s_main));
     }
     if (int e = finish(c)) return e;   // the lanes' streams start from complete inputs
@@ -509,7 +510,7 @@ static int stitch_batch_host(pf_ctx* c, const pf_stitch_plan* plan, int n_frames
   if (out) {
     CallGuard guard_(c);
     for (int k = 0; k < n_frames; ++k)
-      if (out[k]) if (int e2 = down2d(c, out[k], ostep, dfin[k], size_t(cols) * 4, size_t(cols) * 4, rows)) return e2;
+      if (out[k]) if (int e2 = down_plane(c, out[k], ostep, dfin[k], cols, rows, 4)) return e2;
     HIPCHK(c, hipGetLastError());
     if (int e2 = finish(c)) return e2;
   }
@@ -525,497 +526,4 @@ int pf_stitch_step_batch_planned(pf_ctx* c, const pf_stitch_plan* plan, int n_fr
   if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
   if (!plan) return fail(c, PF_ERR_ARG, "pf_stitch_step_batch_planned: null plan");
   return stitch_batch_host(c, plan, n_frames, l, r, cols, rows, step, max_pct, out, ostep, in_flight);
-}
-
-// ---- stitch plans ----
-// Creation: MatchImages into the plan's map, then the blend ramp by blend_ramp_dev with ramp_geom()'s geometry and form, finishing in
-// the plan's ramp plane (the box blur's result plane, or the in-place ramp where the canvas has no box blur); the working planes are the
-// lone entry points' ("st_*"), the inputs go through "h_img0/1": the chain ("ch_*"), the prefetch records and the visualiser's inputs stay.
-static int stitch_plan_make(pf_ctx* c, const uint8_t* dl, const uint8_t* dr, int cols, int rows, const RampGeom& g, pf_stitch_plan** plan_out) {
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dol = (uint8_t*)ensure(c, "st_ovl", n * 4); uint8_t* dor = (uint8_t*)ensure(c, "st_ovr", n * 4);
-  float* db = (float*)ensure(c, "st_blend", n * 4); float* dmd = (float*)ensure(c, "st_md", n * 4);
-  unsigned* dcount = (unsigned*)ensure(c, "plan_count", 256);
-  if (!dol || !dor || !db || !dmd || !dcount) return PF_ERR_NOMEM;
-  StitchPtrs p{};
-  RampWork w;
-  if (int e = ramp_planes(c, kRampLone, 1, cols, rows, g, p, w, false)) return e;
-  pf_stitch_plan* pl = new pf_stitch_plan();
-  pl->cols = cols; pl->rows = rows;
-  struct Drop { pf_stitch_plan* pl; ~Drop() { if (pl) { hipFree(pl->map); hipFree(pl->ramp); delete pl; } } } drop{pl};
-  if (hipMalloc((void**)&pl->map, (n + 255) & ~size_t(255)) != hipSuccess || hipMalloc((void**)&pl->ramp, (n * 4 + 255) & ~size_t(255)) != hipSuccess)
-    return fail(c, PF_ERR_NOMEM, "hipMalloc of a %dx%d stitch plan (5 B/px) failed", cols, rows);
-  hipStream_t sm = c->s_main;
-  p.L[0] = dl; p.R[0] = dr; p.map[0] = pl->map; p.ovL[0] = dol; p.ovR[0] = dor; p.md[0] = dmd;
-  if (g.k2 > 0) { p.blend[0] = db; p.tmp[0] = pl->ramp; } else p.blend[0] = pl->ramp;
-  { PROF(c, sm, "match_images"); launch_match_images(sm, p, 1, cols, rows); }
-  const float* ramp = nullptr;
-  if (int e = blend_ramp_dev(c, sm, p, 1, cols, rows, g, w, true, &ramp)) return e;
-  HIPCHK(c, hipMemsetAsync(dcount, 0, 4, sm));
-  launch_count_code(sm, pl->map, cols, rows, 150, dcount);
-  unsigned overlap = 0;
-  HIPCHK(c, hipMemcpyAsync(&overlap, dcount, 4, hipMemcpyDeviceToHost, sm));
-  HIPCHK(c, hipGetLastError());
-  if (int e = finish(c)) return e;
-  if (int e = check_sweeps(c)) return e;
-  pl->overlap_px = overlap;
-  c->plans.push_back(pl);
-  drop.pl = nullptr;
-  *plan_out = pl;
-  return 0;
-}
-int pf_stitch_plan_create(pf_ctx* c, const uint8_t* l, const uint8_t* r, int cols, int rows, size_t step, pf_stitch_plan** plan_out) {
-  if (int e = use(c)) return e;
-  CallGuard guard_(c);
-  if (!l || !plan_out) return fail(c, PF_ERR_ARG, "null pointer");
-  *plan_out = nullptr;
-  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  if (step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  const RampGeom g = ramp_geom(cols, rows);
-  if (int e = check_blend_ramp(c, cols, rows, g)) return e;
-  const size_t n = size_t(cols) * rows;
-  uint8_t* dl = (uint8_t*)ensure(c, "h_img0", n * 4);
-  if (!dl) return PF_ERR_NOMEM;
-  const uint8_t* dr = nullptr;
-  if (r) {
-    uint8_t* up = (uint8_t*)ensure(c, "h_img1", n * 4);
-    if (!up) return PF_ERR_NOMEM;
-    if (int e = up2d(c, up, size_t(cols) * 4, r, step, size_t(cols) * 4, rows)) return e;
-    dr = up;
-  } else {
-    if (c->chain_cols != cols || c->chain_rows != rows) return fail(c, PF_ERR_ARG, "pf_stitch_plan_create: no previous result of this size to take the R mask from");
-    dr = (const uint8_t*)ensure(c, "ch_final", n * 4);   // read in place
-    if (!dr) return PF_ERR_NOMEM;
-  }
-  if (int e = up2d(c, dl, size_t(cols) * 4, l, step, size_t(cols) * 4, rows)) return e;
-  return stitch_plan_make(c, dl, dr, cols, rows, g, plan_out);
-}
-int pf_stitch_plan_create_dev(pf_ctx* c, const uint8_t* d_l, const uint8_t* d_r, int cols, int rows, pf_stitch_plan** plan_out) {
-  if (int e = use(c)) return e;
-  CallGuard guard_(c);
-  if (!d_l || !d_r || !plan_out) return fail(c, PF_ERR_ARG, "null pointer");
-  *plan_out = nullptr;
-  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  const RampGeom g = ramp_geom(cols, rows);
-  if (int e = check_blend_ramp(c, cols, rows, g)) return e;
-  const uint8_t* const imgs[2] = {d_l, d_r};
-  if (int e = check_dev_align(c, "pf_stitch_plan_create_dev", "image", imgs, 2)) return e;
-  return stitch_plan_make(c, d_l, d_r, cols, rows, g, plan_out);
-}
-int pf_stitch_plan_destroy(pf_ctx* c, pf_stitch_plan* plan) {
-  if (int e = use(c)) return e;
-  auto it = std::find(c->plans.begin(), c->plans.end(), plan);
-  if (it == c->plans.end()) return fail(c, PF_ERR_ARG, "pf_stitch_plan_destroy: not a live stitch plan of this context");
-  if (plan->rig_owned) return fail(c, PF_ERR_ARG, "pf_stitch_plan_destroy: the plan is a step of a rig plan (pf_rig_plan_destroy frees it)");
-  c->plans.erase(it);
-  hipFree(plan->map); hipFree(plan->ramp);   // every call is synchronous on return: nothing in flight reads them
-  delete plan;
-  return 0;
-}
-int pf_stitch_plan_info(const pf_stitch_plan* plan, int* cols, int* rows, long long* overlap_px) {
-  if (!plan) return fail(nullptr, PF_ERR_ARG, "null plan");
-  if (cols) *cols = plan->cols;
-  if (rows) *rows = plan->rows;
-  if (overlap_px) *overlap_px = plan->overlap_px;
-  return 0;
-}
-int pf_stitch_plan_download(pf_ctx* c, const pf_stitch_plan* plan, uint8_t* map_out, size_t mstep, float* blend_out, size_t bstep) {
-  if (int e = use(c)) return e;
-  CallGuard guard_(c);
-  if (std::find(c->plans.begin(), c->plans.end(), plan) == c->plans.end()) return fail(c, PF_ERR_ARG, "pf_stitch_plan_download: not a live stitch plan of this context");
-  const int cols = plan->cols, rows = plan->rows;
-  if ((map_out && mstep < size_t(cols)) || (blend_out && bstep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
-  if (map_out) if (int e = down2d(c, map_out, mstep, plan->map, cols, cols, rows)) return e;
-  if (blend_out) if (int e = down2d(c, blend_out, bstep, plan->ramp, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
-  return finish(c);
-}
-
-// ---- rig plans: the plans of a whole chain from its n + 1 input masks, and the chain in one call ----
-// A composite's alpha is > 0 exactly where L's or R's is, so the R mask of step i is top | L_1 | .. | L_{i-1}: k_rig_maps (kernels_misc.hip)
-// derives every step's map in one pass over the inputs, and the n ramps go through blend_ramp_dev as ONE group of n frames.
-namespace {
-// a handle is valid if the context lists it (never dereferenced before that, as with stitch plans)
-int check_rig(pf_ctx* c, const pf_rig_plan* rig, int cols, int rows, const char* what) {
-  if (std::find(c->rigs.begin(), c->rigs.end(), rig) == c->rigs.end()) return fail(c, PF_ERR_ARG, "%s: not a live rig plan of this context", what);
-  if (cols > 0 && (rig->cols != cols || rig->rows != rows)) return fail(c, PF_ERR_ARG, "%s: the rig plan is %dx%d, the canvas %dx%d", what, rig->cols, rig->rows, cols, rows);
-  return 0;
-}
-// the mapped words k_rig_maps (verify) counts into, zeroed: frames x steps of one call
-int rig_diff_words(pf_ctx* c, size_t words) {
-  if (c->rig_diff_cap < words) {
-    if (c->h_rig_diff) hipHostFree(c->h_rig_diff);
-    c->h_rig_diff = c->d_rig_diff = nullptr; c->rig_diff_cap = 0;
-    const size_t cap = std::max(words, size_t(kMaxBatch) * kMaxBatch);
-    if (hipHostMalloc((void**)&c->h_rig_diff, cap * sizeof(unsigned), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->d_rig_diff, c->h_rig_diff, 0) != hipSuccess) {
-      if (c->h_rig_diff) hipHostFree(c->h_rig_diff);
-      c->h_rig_diff = c->d_rig_diff = nullptr;
-      return fail(c, PF_ERR_NOMEM, "hipHostMalloc of %zu mapped words failed", cap);
-    }
-    c->rig_diff_cap = cap;
-  }
-  memset(c->h_rig_diff, 0, words * sizeof(unsigned));
-  return 0;
-}
-// after the sync that followed the verifying launches: the first frame off the rig, its first differing step and the pixel count
-// (tools/pano_stitch.cpp reads the frame index out of this message: keep "frame %d differs from the rig plan")
-int report_rig_diff(pf_ctx* c, const char* what, int n_frames, int n_steps) {
-  for (int k = 0; k < n_frames; ++k)
-    for (int i = 0; i < n_steps; ++i) {
-      const unsigned d = __atomic_load_n(c->h_rig_diff + size_t(k) * n_steps + i, __ATOMIC_ACQUIRE);
-      if (d) return fail(c, PF_ERR_ARG, "%s: frame %d differs from the rig plan at step %d in %u pixels' region codes (alpha masks are not the rig's)", what, k, i + 1, d);
-    }
-  return 0;
-}
-uint8_t* rig_slot(pf_ctx* c, const char* kind, int w, int j, size_t bytes) {
-  char name[40];
-  snprintf(name, sizeof name, "rg_%s%d_%d", kind, w, j);
-  return (uint8_t*)ensure(c, name, bytes);
-}
-bool all_aligned16(const uint8_t* const* p, size_t count) {
-  uintptr_t bits = 0;
-  for (size_t i = 0; i < count; ++i) bits |= (uintptr_t)p[i];
-  return (bits & 15) == 0;
-}
-RigMaps rig_maps(const pf_rig_plan* rig) {
-  RigMaps m{};
-  for (int i = 0; i < rig->n_steps; ++i) m.m[i] = rig->steps[i]->map;
-  return m;
-}
-int clamp_in_flight(int in_flight, int n_frames) {   // run_lanes' clamp
-  if (in_flight < 1) in_flight = 1;
-  if (in_flight > 2 * kMaxBatch) in_flight = 2 * kMaxBatch;
-  if (in_flight > n_frames) in_flight = n_frames;
-  return in_flight;
-}
-// d_img: n_steps + 1 device images (top, L_1 .. L_n) of this context's device, complete on s_main's timeline
-int rig_plan_make(pf_ctx* c, int n_steps, const uint8_t* const* d_img, int cols, int rows, const RampGeom& g, pf_rig_plan** out) {
-  const size_t n = size_t(cols) * rows;
-  const uint8_t** tbl = (const uint8_t**)ensure(c, "rg_tbl", size_t(n_steps + 1) * sizeof(void*));
-  unsigned* dcount = (unsigned*)ensure(c, "plan_count", 256);
-  size_t s4 = 0;
-  float* blend = frame_planes<float>(c, "sb_blend", n_steps, n * 4, s4); float* md = frame_planes<float>(c, "sb_md", n_steps, n * 4, s4);
-  if (!tbl || !dcount || !blend || !md) return PF_ERR_NOMEM;
-  StitchPtrs p{};
-  RampWork w;
-  if (int e = ramp_planes(c, kRampBatch, n_steps, cols, rows, g, p, w, false)) return e;
-  pf_rig_plan* rig = new pf_rig_plan();
-  rig->n_steps = n_steps; rig->cols = cols; rig->rows = rows;
-  struct Drop { pf_rig_plan* rig; ~Drop() { if (rig) { for (pf_stitch_plan* pl : rig->steps) { hipFree(pl->map); hipFree(pl->ramp); delete pl; } delete rig; } } } drop{rig};
-  for (int i = 0; i < n_steps; ++i) {
-    pf_stitch_plan* pl = new pf_stitch_plan();
-    pl->cols = cols; pl->rows = rows; pl->rig_owned = true;
-    rig->steps.push_back(pl);
-    if (hipMalloc((void**)&pl->map, (n + 255) & ~size_t(255)) != hipSuccess || hipMalloc((void**)&pl->ramp, (n * 4 + 255) & ~size_t(255)) != hipSuccess)
-      return fail(c, PF_ERR_NOMEM, "hipMalloc of a %dx%d rig plan (5 B/px per step, %d steps) failed", cols, rows, n_steps);
-  }
-  hipStream_t sm = c->s_main;
-  HIPCHK(c, hipMemcpyAsync(tbl, d_img, size_t(n_steps + 1) * sizeof(void*), hipMemcpyHostToDevice, sm));
-  HIPCHK(c, hipMemsetAsync(dcount, 0, kMaxBatch * sizeof(unsigned), sm));
-  { PROF(c, sm, "rig_maps"); launch_rig_maps_make(sm, tbl, all_aligned16(d_img, n_steps + 1), rig_maps(rig), n_steps, cols, rows, dcount); }
-  for (int i = 0; i < n_steps; ++i) {
-    p.map[i] = rig->steps[i]->map; p.md[i] = (float*)((char*)md + i * s4);
-    float* work = (float*)((char*)blend + i * s4);
-    if (g.k2 > 0) { p.blend[i] = work; p.tmp[i] = rig->steps[i]->ramp; } else p.blend[i] = rig->steps[i]->ramp;
-  }
-  const float* ramp[kMaxBatch];
-  if (int e = blend_ramp_dev(c, sm, p, n_steps, cols, rows, g, w, true, ramp)) return e;
-  unsigned overlap[kMaxBatch] = {0};
-  HIPCHK(c, hipMemcpyAsync(overlap, dcount, kMaxBatch * sizeof(unsigned), hipMemcpyDeviceToHost, sm));
-  HIPCHK(c, hipGetLastError());
-  if (int e = finish(c)) return e;
-  if (int e = check_sweeps(c)) return e;
-  for (int i = 0; i < n_steps; ++i) { rig->steps[i]->overlap_px = overlap[i]; c->plans.push_back(rig->steps[i]); }
-  c->rigs.push_back(rig);
-  drop.rig = nullptr;
-  *out = rig;
-  return 0;
-}
-int check_rig_create(pf_ctx* c, int n_steps, const void* top, const void* l, int cols, int rows, pf_rig_plan** out, RampGeom& g) {
-  if (!top || !l || !out) return fail(c, PF_ERR_ARG, "null pointer");
-  *out = nullptr;
-  if (n_steps < 1 || n_steps > kMaxBatch) return fail(c, PF_ERR_ARG, "a rig plan has 1..%d steps (n_steps = %d)", kMaxBatch, n_steps);
-  if (int e = check_dims(c, cols, rows, cols / 20)) return e;
-  g = ramp_geom(cols, rows);
-  return check_blend_ramp(c, cols, rows, g);
-}
-}  // namespace
-
-int pf_rig_plan_create(pf_ctx* c, int n_steps, const uint8_t* top, const uint8_t* const* l, int cols, int rows, size_t step, pf_rig_plan** out) {
-  if (int e = use(c)) return e;
-  CallGuard guard_(c);
-  RampGeom g;
-  if (int e = check_rig_create(c, n_steps, top, l, cols, rows, out, g)) return e;
-  for (int i = 0; i < n_steps; ++i) if (!l[i]) return fail(c, PF_ERR_ARG, "null pointer (step %d)", i + 1);
-  if (step < size_t(cols) * 4) return fail(c, PF_ERR_ARG, "row step too small");
-  const size_t n = size_t(cols) * rows;
-  const uint8_t* d_img[kMaxBatch + 1];
-  for (int j = 0; j <= n_steps; ++j) {
-    uint8_t* d = rig_slot(c, "in", 0, j, n * 4);
-    if (!d) return PF_ERR_NOMEM;
-    if (int e = up2d(c, d, size_t(cols) * 4, j == 0 ? top : l[j - 1], step, size_t(cols) * 4, rows)) return e;
-    d_img[j] = d;
-  }
-  return rig_plan_make(c, n_steps, d_img, cols, rows, g, out);
-}
-int pf_rig_plan_create_dev(pf_ctx* c, int n_steps, const uint8_t* d_top, const uint8_t* const* d_l, int cols, int rows, pf_rig_plan** out) {
-  if (int e = use(c)) return e;
-  CallGuard guard_(c);
-  RampGeom g;
-  if (int e = check_rig_create(c, n_steps, d_top, d_l, cols, rows, out, g)) return e;
-  const uint8_t* d_img[kMaxBatch + 1];
-  d_img[0] = d_top;
-  for (int i = 0; i < n_steps; ++i) { if (!d_l[i]) return fail(c, PF_ERR_ARG, "null device pointer (step %d)", i + 1); d_img[i + 1] = d_l[i]; }
-  if (int e = check_dev_align(c, "pf_rig_plan_create_dev", "image", d_img, size_t(n_steps) + 1)) return e;
-  return rig_plan_make(c, n_steps, d_img, cols, rows, g, out);
-}
-int pf_rig_plan_destroy(pf_ctx* c, pf_rig_plan* rig) {
-  if (int e = use(c)) return e;
-  auto it = std::find(c->rigs.begin(), c->rigs.end(), rig);
-  if (it == c->rigs.end()) return fail(c, PF_ERR_ARG, "pf_rig_plan_destroy: not a live rig plan of this context");
-  c->rigs.erase(it);
-  for (pf_stitch_plan* pl : rig->steps) {   // every call is synchronous on return: nothing in flight reads them
-    c->plans.erase(std::remove(c->plans.begin(), c->plans.end(), pl), c->plans.end());
-    hipFree(pl->map); hipFree(pl->ramp);
-    delete pl;
-  }
-  delete rig;
-  return 0;
-}
-int pf_rig_plan_info(const pf_rig_plan* rig, int* n_steps, int* cols, int* rows) {
-  if (!rig) return fail(nullptr, PF_ERR_ARG, "null rig plan");
-  if (n_steps) *n_steps = rig->n_steps;
-  if (cols) *cols = rig->cols;
-  if (rows) *rows = rig->rows;
-  return 0;
-}
-const pf_stitch_plan* pf_rig_plan_step(pf_ctx* c, const pf_rig_plan* rig, int step) {
-  if (!c) { fail(nullptr, PF_ERR_ARG, "null context"); return nullptr; }
-  if (check_rig(c, rig, 0, 0, "pf_rig_plan_step")) return nullptr;
-  if (step < 0 || step >= rig->n_steps) { fail(c, PF_ERR_ARG, "pf_rig_plan_step: step %d of a rig plan of %d steps (0-based)", step, rig->n_steps); return nullptr; }
-  return rig->steps[step];
-}
-
-// The chain in one call.  Frames go through in waves of `in_flight`; a wave runs its steps one after the other through stitch_group with
-// step i's plan (run_lanes' lanes and groups), R of step i + 1 = the composite of step i, which ping-pongs between two internal planes
-// per frame in flight (or lies in the caller's buffer, device form).  Every frame is verified against the rig's maps before any solve.
-namespace {
-// one step of one wave: `count` frames, arrays indexed by the frame's place in the wave
-int rig_wave_step(pf_ctx* c, const pf_rig_plan* rig, int i, int count, const uint8_t* const* dl, const uint8_t* const* dr, uint8_t* const* dout, int cols, int rows,
-                  int max_pct, int in_flight, const char* what) {
-  std::vector<unsigned> diff(count, 0u);
-  if (int e = run_lanes(c, count, in_flight, cols, rows, 3, what, [&](pf_ctx* lane, int first, int cnt) {
-        return stitch_group(lane, first, cnt, dl, dr, cols, rows, max_pct, dout, rig->steps[i], diff.data());
-      })) return e;
-  for (int k = 0; k < count; ++k)
-    if (diff[k]) return fail(c, PF_ERR_DEVICE, "%s: internal error: step %d's match found %u pixels off the plan in a frame that passed the rig's verification", what, i + 1, diff[k]);
-  return 0;
-}
-}  // namespace
-
-int pf_rig_stitch_batch(pf_ctx* c, const pf_rig_plan* rig, int n_frames, const uint8_t* const* top, const uint8_t* const* l, int cols, int rows, size_t step,
-                        int max_pct, uint8_t* const* out, size_t ostep, int in_flight) {
-  const char* const what = "pf_rig_stitch_batch";
-  if (int e = use(c)) return e;
-  c->vis_step_valid = false;   // lane 0 solves in this context's arena
-  if (n_frames < 0 || !top || !l) return fail(c, PF_ERR_ARG, "bad argument");
-  if (int e = check_rig(c, rig, cols, rows, what)) return e;
-  if (n_frames == 0) return 0;
-  const int ns = rig->n_steps;
-  for (int k = 0; k < n_frames; ++k) {
-    if (!top[k]) return fail(c, PF_ERR_ARG, "null pointer (frame %d)", k);
-    for (int i = 0; i < ns; ++i) if (!l[size_t(k) * ns + i]) return fail(c, PF_ERR_ARG, "null pointer (frame %d, step %d)", k, i + 1);
-  }
-  if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
-  if (step < size_t(cols) * 4 || (out && ostep < size_t(cols) * 4)) return fail(c, PF_ERR_ARG, "row step too small");
-  const int W = clamp_in_flight(in_flight, n_frames), nwaves = (n_frames + W - 1) / W;
-  const size_t n = size_t(cols) * rows, rb = size_t(cols) * 4;
-  // per frame in flight: the n + 1 inputs -- two sets of them where the call has several waves, wave wv in set wv & 1 -- and two composites
-  const int nsets = nwaves > 1 ? 2 : 1;
-  const size_t set_len = size_t(W) * (ns + 1);
-  std::vector<const uint8_t*> in(nsets * set_len);
-  std::vector<uint8_t*> comp(size_t(W) * 2);
-  for (int w = 0; w < nsets * W; ++w)
-    for (int j = 0; j <= ns; ++j) if (!(in[size_t(w) * (ns + 1) + j] = rig_slot(c, "in", w, j, n * 4))) return PF_ERR_NOMEM;
-  for (int w = 0; w < W; ++w)
-    for (int j = 0; j < 2; ++j) if (!(comp[w * 2 + j] = rig_slot(c, "c", w, j, n * 4))) return PF_ERR_NOMEM;
-  const uint8_t** tbl = (const uint8_t**)ensure(c, "rg_tbl", in.size() * sizeof(void*));
-  if (!tbl) return PF_ERR_NOMEM;
-  if (int e = rig_diff_words(c, size_t(n_frames) * ns)) return e;
-  auto upload_wave = [&](int wv) -> int {
-    const int first = wv * W, count = std::min(W, n_frames - first);
-    const uint8_t* const* slot = in.data() + (wv & 1) * set_len;
-    for (int w = 0; w < count; ++w)
-      for (int j = 0; j <= ns; ++j) {
-        const uint8_t* src = j == 0 ? top[first + w] : l[size_t(first + w) * ns + j - 1];
-        if (int e = up2d(c, (void*)slot[size_t(w) * (ns + 1) + j], rb, src, step, rb, rows)) return e;
-      }
-    return 0;
-  };
-  // The overlapped form of a later wave's second upload: while wave wv - 1 computes, a host thread of its own copies wave wv (>= 2) into
-  // the set wave wv - 2 has left, on the copy stream.  (A thread, because the copy of a pageable source blocks its caller while it is
-  // staged: issued from the calling thread it would hold back the launches it is meant to run beside.)
-  struct Prefetch {
-    std::thread th; hipError_t err = hipSuccess;
-    int join() { if (th.joinable()) th.join(); return err == hipSuccess ? 0 : 1; }
-    ~Prefetch() { if (th.joinable()) th.join(); }
-  } pre;
-  auto prefetch_wave = [&](int wv) {
-    pre.err = hipSuccess;
-    pre.th = std::thread([&, wv]() {
-      const int first = wv * W, count = std::min(W, n_frames - first);
-      const uint8_t* const* slot = in.data() + (wv & 1) * set_len;
-      hipError_t e = hipSetDevice(c->device);
-      for (int w = 0; w < count && e == hipSuccess; ++w)
-        for (int j = 0; j <= ns && e == hipSuccess; ++j) {
-          const uint8_t* src = j == 0 ? top[first + w] : l[size_t(first + w) * ns + j - 1];
-          void* dst = (void*)slot[size_t(w) * (ns + 1) + j];
-          e = step == rb ? hipMemcpyAsync(dst, src, rb * size_t(rows), hipMemcpyHostToDevice, c->s_copy)
-                         : hipMemcpy2DAsync(dst, rb, src, step, rb, rows, hipMemcpyHostToDevice, c->s_copy);
-        }
-      if (e == hipSuccess) e = hipStreamSynchronize(c->s_copy);
-      pre.err = e;
-    });
-  };
-  const bool overlap = c->rig_overlap_uploads && nwaves > 2;
-  if (overlap && !c->s_copy) HIPCHK(c, hipStreamCreateWithFlags(&c->s_copy, hipStreamNonBlocking));
-  {
-    // verification: every wave's images go through its set of slots and one verifying launch, the last wave first, so that waves 0 and 1
-    // are resident when the solves begin (a call of up to two waves uploads nothing twice)
-    CallGuard guard_(c);
-    HIPCHK(c, hipMemcpyAsync(tbl, in.data(), in.size() * sizeof(void*), hipMemcpyHostToDevice, c->s_main));
-    for (int wv = nwaves - 1; wv >= 0; --wv) {
-      const int first = wv * W, count = std::min(W, n_frames - first);
-      if (int e = upload_wave(wv)) return e;
-      PROF(c, c->s_main, "rig_verify");
-      launch_rig_maps_verify(c->s_main, tbl + (wv & 1) * set_len, true, rig_maps(rig), ns, count, cols, rows, c->d_rig_diff + size_t(first) * ns);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (int e = finish(c)) return e;
-  }
-  if (int e = report_rig_diff(c, what, n_frames, ns)) return e;   // nothing is solved, nothing downloaded
-  std::vector<const uint8_t*> dl(W), dr(W);
-  std::vector<uint8_t*> dout(W);
-  for (int wv = 0; wv < nwaves; ++wv) {
-    const int first = wv * W, count = std::min(W, n_frames - first);
-    if (wv > 1) {   // into the set wave wv - 2 has left
-      if (overlap) {
-        if (pre.join()) return fail(c, PF_ERR_DEVICE, "%s: the upload of wave %d beside wave %d's compute failed: %s", what, wv, wv - 1, hipGetErrorString(pre.err));
-      } else {
-        CallGuard guard_(c);
-        if (int e = upload_wave(wv)) return e;
-        if (int e = finish(c)) return e;   // the lanes' streams start from complete inputs
-      }
-    }
-    if (overlap && wv >= 1 && wv + 1 < nwaves) prefetch_wave(wv + 1);
-    const uint8_t* const* slot = in.data() + (wv & 1) * set_len;
-    for (int i = 0; i < ns; ++i) {
-      for (int w = 0; w < count; ++w) {
-        dl[w] = slot[size_t(w) * (ns + 1) + i + 1];
-        dr[w] = i == 0 ? slot[size_t(w) * (ns + 1)] : comp[w * 2 + ((i - 1) & 1)];
-        dout[w] = comp[w * 2 + (i & 1)];
-      }
-      if (int e = rig_wave_step(c, rig, i, count, dl.data(), dr.data(), dout.data(), cols, rows, max_pct, in_flight, what)) return e;
-      bool any = false;
-      for (int w = 0; out && w < count; ++w) any = any || out[size_t(first + w) * ns + i];
-      if (!any) continue;
-      CallGuard guard_(c);
-      for (int w = 0; w < count; ++w)
-        if (uint8_t* o = out[size_t(first + w) * ns + i]) if (int e = down2d(c, o, ostep, dout[w], rb, rb, rows)) return e;
-      HIPCHK(c, hipGetLastError());
-      if (int e = finish(c)) return e;
-    }
-  }
-  return 0;
-}
-
-int pf_rig_stitch_batch_dev(pf_ctx* c, const pf_rig_plan* rig, int n_frames, const uint8_t* const* d_top, const uint8_t* const* d_l, int cols, int rows,
-                            int max_pct, uint8_t* const* d_out, int in_flight) {
-  const char* const what = "pf_rig_stitch_batch_dev";
-  if (int e = use(c)) return e;
-  c->vis_step_valid = false;
-  if (n_frames < 0 || !d_top || !d_l || !d_out) return fail(c, PF_ERR_ARG, "bad argument");
-  if (int e = check_rig(c, rig, cols, rows, what)) return e;
-  if (n_frames == 0) return 0;
-  const int ns = rig->n_steps;
-  if (int e = check_stitch_canvas(c, cols, rows, max_pct)) return e;
-  const size_t n = size_t(cols) * rows, bytes = n * 4;
-  std::vector<const uint8_t*> img(size_t(n_frames) * (ns + 1));   // the verifying launch's table: frame-major (top, L_1 .. L_n)
-  std::vector<uint8_t*> outs;                                     // the caller's composites
-  for (int k = 0; k < n_frames; ++k) {
-    if (!d_top[k]) return fail(c, PF_ERR_ARG, "null device pointer (frame %d)", k);
-    img[size_t(k) * (ns + 1)] = d_top[k];
-    for (int i = 0; i < ns; ++i) {
-      if (!d_l[size_t(k) * ns + i]) return fail(c, PF_ERR_ARG, "null device pointer (frame %d, step %d)", k, i + 1);
-      img[size_t(k) * (ns + 1) + i + 1] = d_l[size_t(k) * ns + i];
-      if (uint8_t* o = d_out[size_t(k) * ns + i]) outs.push_back(o);
-    }
-    if (!d_out[size_t(k) * ns + ns - 1]) return fail(c, PF_ERR_ARG, "frame %d: the last step's d_out must not be NULL", k);
-  }
-  if (int e = check_dev_align(c, what, "image", img.data(), img.size())) return e;
-  if (int e = check_dev_align(c, what, "d_out", outs.data(), outs.size())) return e;
-  // a composite is written while inputs of the call are still read: no aliasing (the rules of pf_stitch_step_batch_dev)
-  for (size_t a = 0; a < outs.size(); ++a) {
-    for (size_t j = 0; j < img.size(); ++j)
-      if (overlaps(outs[a], img[j], bytes)) return fail(c, PF_ERR_ARG, "a d_out of the call overlaps an input of the call (frame %d)", (int)(j / (ns + 1)));
-    for (size_t b = a + 1; b < outs.size(); ++b)
-      if (overlaps(outs[a], outs[b], bytes)) return fail(c, PF_ERR_ARG, "two d_out entries of the call overlap");
-  }
-  const int W = clamp_in_flight(in_flight, n_frames), nwaves = (n_frames + W - 1) / W;
-  std::vector<uint8_t*> comp(size_t(W) * 2);
-  for (int w = 0; w < W; ++w)
-    for (int j = 0; j < 2; ++j) if (!(comp[w * 2 + j] = rig_slot(c, "c", w, j, bytes))) return PF_ERR_NOMEM;
-  const uint8_t** tbl = (const uint8_t**)ensure(c, "rg_tbl", img.size() * sizeof(void*));
-  if (!tbl) return PF_ERR_NOMEM;
-  if (int e = rig_diff_words(c, size_t(n_frames) * ns)) return e;
-  {
-    CallGuard guard_(c);
-    HIPCHK(c, hipMemcpyAsync(tbl, img.data(), img.size() * sizeof(void*), hipMemcpyHostToDevice, c->s_main));
-    const bool vec = all_aligned16(img.data(), img.size());
-    for (int first = 0; first < n_frames; first += 32768) {   // (one launch for any call below the grid's z limit)
-      PROF(c, c->s_main, "rig_verify");
-      launch_rig_maps_verify(c->s_main, tbl + size_t(first) * (ns + 1), vec, rig_maps(rig), ns, std::min(32768, n_frames - first), cols, rows,
-                             c->d_rig_diff + size_t(first) * ns);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (int e = finish(c)) return e;
-  }
-  if (report_rig_diff(c, what, n_frames, ns)) {
-    // the call fails as a whole before any solve; the caller's buffers are cleared, as the planned device form clears them
-    const std::string msg = c->err;
-    CallGuard guard_(c);
-    for (uint8_t* o : outs) HIPCHK(c, hipMemsetAsync(o, 0, bytes, c->s_main));
-    if (int e = finish(c)) return e;
-    return fail(c, PF_ERR_ARG, "%s", msg.c_str());
-  }
-  std::vector<const uint8_t*> dl(W), dr(W);
-  std::vector<uint8_t*> dout(W);
-  for (int wv = 0; wv < nwaves; ++wv) {
-    const int first = wv * W, count = std::min(W, n_frames - first);
-    std::vector<int> tog(count, 0);
-    for (int i = 0; i < ns; ++i) {
-      for (int w = 0; w < count; ++w) {
-        const size_t k = size_t(first + w);
-        dl[w] = d_l[k * ns + i];
-        dr[w] = i == 0 ? d_top[k] : dout[w];   // the previous step's composite, wherever it went
-        uint8_t* o = d_out[k * ns + i];
-        if (!o) { o = comp[w * 2 + tog[w]]; tog[w] ^= 1; }   // never the plane the previous step wrote
-        dout[w] = o;
-      }
-      if (int e = rig_wave_step(c, rig, i, count, dl.data(), dr.data(), dout.data(), cols, rows, max_pct, in_flight, what)) return e;
-    }
-  }
-  return 0;
-}
-int pf_rig_set_upload_overlap(pf_ctx* c, int on) {
-  if (!c) return fail(nullptr, PF_ERR_ARG, "null context");
-  c->rig_overlap_uploads = on != 0;
-  return 0;
-}
-int pf_rig_stitch(pf_ctx* c, const pf_rig_plan* rig, const uint8_t* top, const uint8_t* const* l, int cols, int rows, size_t step, int max_pct, uint8_t* const* out,
-                  size_t ostep) {
-  return pf_rig_stitch_batch(c, rig, 1, top ? &top : nullptr, l, cols, rows, step, max_pct, out, ostep, 1);
-}
-int pf_rig_stitch_dev(pf_ctx* c, const pf_rig_plan* rig, const uint8_t* d_top, const uint8_t* const* d_l, int cols, int rows, int max_pct, uint8_t* const* d_out) {
-  return pf_rig_stitch_batch_dev(c, rig, 1, d_top ? &d_top : nullptr, d_l, cols, rows, max_pct, d_out, 1);
 }

@@ -158,7 +158,7 @@ int pf_tiff_decode(pf_ctx* c, const uint8_t* file, size_t bytes, int cols, int r
   if (!d) return PF_ERR_NOMEM;
   if (int e = tiff_decode_many(c, 1, &file, &bytes, cols, rows, &d)) return e;   // on failure the host image is not written
   c->drained = false;
-  if (int e = download_bgra(c, out_bgra, out_step, d, cols, rows)) return e;
+  if (int e = down_plane(c, out_bgra, out_step, d, cols, rows, 4)) return e;
   return finish(c);
 }
 

@@ -48,12 +48,12 @@ int pf_vis_grey_disparity(pf_ctx* c, const float* flow, size_t fstep, int cols, 
   const size_t n = size_t(cols) * rows;
   float* df = (float*)ensure(c, "vis_flow", n * 8); uint8_t* dout = (uint8_t*)ensure(c, "vis_out", n);
   if (!df || !dout) return PF_ERR_NOMEM;
-  if (int e = up2d(c, df, size_t(cols) * 8, flow, fstep, size_t(cols) * 8, rows)) return e;
+  if (int e = up_plane(c, df, flow, fstep, cols, rows, 8)) return e;
   VisParams* par; void* arrows;
   if (int e = vis_prepare(c, df, cols, rows, true, false, &par, &arrows)) return e;
   { PROF(c, c->s_main, "vis_grey"); launch_vis_grey(c->s_main, df, cols, rows, par, dout); }
   if (int e = vis_finish(c, par)) return e;
-  if (int e = down2d(c, out, ostep, dout, size_t(cols), size_t(cols), rows)) return e;
+  if (int e = down_plane(c, out, ostep, dout, cols, rows, 1)) return e;
   return finish(c);
 }
 
@@ -65,11 +65,11 @@ int pf_vis_color_wheel(pf_ctx* c, const float* flow, size_t fstep, int cols, int
   float* df = (float*)ensure(c, "vis_flow", n * 8); uint8_t* dout = (uint8_t*)ensure(c, "vis_out", n * 3);
   VisParams* par = (VisParams*)ensure(c, "vis_params", sizeof(VisParams));
   if (!df || !dout || !par) return PF_ERR_NOMEM;
-  if (int e = up2d(c, df, size_t(cols) * 8, flow, fstep, size_t(cols) * 8, rows)) return e;
+  if (int e = up_plane(c, df, flow, fstep, cols, rows, 8)) return e;
   HIPCHK(c, hipMemsetAsync(par, 0, sizeof(VisParams), c->s_main));
   { PROF(c, c->s_main, "vis_wheel"); launch_vis_wheel(c->s_main, df, cols, rows, par, dout); }   // counts non-finite components itself
   if (int e = vis_finish(c, par)) return e;
-  if (int e = down2d(c, out, ostep, dout, size_t(cols) * 3, size_t(cols) * 3, rows)) return e;
+  if (int e = down_plane(c, out, ostep, dout, cols, rows, 3)) return e;
   return finish(c);
 }
 
@@ -82,14 +82,14 @@ int pf_vis_vector_field(pf_ctx* c, const float* flow, size_t fstep, const uint8_
   const size_t n = size_t(cols) * rows;
   float* df = (float*)ensure(c, "vis_flow", n * 8); uint8_t* di = (uint8_t*)ensure(c, "vis_img", n * 4); uint8_t* dout = (uint8_t*)ensure(c, "vis_out", n * 4);
   if (!df || !di || !dout) return PF_ERR_NOMEM;
-  if (int e = up2d(c, df, size_t(cols) * 8, flow, fstep, size_t(cols) * 8, rows)) return e;
-  if (int e = up2d(c, di, size_t(cols) * 4, img, istep, size_t(cols) * 4, rows)) return e;
+  if (int e = up_plane(c, df, flow, fstep, cols, rows, 8)) return e;
+  if (int e = up_plane(c, di, img, istep, cols, rows, 4)) return e;
   VisParams* par; void* arrows;
   // the reduction only for its count of non-finite components: every entry point refuses such a flow, not just where an arrow reads it
   if (int e = vis_prepare(c, df, cols, rows, true, true, &par, &arrows)) return e;
   { PROF(c, c->s_main, "vis_field"); launch_vis_field(c->s_main, di, cols, rows, arrows, dout); }
   if (int e = vis_finish(c, par)) return e;
-  if (int e = down2d(c, out, ostep, dout, size_t(cols) * 4, size_t(cols) * 4, rows)) return e;
+  if (int e = down_plane(c, out, ostep, dout, cols, rows, 4)) return e;
   return finish(c);
 }
 
@@ -102,10 +102,10 @@ int pf_vis_panel(pf_ctx* c, const float* flow, size_t fstep, const uint8_t* img,
   const size_t n = size_t(cols) * rows;
   float* df = (float*)ensure(c, "vis_flow", n * 8); uint8_t* di = (uint8_t*)ensure(c, "vis_img", n * 4); uint8_t* dout = (uint8_t*)ensure(c, "vis_out", n * 12);
   if (!df || !di || !dout) return PF_ERR_NOMEM;
-  if (int e = up2d(c, df, size_t(cols) * 8, flow, fstep, size_t(cols) * 8, rows)) return e;
-  if (int e = up2d(c, di, size_t(cols) * 4, img, istep, size_t(cols) * 4, rows)) return e;
+  if (int e = up_plane(c, df, flow, fstep, cols, rows, 8)) return e;
+  if (int e = up_plane(c, di, img, istep, cols, rows, 4)) return e;
   if (int e = vis_panel_dev(c, df, di, cols, rows, dout)) return e;
-  if (int e = down2d(c, out, ostep, dout, size_t(cols) * 12, size_t(cols) * 12, rows)) return e;
+  if (int e = down_plane(c, out, ostep, dout, cols, rows, 12)) return e;
   return finish(c);
 }
 
@@ -138,7 +138,7 @@ int pf_stitch_visualize(pf_ctx* c, uint8_t* l2r_panel, uint8_t* r2l_panel, size_
   for (int d = 0; d < 2; ++d) {
     if (!outs[d]) continue;
     if (int e = vis_panel_dev(c, (const float*)c->bufs[flows[d]].p, (const uint8_t*)c->bufs[imgs[d]].p, cols, rows, dout)) return e;
-    if (int e = down2d(c, outs[d], step, dout, size_t(cols) * 12, size_t(cols) * 12, rows)) return e;
+    if (int e = down_plane(c, outs[d], step, dout, cols, rows, 12)) return e;
     if (int e = finish(c)) return e;
   }
   return 0;

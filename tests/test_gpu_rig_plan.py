@@ -156,6 +156,37 @@ def test_step_handles_are_stitch_plans(pf, synth, rig_a):
 
 
 @pytest.mark.gpu
+def test_plan_lifetime_across_owners(pf):
+    """two stitch plans and a rig's step plans live in one list: the rig's end takes its steps out and leaves the others whole, a plan's end
+    leaves its neighbour whole, and the context's end takes what is left"""
+    cols, rows = 240, 200
+    top, Ls = window_set(cols, rows, 2, 41)
+    Rs = stand_ins(top, Ls)
+    c = pf.Context(0)
+    plans = [c.stitch_plan(Ls[i], Rs[i]) for i in range(2)]
+    rg = c.rig_plan(top, Ls)
+    before = [p.download() for p in plans]
+    assert not np.array_equal(before[0][0], before[1][0]), "the two plans were meant to differ"
+    h = C.c_void_p(rg.steps[0].h.value)   # what pf_rig_plan_step returned
+    rg.close()
+    sz = C.c_size_t(cols * 4)
+    out = np.empty((rows, cols, 4), np.uint8); mp = np.empty((rows, cols), np.uint8)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    for name, call in (("pf_stitch_plan_download", lambda: c.l.pf_stitch_plan_download(c.h, h, ptr(mp), C.c_size_t(cols), None, sz)),
+                       ("pf_stitch_step_planned", lambda: c.l.pf_stitch_step_planned(c.h, h, ptr(Ls[0]), ptr(top), cols, rows, sz, PCT, ptr(out), sz)),
+                       ("pf_stitch_plan_destroy", lambda: c.l.pf_stitch_plan_destroy(c.h, h))):
+        assert call() == -1, name
+        assert name.encode() + b": not a live stitch plan" in c.l.pf_last_error(c.h)
+    for i, p in enumerate(plans):
+        _same_plan(p, before[i] + (p.overlap_px,), "stitch plan %d after the rig's end" % i)
+    plans[0].close()
+    want = c.stitch_step(Ls[1], Rs[1], PCT)
+    got = c.stitch_step(Ls[1], Rs[1], PCT, plan=plans[1])
+    assert np.array_equal(got, want), "planned step after its neighbour's end: %d bytes differ" % _ndiff(got, want)
+    c.close()   # with plans[1] still live
+
+
+@pytest.mark.gpu
 def test_rig_plans_that_are_refused(pf, rig_a):
     top, imgs = rig_a
     c = pf.Context(0); other = pf.Context(0)
