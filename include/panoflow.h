@@ -576,6 +576,52 @@ int pf_tiff_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int
 int pf_tiff_decode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, int cols, int rows,
                              uint8_t* const* d_out_bgra);
 
+/* ---- JPEG files decoded on the device -------------------------------------------------------
+ * The counterpart of the JPEG encoder: the bytes of a baseline JPEG file (HOST memory) go up as they are and come out as packed
+ * BGRA, alpha 255, byte for byte Pillow's Image.open(file).convert("RGB") (libjpeg-turbo's integer IDCT, fancy upsampling and colour
+ * transform); grey files give B = G = R = Y.  The scan's one Huffman stream is decoded in parallel by self-synchronising lanes over
+ * subsequences of the entropy segment, so files without restart markers decode in parallel, too.  Opt-in: no other
+ * entry point's behaviour depends on these.
+ * Accepted, checked on the host before any device work: baseline SOF0, 8-bit samples, 8-bit quantisation tables, Huffman tables 0..3,
+ * one component or Y Cb Cr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, one interleaved scan, any restart interval, sides up to
+ * 65535.  APPn and COM segments are skipped; EXIF orientation and ICC profiles are ignored.  Everything else -- progressive, extended,
+ * lossless and arithmetic frames, 12-bit samples, four components, other samplings, several scans, DNL, a file libjpeg would read as
+ * RGB, a Huffman table libjpeg refuses, a missing table, another size than the caller expects -- is PF_ERR_ARG with the reason.
+ *   pf_jpeg_probe   host only, needs no device; ctx may be NULL.  out->struct_size must be set to sizeof(pf_jpeg_info).  PF_OK for
+ *                   anything that begins as a JPEG: device_decodable says whether the decode calls take it, `reason` why not (cols,
+ *                   rows and components are then what the frame header gave, 0 where it was not reached).  subsampling: 0 grey,
+ *                   444, 422 or 420.
+ *   cols, rows      what the caller expects, as learned from the probe; a file of another size is PF_ERR_ARG before any work.
+ *   _dev            d_out_bgra: device memory of this context's device, cols * rows * 4 bytes, packed rows, 4-byte aligned.
+ *   pf_jpeg_decode  delivers to HOST memory with a row step of out_step bytes; bytes of a row beyond cols * 4 are left untouched.
+ *   batch           n same-size files, which may differ in tables, subsampling and interval -> the bytes of n single calls; every
+ *                   step's kernels of all files are enqueued before the step's one drain.  Outputs must not overlap.
+ * A scan is accepted exactly when its decode meets no event: every code valid, every run inside its block, every restart interval
+ * holding exactly its MCUs and followed by its own RSTn, the last by EOI after at most 7 pad bits.  libjpeg tolerates such events
+ * with a warning; the device path refuses the file with PF_ERR_ARG, pf_last_error names the file and the MCU where decoding stopped,
+ * the device forms zero-fill their outputs (all of them, in the batch form) and the host form writes nothing.  IDCT outputs beyond
+ * libjpeg's range table are clamped to 0..255.  A synchronisation that does not settle within its bound of launches (never expected) is
+ * PF_ERR_DEVICE and zero-fills the device outputs, too.
+ *   pf_stage_jpeg_decode   the stage hook for the tests: one file decoded as above; states_out receives every subsequence's final
+ *                   exit state (4 words each: bit, block in MCU | zigzag index << 8, blocks completed, markers crossed; subsequence
+ *                   i enters where i - 1 left), coef_out the coefficient plane (64 int16 per block in MCU order, zigzag order, DC
+ *                   summed), planes_out the component planes (Y, then Cb and Cr, at their block-padded sizes); the caps are in bytes.
+ *                   counts_out: [0] subsequences, [1] rounds, [2] launches to the fixed point, [3] the subsequence size,
+ *                   [4] subsequences whose exit state changed after their first walk (one that changed in two launches counts twice).
+ * The scratch is the decoder's own: these calls leave alone the chain state, the prefetch records, the frame slots, the plans and
+ * every other family's scratch.  Kernel families in pf_profile_*: jpegd_sync, jpegd_write, jpegd_pixels. */
+typedef struct pf_jpeg_info {
+  int struct_size, cols, rows, components, subsampling, restart_interval, device_decodable;
+  char reason[128];
+} pf_jpeg_info;
+int pf_jpeg_probe(pf_ctx* ctx, const uint8_t* file, size_t bytes, pf_jpeg_info* out);
+int pf_jpeg_decode_dev(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* d_out_bgra);
+int pf_jpeg_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, int cols, int rows, uint8_t* out_bgra, size_t out_step);
+int pf_jpeg_decode_batch_dev(pf_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, int cols, int rows,
+                             uint8_t* const* d_out_bgra);
+int pf_stage_jpeg_decode(pf_ctx* ctx, const uint8_t* file, size_t bytes, uint32_t* states_out, size_t states_cap, int16_t* coef_out,
+                         size_t coef_cap, uint8_t* planes_out, size_t planes_cap, int* counts_out);
+
 /* ---- Resize on the device --------------------------------------------------------------------
  * A packed BGRA image at another size, byte for byte what Pillow's Image.resize(size, filter) gives for the same bytes as an RGBA
  * image (the three colour channels are treated alike, so the channel order does not matter): an antialiased separable resample --

@@ -20,12 +20,13 @@
 #include "png_frame.hpp"
 #include "jpeg_frame.hpp"
 #include "tiff_parse.hpp"
+#include "jpeg_parse.hpp"
 #include "resize_table.hpp"
 
 using namespace pf;
 
 
-// One translation unit in fifteen parts (the anonymous namespace and the extern "C" block span several of them):
+// One translation unit in sixteen parts (the anonymous namespace and the extern "C" block span several of them):
 #include "pf_api_ctx.inl"      // pf_ctx, errors / warnings, arena, profiling events, geometry, checks
 #include "pf_api_solve.inl"    // run_level, solve buffers, solve / solve_n (stream orchestration)
 #include "pf_api_life.inl"     // finish / CallGuard, pf_create* / pf_destroy, memory helpers            (opens extern "C")
@@ -38,6 +39,7 @@ using namespace pf;
 #include "pf_api_png.inl"      // pf_png_*, pf_stitch_result_png (PNG files made on the device)
 #include "pf_api_tiff.inl"     // pf_tiff_* (TIFF files decoded on the device)
 #include "pf_api_jpeg.inl"     // pf_jpeg_*, pf_stitch_result_jpeg (JPEG files made on the device)
+#include "pf_api_jpegd.inl"    // pf_jpeg_probe, pf_jpeg_decode* (JPEG files decoded on the device)
 #include "pf_api_resize.inl"   // pf_resize*, pf_stitch_result_resized_dev (Pillow's resample on the device)
 #include "pf_api_reproject.inl"   // pf_reproject*, pf_stitch_result_reprojected_dev (cube faces, views, a turned sphere)
 #include "pf_api_lens.inl"        // pf_lens_* (raw photos of a rig remapped onto the canvas: fisheye and rectilinear lenses)

@@ -319,4 +319,27 @@ void launch_tiff_packbits(hipStream_t st, const TiffWork& w);   // file -> plane
 void launch_tiff_inflate(hipStream_t st, const TiffWork& w);    // file -> plane, status
 void launch_tiff_finish(hipStream_t st, const TiffWork& w, bool from_file /* compression 1: samples read from the file */, uint8_t* bgra /* packed, 4-byte aligned */);
 
+// ---- JPEG decoder (kernels_jpegd.hip): self-synchronising Huffman decode over subsequences, DC sums, IDCT, upsampling and colour ----
+constexpr unsigned kJpegdSubseq = 64;       // the product's subsequence size S in bytes: measured, DESIGN.md 8.10, profiles/jpeg_decode_ab.txt
+constexpr unsigned kJpegdSubseqMin = 32, kJpegdSubseqMax = 1024;   // what the lab build's PANOFLOW_JPEGD_SUBSEQ may choose (powers of two)
+constexpr unsigned kJpegdLanes = 256;       // subsequences per workgroup of the entropy kernels
+struct JpegdWork {
+  const uint8_t* seg;          // the entropy segment inside the uploaded file
+  unsigned seg_bytes, S, nsub; // ... its bytes, the subsequence size, ceil(seg_bytes / S) (at least 1)
+  int ncomp, hs, vs;           // 1 or 3 components; luma sampling (chroma is 1 x 1)
+  unsigned restart, cols, rows;
+  const void* tables;          // a jpeg_parse::Tables in device memory
+  void* states[2];             // nsub x 16 bytes each: the lanes' exit states, read from one and written to the other
+  unsigned* words;             // [0] changed, [1] rounds of the launch, [2] the MCU of the true path's first event (0xFFFFFFFF: none);
+                               // [3] lanes whose record changed after their first walk, summed over the launches
+  void* first;                 // nsub x 8 bytes: blocks and markers before each subsequence
+  int16_t* coef;               // 64 int16 per block in MCU order, zigzag order; zeroed before the write pass
+  uint8_t* planes;             // Y, then Cb and Cr, at their block-padded sizes
+  unsigned* dcsum;             // intervals x components x jpegd_dc_chunks() words: the DC pass's chunk sums
+};
+unsigned jpegd_dc_chunks(int ncomp, int hs, int vs, unsigned restart, unsigned nmcu);   // workgroups per (interval, component) of the DC pass
+void launch_jpegd_sync(hipStream_t st, const JpegdWork& w, int first /* the first launch: lanes guess */, int from /* states[from] -> states[1 - from] */);
+void launch_jpegd_write(hipStream_t st, const JpegdWork& w, int from);   // states[from] -> first, coef, words[2]
+void launch_jpegd_pixels(hipStream_t st, const JpegdWork& w, uint8_t* bgra /* packed, 4-byte aligned; null: planes only */);   // coef -> planes -> bgra
+
 }  // namespace pf

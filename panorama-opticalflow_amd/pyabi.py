@@ -76,6 +76,12 @@ class TiffInfo(C.Structure):
                                         "device_decodable")]
 
 
+class JpegInfo(C.Structure):
+    """pf_jpeg_info (include/panoflow.h)"""
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "cols", "rows", "components", "subsampling", "restart_interval", "device_decodable")] + \
+               [("reason", C.c_char * 128)]
+
+
 def lib(exp=False):
     """exp=False: the product library.  exp=True: the lab build with the cross-check sweeps (tests / diagnostics only)."""
     _lib = _libs.get(bool(exp))
@@ -138,6 +144,11 @@ def lib(exp=False):
         _lib.pf_tiff_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
         _lib.pf_tiff_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         _lib.pf_tiff_decode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_jpeg_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(JpegInfo)]
+        _lib.pf_jpeg_decode_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        _lib.pf_jpeg_decode_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        _lib.pf_stage_jpeg_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib.pf_resize_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
         _lib.pf_resize.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]
         _lib.pf_resize_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]
@@ -190,6 +201,7 @@ EXPORTS = [
     "pf_jpeg_params_init", "pf_jpeg_bound", "pf_jpeg_restart_interval", "pf_jpeg_encode_dev", "pf_jpeg_encode", "pf_jpeg_encode_batch_dev",
     "pf_stitch_result_jpeg", "pf_stitch_batch_result_jpeg",
     "pf_tiff_probe", "pf_tiff_set_inflate", "pf_tiff_device_decodable", "pf_tiff_decode_dev", "pf_tiff_decode", "pf_tiff_decode_batch_dev",
+    "pf_jpeg_probe", "pf_jpeg_decode_dev", "pf_jpeg_decode", "pf_jpeg_decode_batch_dev", "pf_stage_jpeg_decode",
     "pf_resize_dev", "pf_resize", "pf_resize_batch_dev", "pf_stitch_result_resized_dev", "pf_stitch_batch_result_resized_dev", "pf_stage_resize_pass",
     "pf_reproject_params_init", "pf_reproject_rotation", "pf_reproject_dev", "pf_reproject", "pf_reproject_batch_dev", "pf_reproject_cube_dev",
     "pf_stitch_result_reprojected_dev", "pf_stitch_batch_result_reprojected_dev", "pf_stage_reproject_coords",
@@ -394,6 +406,16 @@ def tiff_probe(data):
 def tiff_device_decodable(info, ctx=None):
     """would the decode calls of `ctx` (a Context; None: default settings) take the probed file?  (pf_tiff_device_decodable)"""
     return bool(lib().pf_tiff_device_decodable(ctx.h if ctx is not None else None, C.byref(info)))
+
+
+def jpeg_probe(data):
+    """JpegInfo of a JPEG file's bytes (pf_jpeg_probe: host only, no device needed).  device_decodable says whether the decode calls
+    take the file and `reason` why not; raises only for bytes that do not begin as a JPEG"""
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    info = JpegInfo(); info.struct_size = C.sizeof(JpegInfo)
+    if lib().pf_jpeg_probe(None, _p(buf), C.c_size_t(len(data)), C.byref(info)) != 0:
+        raise PanoflowError(lib().pf_last_error(None).decode())
+    return info
 
 
 def png_segment_bytes():
@@ -867,6 +889,41 @@ class Context:
         bufs = [np.frombuffer(bytes(d), np.uint8) for d in datas]
         files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)(*[b.size for b in bufs])
         self._chk(self.l.pf_tiff_decode_batch_dev(self.h, n, files, sizes, cols, rows, _dptrs(d_outs, n)))
+
+    # ---- JPEG files decoded on the device (pf_jpeg_decode*): `data` = the file's bytes ----
+    def jpeg_decode(self, data, shape=None, row_step=None, out=None):
+        """file bytes -> host BGRA (rows, cols, 4); shape = (rows, cols) the caller expects (default: the probe's).  row_step (bytes) or
+        out (an array whose rows are row_step apart) selects a padded destination; the padding is left as it is"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        if shape is None:
+            info = jpeg_probe(data); shape = (info.rows, info.cols)
+        rows, cols = shape
+        step = int(row_step) if row_step is not None else cols * 4
+        if out is None:
+            out = np.empty((rows, step), np.uint8)
+        self._chk(self.l.pf_jpeg_decode(self.h, _p(buf), C.c_size_t(buf.size), cols, rows, _p(out), C.c_size_t(step)))
+        return out[:, :cols * 4].reshape(rows, cols, 4)
+
+    def jpeg_decode_dev(self, data, cols, rows, d_out):
+        buf = np.frombuffer(bytes(data), np.uint8)
+        self._chk(self.l.pf_jpeg_decode_dev(self.h, _p(buf), C.c_size_t(buf.size), cols, rows, C.c_void_p(d_out)))
+
+    def jpeg_decode_batch_dev(self, datas, cols, rows, d_outs):
+        """n same-size files -> n device images"""
+        n = len(datas)
+        bufs = [np.frombuffer(bytes(d), np.uint8) for d in datas]
+        files = (C.c_void_p * n)(*[b.ctypes.data for b in bufs]); sizes = (C.c_size_t * n)(*[b.size for b in bufs])
+        self._chk(self.l.pf_jpeg_decode_batch_dev(self.h, n, files, sizes, cols, rows, _dptrs(d_outs, n)))
+
+    def stage_jpeg_decode(self, data, nsub, nblocks, plane_bytes):
+        """pf_stage_jpeg_decode: -> (states (nsub, 4) uint32, coef (nblocks, 64) int16, planes (plane_bytes,) uint8, counts (5,) int32:
+        subsequences, rounds, launches, subsequence size, subsequences that changed after their first walk).  The caller gives the sizes (from the header's geometry)"""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        states = np.zeros((nsub, 4), np.uint32); coef = np.zeros((nblocks, 64), np.int16); planes = np.zeros(plane_bytes, np.uint8)
+        counts = np.zeros(5, np.int32)
+        self._chk(self.l.pf_stage_jpeg_decode(self.h, _p(buf), C.c_size_t(buf.size), _p(states), C.c_size_t(states.nbytes), _p(coef), C.c_size_t(coef.nbytes),
+                                              _p(planes), C.c_size_t(planes.nbytes), _p(counts)))
+        return states, coef, planes, counts
 
     # ---- resize on the device (pf_resize*): Pillow's Image.resize of an RGBA image, byte for byte; filter = one of RESIZE_* ----
     def resize(self, image, out_cols, out_rows, filter=RESIZE_LANCZOS, out=None):

@@ -62,6 +62,12 @@
 //   photos into device buffers and remaps them there (pf_lens_remap_batch_dev, one launch per directory when the photos have one size), so
 //   that no raw image crosses the link.  The canvas is 360 degrees across with square angular pixels, centred on the horizon.  Agreement
 //   with Hugin's nona is not claimed.
+//   -input_ext jpg (any mode; default tif; needs -lens_rig and -canvas): the photos are 1.jpg .. 5.jpg -- what a camera writes -- and are
+//   decoded on the GPU (pf_jpeg_decode*, DESIGN.md 8.10: baseline files, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0).  The top image is as
+//   -top_img names it; a .jpg or .jpeg top image is decoded the same way.  A JPEG has no alpha, so the flag is refused without -lens_rig,
+//   whose remap makes the masks.  There is no host JPEG reader: the host-image modes call pf_jpeg_decode, and -rig_chain 1 -tiff_device 1
+//   decodes a directory's photos in one pf_jpeg_decode_batch_dev per photo size into the buffers pf_lens_remap_batch_dev reads.  A file
+//   outside the decoder's contract or with a damaged scan ends the run with the library's reason.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -173,9 +179,35 @@ static pf_lens lensOf(const std::string& path, int cols, int rows) {
     throw VrCamException("-lens_rig: " + path + " is " + std::to_string(cols) + "x" + std::to_string(rows) + ", not the " + std::to_string(im->w()) + "x" + std::to_string(im->h()) + " of its description");
   return lens_rig::to_lens(*im, PF_REPROJECT_BICUBIC);
 }
+static std::string g_input_ext = "tif";   // -input_ext tif|jpg: the extension of <1..steps>.<ext>
+static bool isJpegName(const std::string& path) {
+  const size_t dot = path.rfind('.'); std::string ext = dot == std::string::npos ? "" : path.substr(dot + 1);
+  for (auto& c : ext) c = (char)tolower(c);
+  return ext == "jpg" || ext == "jpeg";
+}
+// a JPEG file's bytes and what the decoder's probe says of them; a file the device does not decode ends the run with the reason
+static std::vector<unsigned char> readJpegFile(const std::string& path, pf_jpeg_info* info) {
+  if (g_lens_rig.empty()) throw VrCamException("a JPEG input needs -lens_rig FILE and -canvas WxH (a JPEG has no alpha; the remap makes the masks): " + path);
+  std::vector<unsigned char> b = pano_io::read_file(path);
+  info->struct_size = sizeof *info;
+  if (pf_jpeg_probe(nullptr, b.data(), b.size(), info) != 0) throw VrCamException(std::string("panoflow: ") + pf_last_error(nullptr) + ": " + path);
+  if (!info->device_decodable) throw VrCamException(std::string("panoflow: jpeg: ") + info->reason + ": " + path);
+  return b;
+}
 // an image file to a host image, by the host readers or (a .tif under the device rule, see the usage note) through the device decoder;
 // with -lens_rig the file is a raw photo and the image its canvas
 static Mat readImage(const std::string& path) {
+  if (isJpegName(path)) {   // (always a raw photo: readJpegFile refuses it without -lens_rig)
+    pf_jpeg_info info;
+    const std::vector<unsigned char> b = readJpegFile(path, &info);
+    Mat photo(info.rows, info.cols, CV_8UC4);
+    if (pf_jpeg_decode(pano::context(), b.data(), b.size(), info.cols, info.rows, photo.data, photo.step) != 0)
+      throw VrCamException(std::string("panoflow: ") + pf_last_error(pano::context()) + ": " + path);
+    const pf_lens lens = lensOf(path, photo.cols, photo.rows);
+    Mat canvas(g_canvas_rows, g_canvas_cols, CV_8UC4);
+    pano::check(pf_lens_remap(pano::context(), photo.data, photo.step, photo.cols, photo.rows, canvas.data, canvas.step, canvas.cols, canvas.rows, &lens));
+    return canvas;
+  }
   Mat raw = g_tiff_device ? pano_io::imread_device(path, tiffContext()) : pano_io::imreadExceptionOnFail(path);
   if (g_lens_rig.empty()) return raw;
   if (raw.type() != CV_8UC4) throw VrCamException("-lens_rig: " + path + " is not a CV_8UC4 image");
@@ -240,7 +272,7 @@ static void stitchVisualizations(int cols, int rows, const std::string& dir, con
 static int run4Input(const std::string& dir, const std::string& flow_alg) {
   double StartTime = getCurrTimeSec();
   Mat im[4];
-  for (int i = 0; i < 4; ++i) im[i] = readImage(dir + "/" + char(i + 49) + ".tif");
+  for (int i = 0; i < 4; ++i) im[i] = readImage(dir + "/" + char(i + 49) + "." + g_input_ext);
   for (int i = 1; i < 4; ++i)
     if (im[i].rows != im[0].rows || im[i].cols != im[0].cols) throw VrCamException("4-input mode: the four photos must have the same size");
   const int rows = im[0].rows, cols = im[0].cols;
@@ -288,7 +320,7 @@ static int runBatchDirs(const std::vector<std::string>& dirs, const std::string&
   for (int k = 0; k < n; ++k) tops[k] = readImage(dirs[k] + "/" + top_img);
   for (int i = 1; i <= nsteps; i++) {
     double StepStart = getCurrTimeSec();
-    for (int k = 0; k < n; ++k) Ls[k] = readImage(dirs[k] + "/" + char(i + 48) + ".tif");
+    for (int k = 0; k < n; ++k) Ls[k] = readImage(dirs[k] + "/" + char(i + 48) + "." + g_input_ext);
     std::vector<const uint8_t*> l(n), r(n);
     std::vector<uint8_t*> o(n);
     for (int k = 0; k < n; ++k) {
@@ -349,7 +381,7 @@ static int runRigChain(const std::vector<std::string>& dirs, const std::string& 
   std::vector<uint8_t*> o(size_t(n) * nsteps);
   for (int k = 0; k < n; ++k) {
     tops[k] = readImage(dirs[k] + "/" + top_img);
-    for (int i = 0; i < nsteps; ++i) Ls[size_t(k) * nsteps + i] = readImage(dirs[k] + "/" + char(i + 49) + ".tif");
+    for (int i = 0; i < nsteps; ++i) Ls[size_t(k) * nsteps + i] = readImage(dirs[k] + "/" + char(i + 49) + "." + g_input_ext);
   }
   auto same = [&](const Mat& m) { return m.type() == CV_8UC4 && m.rows == tops[0].rows && m.cols == tops[0].cols && m.step == tops[0].step; };
   for (int k = 0; k < n; ++k) {
@@ -412,10 +444,23 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
   struct Raw { uint8_t* d; int cols, rows; pf_lens lens; uint8_t* canvas; };
   std::vector<Raw> raws;
   DevImages raw_dev{ctx, {}};
+  // JPEG photos: their bytes wait on the host until remapRaws() decodes those of one size in one call, into their raw buffers
+  struct Jpeg { std::vector<unsigned char> bytes; uint8_t* d; int cols, rows; std::string path; };
+  std::vector<Jpeg> jpegs;
   auto load = [&](const std::string& path) {
     int c = 0, r = 0;
     if (!g_lens_rig.empty()) {
-      raw_dev.p.push_back(pano_io::imread_to_device(path, ctx, &c, &r));
+      if (isJpegName(path)) {
+        pf_jpeg_info info;
+        std::vector<unsigned char> b = readJpegFile(path, &info);
+        c = info.cols; r = info.rows;
+        uint8_t* d = (uint8_t*)pf_dev_alloc(ctx, size_t(c) * r * 4);
+        if (!d) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
+        raw_dev.p.push_back(d);
+        jpegs.push_back(Jpeg{std::move(b), d, c, r, path});
+      } else {
+        raw_dev.p.push_back(pano_io::imread_to_device(path, ctx, &c, &r));
+      }
       cols = g_canvas_cols; rows = g_canvas_rows;
       uint8_t* canvas = (uint8_t*)pf_dev_alloc(ctx, size_t(cols) * rows * 4);
       if (!canvas) throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx));
@@ -430,6 +475,21 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
   };
   // the waiting photos onto their canvases, the photos of one size in one call (a rig's cameras: one launch), then the photos freed
   auto remapRaws = [&]() {
+    {
+      std::vector<bool> decoded(jpegs.size(), false);
+      for (size_t a = 0; a < jpegs.size(); ++a) {
+        if (decoded[a]) continue;
+        std::vector<const uint8_t*> files; std::vector<size_t> sizes; std::vector<uint8_t*> dst; std::string names;
+        for (size_t b = a; b < jpegs.size(); ++b)
+          if (!decoded[b] && jpegs[b].cols == jpegs[a].cols && jpegs[b].rows == jpegs[a].rows) {
+            files.push_back(jpegs[b].bytes.data()); sizes.push_back(jpegs[b].bytes.size()); dst.push_back(jpegs[b].d); decoded[b] = true;
+            names += " " + std::to_string(files.size() - 1) + "=" + jpegs[b].path;
+          }
+        if (pf_jpeg_decode_batch_dev(ctx, (int)files.size(), files.data(), sizes.data(), jpegs[a].cols, jpegs[a].rows, dst.data()) != 0)
+          throw VrCamException(std::string("panoflow: ") + pf_last_error(ctx) + " (files:" + names + ")");
+      }
+      jpegs.clear();
+    }
     std::vector<bool> done(raws.size(), false);
     for (size_t a = 0; a < raws.size(); ++a) {
       if (done[a]) continue;
@@ -443,7 +503,7 @@ static int runRigChainDevice(const std::vector<std::string>& dirs, const std::st
   };
   for (int k = 0; k < n; ++k) {
     t[k] = load(dirs[k] + "/" + top_img);
-    for (int i = 0; i < nsteps; ++i) l[size_t(k) * nsteps + i] = load(dirs[k] + "/" + char(i + 49) + ".tif");
+    for (int i = 0; i < nsteps; ++i) l[size_t(k) * nsteps + i] = load(dirs[k] + "/" + char(i + 49) + "." + g_input_ext);
     remapRaws();
   }
   for (size_t at = 0; at < o.size(); ++at) {
@@ -549,6 +609,12 @@ int main(int argc, char** argv) {
       catch (const lens_rig::ParseError& e) { throw VrCamException("-lens_rig: " + g_lens_rig_file + ": " + e.what()); }
       if (g_lens_rig.empty()) throw VrCamException("-lens_rig: " + g_lens_rig_file + " describes no image (no `i` line)");
     }
+    if (flags.count("input_ext")) {   // (refused before any device call)
+      g_input_ext = flags["input_ext"];
+      if (g_input_ext != "tif" && g_input_ext != "jpg") throw VrCamException("-input_ext must be tif or jpg");
+      if (g_input_ext == "jpg" && g_lens_rig.empty())
+        throw VrCamException("-input_ext jpg needs -lens_rig FILE and -canvas WxH (a JPEG has no alpha; the remap makes the masks)");
+    }
     g_tiff_device = flags.count("tiff_device") && atoi(flags["tiff_device"].c_str()) != 0;
     g_tiff_inflate = flags.count("tiff_inflate") && atoi(flags["tiff_inflate"].c_str()) != 0;   // (read only on the -tiff_device 1 paths)
     if (flags.count("test_dirs")) {   // every refusal before any device call
@@ -593,7 +659,7 @@ int main(int argc, char** argv) {
     for (int i = 1; i <= nsteps; i++) {
       double StepStart = getCurrTimeSec();
       if (i == 1) colorImageR = colorImageT; else colorImageR = FinalResult;
-      colorImageL = readImage(FLAGS_test_dir + "/" + char(i + 48) + ".tif");
+      colorImageL = readImage(FLAGS_test_dir + "/" + char(i + 48) + "." + g_input_ext);
 
       if (fused && (g_png_device || g_jpeg_device)) {
         // the composite stays in HBM (out_bgra = NULL) for the next step to chain on and for the encoder: only its PNG or JPEG comes down
